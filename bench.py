@@ -9,9 +9,13 @@ Workload (BASELINE.json configs[1], "cfg2" of SURVEY.md 8(d)): synthetic 256x256
 PER GPU (weak scaling; cfg3 = 8 x 16), UNet nf=64 leakyrelu/sigmoid, Discriminator ndf=64 n_layers=3 norm=False,
 focal-Tversky x 200 + BCE, Adam lr 1e-3, fp32, random-init weights, inputs resident in HBM before timing.
 
-Prints ONE JSON line on rank 0.  `roofline` is measured live with HIP events around every launch of the conv
-kernels in the timed region; `cpu_baseline` times the CPU oracle (oracle/, the restatement pinned to the
-reference's goldens) on this box's host cores for a bounded sample of the same workload (rank 0, N=1 only).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline (`value`,
+`ms_per_step`, ...).  `--full` adds what takes measurements of its own: `roofline` and `conv_kernels` (HIP events around the
+launches of the conv kernels), `comm` under data parallelism, `cpu_baseline` (the CPU oracle -- oracle/, the restatement
+pinned to the reference's goldens -- on the host cores for a bounded sample of the same workload; rank 0, N=1 only) and
+`extra_configs` (the other single-GPU configurations).  `--dump-outputs DIR` writes what the last timed step computed as
+.npy files (dump_outputs); the inputs and the number of steps before it are fixed by the arguments, so two builds can be
+compared output for output.
 """
 import argparse
 import json
@@ -52,6 +56,48 @@ def make_inputs(batch, rank, cfg=None):
     x = torch.rand(batch, 3, cfg['size'], cfg['size'], generator=g)
     y = (torch.rand(batch, cfg['out_nc'], cfg['size'], cfg['size'], generator=g) > 0.7).float()
     return x, y
+
+
+DUMP_CAP = 4 << 20        # values per dumped array (16 MiB in float32): a longer output is written as a fixed, seeded sample
+
+
+def _dump_sample(v, seed):
+    """The 1-D device tensor `v` on the host: whole if it has at most DUMP_CAP values, else the DUMP_CAP of them at positions drawn
+    (sorted, without repetition) by numpy's default_rng(seed) -- the same positions in every run of the same workload."""
+    import numpy as np
+    import torch
+    if v.numel() <= DUMP_CAP:
+        return v.cpu().numpy()
+    idx = np.sort(np.random.default_rng(seed).choice(v.numel(), DUMP_CAP, replace=False))
+    return v[torch.from_numpy(idx).to(v.device)].cpu().numpy()
+
+
+def dump_outputs(folder, t, losses):
+    """What the timed path, Trainer.batch(x, y, train=True), left its caller after the last timed step, as folder/<name>.npy
+    (at most ~32 MiB in all):
+      loss_<key>.npy      float64 scalar: the step's losses (StepLosses.KEYS, the dict batch() returns)
+      generator.npy       float32: the generator's weights after the step -- every state_dict() tensor in key order, flattened and
+      discriminator.npy   concatenated (the reference's layout) -- / the discriminator's; sampled as in _dump_sample"""
+    import numpy as np
+    import torch
+    os.makedirs(folder, exist_ok=True)
+    for k in losses.KEYS:
+        np.save(os.path.join(folder, f'loss_{k}.npy'), np.float64(losses[k]))
+    for seed, (name, net) in enumerate((('generator', t.generator), ('discriminator', t.discriminator))):
+        flat = torch.cat([v.detach().reshape(-1) for v in net.state_dict().values() if v.is_floating_point()])
+        np.save(os.path.join(folder, name + '.npy'), _dump_sample(flat.float(), seed))
+    torch.cuda.synchronize()
+
+
+def planned_split_bf16(G, D, batch, size):
+    """Whether the conv kernels the planner picks for this step hold a split-bf16 GEMM (k_*_s3: every fp32 product as six bf16
+    MFMA products): asked of the C ABI (pg_conv_kernel, ConvOp.describe) for each layer of both networks at the step's extents
+    (D at N and at 2N) -- no launch, no events."""
+    from patchgan_amd import _lib as L
+    enc, dec = G.engine.ops(batch, size, size)
+    ops = list(enc) + list(dec) + list(D.engine.ops(batch, size, size)) + list(D.engine.ops(2 * batch, size, size))
+    io = L.IO_MASK if G.engine.act_bf else 0
+    return any('_s3<' in op.describe(oc, io)[0] for op in ops if op.algo & L.ALGO_MASK != L.ALGO_DIRECT for oc in (0, 1, 2))
 
 
 def pmc_traffic(symbol):
@@ -285,9 +331,14 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline does not need: roofline and per-kernel table, communication statistics, '
+                         'CPU baseline, extra configurations')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write what the last one computed as DIR/<name>.npy (dump_outputs)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU-oracle legs')
     ap.add_argument('--no-extra', action='store_true',
-                    help='skip the extra_configs leg (cfg4 bf16 training, cfg5 tiled inference) measured after the headline')
+                    help='with --full: skip the extra_configs leg (cfg4 bf16 training, cfg5 tiled inference) measured after the headline')
     ap.add_argument('--dropout', action='store_true', help='nn.Dropout(0.2) in the generator (CLI default of the reference)')
     ap.add_argument('--no-graph', action='store_true',
                     help='enqueue every step launch by launch (default on one GPU with dropout off: the steady-state step is replayed from a captured hipGraph)')
@@ -297,8 +348,10 @@ def main():
     ap.add_argument('--fp32-activations', action='store_true',
                     help='with --dtype bf16: keep the activations fp32 in HBM (round-1 behaviour) instead of bf16 activation storage')
     ap.add_argument('--events', choices=['dominant', 'all', 'none'], default='dominant',
-                    help='which conv launches get HIP events in the timed region (roofline leg)')
+                    help='with --full: which conv launches get HIP events in the timed region (roofline leg)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
     global CFG, GFLOP_PER_IMAGE, BATCH_PER_GPU, SIZE
     CFG = CONFIGS[args.config]
     GFLOP_PER_IMAGE, BATCH_PER_GPU, SIZE = CFG['gflop_per_image'], CFG['batch'], CFG['size']
@@ -346,7 +399,8 @@ def main():
             raise SystemExit(f"process group has {dist.get_world_size()} ranks, expected {args.gpus}")
 
     m = measure_training(CFG, args.dtype, args.steps, args.warmup, dev, rank, world, use_dist, events=args.events,
-                         dropout=args.dropout, fp32_activations=args.fp32_activations, graph=not args.no_graph)
+                         dropout=args.dropout, fp32_activations=args.fp32_activations, graph=not args.no_graph, full=args.full,
+                         dump_dir=args.dump_outputs)
     if rank == 0:
         out = {
             'metric': f'train images/sec (G+D step) at {SIZE}x{SIZE} bs={BATCH_PER_GPU} per GPU', 'value': round(m['value'], 2),
@@ -366,21 +420,22 @@ def main():
             'config': {'workload': CFG['desc'] + ', dropout ' + ('on' if args.dropout else 'off'),
                        'global_batch': BATCH_PER_GPU * world, 'parallelism': f'dp{world}'},
             'last_losses': m['last_losses'],
-            'roofline': m['roofline'],
         }
-        if m['comm'] is not None:
-            out['comm'] = m['comm']
-        if world == 1 and not args.no_cpu_baseline:
-            out['cpu_baseline'] = cpu_baseline()
-        elif world == 1:
-            out['cpu_baseline'] = None
-        out['conv_kernels_note'] = 'per-kernel table from one fully instrumented warm-up step; roofline from the timed region'
-        out['conv_kernels'] = m['conv_kernels']
-        # the other single-GPU configurations of BASELINE.json, measured AFTER the headline's timed region and JSON assembly (the
-        # headline metric / config / dtype above stay cfg2 fp32): cfg4 in bf16 (the "next" row f2) and cfg5 tiled inference (f1)
-        if world == 1 and not use_dist and not args.no_extra and args.config == 'cfg2' and args.dtype == 'f32':
-            del m
-            out['extra_configs'] = extra_configs(dev, cpu=not args.no_cpu_baseline)
+        if args.full:
+            out['roofline'] = m['roofline']
+            if m['comm'] is not None:
+                out['comm'] = m['comm']
+            if world == 1 and not args.no_cpu_baseline:
+                out['cpu_baseline'] = cpu_baseline()
+            elif world == 1:
+                out['cpu_baseline'] = None
+            out['conv_kernels_note'] = 'per-kernel table from one fully instrumented warm-up step; roofline from the timed region'
+            out['conv_kernels'] = m['conv_kernels']
+            # the other single-GPU configurations of BASELINE.json, measured AFTER the headline's timed region and JSON assembly (the
+            # headline metric / config / dtype above stay cfg2 fp32): cfg4 in bf16 (the "next" row f2) and cfg5 tiled inference (f1)
+            if world == 1 and not use_dist and not args.no_extra and args.config == 'cfg2' and args.dtype == 'f32':
+                del m
+                out['extra_configs'] = extra_configs(dev, cpu=not args.no_cpu_baseline)
         sys.stdout.flush()
         os.write(line_fd, (json.dumps(out) + '\n').encode())
     if use_dist:
@@ -389,11 +444,13 @@ def main():
 
 
 def measure_training(cfg, dtype, steps, warmup, dev, rank=0, world=1, use_dist=False, events='dominant', dropout=False,
-                     fp32_activations=False, graph=True):
+                     fp32_activations=False, graph=True, full=True, dump_dir=None):
     """W untimed + K timed G+D steps of workload `cfg` on this rank's device (inputs resident in HBM; barrier + synchronize on
-    both sides; MAX over ranks).  Returns the pieces of the JSON line: value (whole-job images/s), ms_per_step, roofline of the
-    dominant conv kernel (HIP events on the launch stream inside the timed region), the per-kernel table of one fully
-    instrumented warm-up step, comm statistics under data parallelism."""
+    both sides; MAX over ranks).  Returns the pieces of the JSON line: value (whole-job images/s), ms_per_step and, with `full`,
+    the roofline of the dominant conv kernel (HIP events on the launch stream inside the timed region), the per-kernel table of
+    one fully instrumented warm-up step, comm statistics under data parallelism.  Without `full` no step carries events (whether
+    the plan holds split-bf16 kernels comes from the planner: planned_split_bf16).  `dump_dir`: rank 0 writes the last timed
+    step's outputs there (dump_outputs) before anything else runs."""
     import torch
     import torch.distributed as dist
     import patchgan_amd as pg
@@ -426,16 +483,18 @@ def measure_training(cfg, dtype, steps, warmup, dev, rank=0, world=1, use_dist=F
             dist.barrier()
         torch.cuda.synchronize()
 
-    # warm-up; the last warm-up step is profiled launch by launch to find the dominant conv kernel symbol, so that the
+    # warm-up; with `full` the last warm-up step is profiled launch by launch to find the dominant conv kernel symbol, so that the
     # timed region only carries events around THAT kernel's launches (2 event records per launch are not free)
     wprof = E.LaunchProfiler()
     for i in range(warmup):
-        E.PROFILER = wprof if i == warmup - 1 else None
+        E.PROFILER = wprof if (full and i == warmup - 1) else None
         t.batch(x, y, train=True)
     E.PROFILER = None
     torch.cuda.synchronize()
     wsum = wprof.summary()
-    if not wsum:                       # --warmup 0: nothing to pick the dominant kernel from: instrument every launch
+    if not full:                       # the headline needs no per-launch timing
+        events = 'none'
+    elif not wsum:                     # --warmup 0: nothing to pick the dominant kernel from: instrument every launch
         events = 'all'
     dominant = max(wsum.items(), key=lambda kv: kv[1]['ms'])[0] if wsum else None
     prof = E.LaunchProfiler(only=None if events == 'all' else dominant)
@@ -458,10 +517,10 @@ def measure_training(cfg, dtype, steps, warmup, dev, rank=0, world=1, use_dist=F
         # (under data parallelism every rank must run the SAME number of steps -- each step holds collectives -- so nothing below may
         #  depend on a rank's own clock: the tournament has a fixed length, the settling loop a fixed count, and the flags that steer
         #  the rest of this function are agreed on across ranks)
+        # (on one rank too, the number of steps before the timed ones is fixed by the arguments, whichever way the tournament
+        #  decides: the last timed step's outputs, --dump-outputs, are then the same from run to run)
         n_decide = 3 * (2 * t.TRIAL_STEPS + 2) + 4
         for _ in range(n_decide):
-            if t.graph_decided() and not use_dist:
-                break
             t.batch(x, y, train=True)
         graphed, after = t.graph_captured(), t.graph_decided()
         two = 'eager2' in t.decided_modes()
@@ -469,27 +528,12 @@ def measure_training(cfg, dtype, steps, warmup, dev, rank=0, world=1, use_dist=F
             flags = torch.tensor([int(two), int(graphed)], dtype=torch.int32, device=dev)
             dist.all_reduce(flags, op=dist.ReduceOp.MAX)
             two, graphed = bool(flags[0].item()), bool(flags[1].item())
-        after = graphed or two          # (decided 'eager1': nothing to settle, the timed steps carry the launch profiler as before)
-        if two:
-            # the first two-stream steps hold every backward operand until the streams join: the caching allocator grows for some
-            # steps (device allocations synchronise: 12-15 ms per step instead of 8.7) before the pattern settles -- outside the timed
-            # region, as any warm-up: groups of four steps until two consecutive groups take the same time (2 %), at most 48 steps
-            # (data parallel: a fixed 16 steps)
-            prev = None
-            for grp in range(12):
-                torch.cuda.synchronize()
-                tg = time.perf_counter()
-                for _ in range(4):
-                    t.batch(x, y, train=True)
-                torch.cuda.synchronize()
-                tg = time.perf_counter() - tg
-                if use_dist:
-                    if grp == 3:
-                        break
-                    continue
-                if prev is not None and abs(tg - prev) <= 0.02 * prev:
-                    break
-                prev = tg
+        after = graphed or two          # (decided 'eager1': the timed steps carry the launch profiler as before)
+        # the first two-stream steps hold every backward operand until the streams join: the caching allocator grows for some
+        # steps (device allocations synchronise: 12-15 ms per step instead of 8.7) before the pattern settles -- outside the timed
+        # region, as any warm-up: 48 steps (data parallel: 16), whichever way the step is launched (a fixed count, as above)
+        for _ in range(16 if use_dist else 48):
+            t.batch(x, y, train=True)
         E.PROFILER = None if after else (prof if events != 'none' else None)
     pd = parallel.current()
     trace = bool(os.environ.get('PATCHGAN_BENCH_TRACE'))
@@ -518,6 +562,8 @@ def measure_training(cfg, dtype, steps, warmup, dev, rank=0, world=1, use_dist=F
     t.flush()                      # the last step's (deferred, data-parallel) discriminator update belongs to the timed work
     sync()
     elapsed = time.perf_counter() - t0
+    if dump_dir is not None and rank == 0:
+        dump_outputs(dump_dir, t, last)
     sample_note = 'every launch of the kernel in the first steps of the timed region (<= 96 launches), HIP events on the launch stream'
     if after and events != 'none' and wsum:
         # the timed steps were hipGraph replays (or two-stream steps) (no per-launch events: the HIP runtime torch brings along refuses external event-record
@@ -536,7 +582,7 @@ def measure_training(cfg, dtype, steps, warmup, dev, rank=0, world=1, use_dist=F
                        + '): every launch of the kernel, HIP events on the launch stream')
     E.PROFILER = None
     comm = None
-    if pd.on:
+    if pd.on and full:
         # communication statistics from `csteps` EXTRA steps after the timed region (every rank runs them: they hold collectives):
         # HIP events around each collective (comm stream) and around each wait for one (compute stream).  Not inside the timed
         # region: an event record or a stream wait is a barrier packet on MI355X (5-10 us of an otherwise back-to-back kernel
@@ -582,6 +628,11 @@ def measure_training(cfg, dtype, steps, warmup, dev, rank=0, world=1, use_dist=F
         return res
     value = batch * world * steps / elapsed
     summ = prof.summary() if events != 'none' else wsum
+    res.update({'value': value, 'ms_per_step': elapsed / steps * 1e3, 'host_ms_per_step': host_ms / steps,
+                'activation_storage': 'bf16' if (dtype == 'bf16' and G.engine.act_bf) else 'f32',
+                'last_losses': last_vals, 'split_bf16': planned_split_bf16(G, D, batch, size)})
+    if not full:
+        return res
     # dominant kernel = the conv kernel symbol with the most device time (found in the profiled warm-up step)
     sym, d = max(summ.items(), key=lambda kv: kv[1]['ms'])
     if events == 'none':
@@ -606,12 +657,8 @@ def measure_training(cfg, dtype, steps, warmup, dev, rank=0, world=1, use_dist=F
     fp32_equiv = achieved
     if s3_dom:
         achieved, useful, peak = 6.0 * achieved, 6.0 * useful, 2500.0
-    s3_any = any('_s3<' in k for k in per_step_all)
     traffic, traffic_src = pmc_traffic(sym)
     res.update({
-        'value': value, 'ms_per_step': elapsed / steps * 1e3, 'host_ms_per_step': host_ms / steps,
-        'activation_storage': 'bf16' if (dtype == 'bf16' and G.engine.act_bf) else 'f32',
-        'last_losses': last_vals, 'split_bf16': s3_any,
         'roofline': {'bound': 'mfma', 'kernel': sym,
                      'achieved': round(achieved, 2), 'peak': peak, 'unit': 'TFLOP/s',
                      'frac': round(achieved / peak, 4), 'achieved_useful': round(useful, 2), 'frac_useful': round(useful / peak, 4),

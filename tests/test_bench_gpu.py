@@ -13,12 +13,15 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _bench(extra_args, extra_env, timeout=900, extras=False, cpu=False):
+def _bench(extra_args, extra_env, timeout=900, extras=False, cpu=False, full=True):
+    """One bench.py run's JSON line; `full`: with --full (roofline, per-kernel table, comm; `extras` / `cpu`: its extra
+    configurations / CPU-oracle legs too)."""
     env = dict(os.environ, **extra_env)
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_PORT'):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '3', '--warmup', '2']
-                       + ([] if cpu else ['--no-cpu-baseline']) + ([] if extras else ['--no-extra']) + extra_args,
+                       + (['--full'] + ([] if cpu else ['--no-cpu-baseline']) + ([] if extras else ['--no-extra']) if full else [])
+                       + extra_args,
                        env=env, capture_output=True, text=True, timeout=timeout, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
@@ -55,10 +58,46 @@ def test_bench_single_gpu_line():
     from tests import bench_layers as BL
     planned = {s for k, v in BL.committed_plan().items() if k.startswith('cfg2-fp32-') for s in v}
     assert set(out['conv_kernels']) <= planned, set(out['conv_kernels']) - planned
+    # the dtype's split-bf16 note comes from the planner (bench.planned_split_bf16): it names the kernels the step really launched
+    for o in (out, small):
+        assert ('bf16x3 split form' in o['dtype']) == any('_s3<' in k for k in o['conv_kernels']), (o['dtype'], sorted(o['conv_kernels']))
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) prints the headline and nothing that takes measurements of its own, and --dump-outputs writes what the
+    last timed step computed: float32 / float64 .npy files, 64 MB at most, holding the losses the line reports.  The same arguments
+    give the same bits; --steps sets the training work: 2 timed steps behind 3 warm-up ones end on the same bits as 3 behind 2, one
+    step more on other ones, and the timed region of 40 steps takes about 4x that of 10 (the same ms_per_step)."""
+    import numpy as np
+    import bench
+
+    def run(tag, steps, warmup):
+        d = tmp_path / tag
+        out = _bench(['--steps', str(steps), '--warmup', str(warmup), '--dump-outputs', str(d)], {}, full=False)
+        assert out['steps'] == steps and out['warmup'] == warmup
+        return out, {p.name[:-4]: np.load(p) for p in sorted(d.glob('*.npy'))}
+    out, a = run('a', 3, 2)
+    assert out['unit'] == 'images/sec' and out['higher_is_better'] is True and out['dtype'].startswith('f32')
+    assert out['value'] > 100 and abs(out['value'] * out['ms_per_step'] - 16e3) < 16.0        # 16 images per timed step
+    assert not {'roofline', 'conv_kernels', 'comm', 'cpu_baseline', 'extra_configs'} & set(out), sorted(out)
+    assert set(a) == {'loss_' + k for k in out['last_losses']} | {'generator', 'discriminator'}, sorted(a)
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a['generator'].shape == (bench.DUMP_CAP,) and np.isfinite(a['generator']).all() and np.isfinite(a['discriminator']).all()
+    for k, v in out['last_losses'].items():
+        assert abs(float(a['loss_' + k]) - v) <= 1e-5, (k, float(a['loss_' + k]), v)
+    b = run('b', 3, 2)[1]
+    shifted = run('shifted', 2, 3)[1]
+    for k in a:
+        assert np.array_equal(a[k], b[k]) and np.array_equal(a[k], shifted[k]), k
+    more = run('more', 4, 2)[1]
+    assert not np.array_equal(a['generator'], more['generator']) and not np.array_equal(a['discriminator'], more['discriminator'])
+    short = _bench(['--steps', '10'], {}, full=False)
+    long = _bench(['--steps', '40'], {}, full=False)
+    assert long['steps'] == 40 and 1 / 1.4 < long['ms_per_step'] / short['ms_per_step'] < 1.4, (short['ms_per_step'], long['ms_per_step'])
 
 
 def test_bench_extra_configs_ride_on_the_headline_line():
-    """The default N = 1 run also measures BASELINE.json's other single-GPU configurations after the headline's timed region -- cfg4
+    """The N = 1 run with --full also measures BASELINE.json's other single-GPU configurations after the headline's timed region -- cfg4
     in bf16 (images/s, dominant-kernel fraction of the bf16 MFMA peak) and cfg5 tiled inference (tiles/s, peak VRAM) -- under
     `extra_configs` of the same single line; the headline metric / config / dtype stay cfg2 fp32.  Each carries its CPU-oracle leg
     (bounded), cfg5 its fraction of the fp32 MFMA roofline, and `e2e_cfg2` the loader-fed rate of Trainer.train for both item formats."""

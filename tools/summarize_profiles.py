@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Turn the rocprofv3 output of tools/collect_profiles.sh <tag> (merged back under gpurun_out/<tag>/) into the committed
-evidence: profiles/<tag>_kernel_stats.csv, profiles/<tag>_pmc_traffic.json, profiles/<tag>_bench.json."""
+"""Turn the rocprofv3 output of `OUT=<dir> tools/collect_profiles.sh <tag>` (under <dir>/<tag>/, read back with the same OUT) into
+the committed evidence: profiles/<tag>_kernel_stats.csv, profiles/<tag>_pmc_traffic.json, profiles/<tag>_bench.json."""
 import collections
 import csv
 import glob
@@ -12,7 +12,8 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag = sys.argv[1]
-src = os.path.join(ROOT, 'gpurun_out', tag)
+OUT = os.environ.get('OUT') or sys.exit('OUT: the directory tools/collect_profiles.sh wrote to, relative to the repository root')
+src = os.path.join(ROOT, OUT, tag)
 
 
 def short(name):
@@ -95,7 +96,7 @@ note = ('rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE / --pmc SQ_VALU_MFMA_BUSY
         'the bytes of 16-B-per-lane loads; WRITE_SIZE is exact. Infinity-Cache hits are counted (fabric-side requests), so '
         'this is an upper bound on DRAM traffic. mfma_pipe_utilisation = MFMA busy cycles per SIMD / kernel cycles.')
 json.dump({'_note': note, 'kernels': kernels}, open(os.path.join(ROOT, 'profiles', f'{tag}_pmc_traffic.json'), 'w'), indent=1)
-b = os.path.join(ROOT, 'gpurun_out', f'{tag}.bench.json')
+b = os.path.join(ROOT, OUT, f'{tag}.bench.json')
 if os.path.exists(b):
     shutil.copy(b, os.path.join(ROOT, 'profiles', f'{tag}_bench.json'))
 top = sorted(kernels.items(), key=lambda kv: -kv[1]['hbm_bytes_per_launch'] * kv[1]['launches'])[:8]
