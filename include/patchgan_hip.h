@@ -310,6 +310,49 @@ int pg_softmax_bwd(const float* g1, int ld_g1, const float* g2, int ld_g2, const
 /* Writes the dropout keep-mask (1.0 / 0.0) the kernels above use, for tests. */
 int pg_dropout_mask(float* mask, long nelem, float drop_p, uint64_t seed, void* stream);
 
+/* ---- BatchNorm2d (eps, momentum, affine, tracked running statistics; unet.py:20,55 and disc.py:32,42 with
+ * norm_layer=nn.BatchNorm2d) + activation + Dropout(p), fp32 tensors.  y[N, HW, C] splits into `nseg` (1 or 2) SEGMENTS of
+ * N / nseg consecutive samples, each normalised with its own batch statistics over its (N / nseg) * HW pixels: nseg = 2 is the
+ * discriminator step's one pass over din[2N], which the reference runs as two calls (trainer.py:97,99).
+ *   coef[(s*C + c)*4 + {0..3}] = (mean, rstd, scale = weight*rstd, shift = bias - mean*scale);  out = drop(act(y*scale + shift)).
+ *   bstat[(s*C + c)*2 + {0,1}] = (batch mean, unbiased batch variance), fp64 (may be NULL): the input of the running update.
+ * Statistics: fp64 partial sums per (sample, pixel chunk, channel), merged in a fixed order (bit-reproducible).  Every
+ * (N / nseg) * HW must be > 1 (torch raises "Expected more than 1 value per channel when training" there).  Dropout as
+ * pg_instnorm_act_fwd.  ws: pg_batchnorm_workspace_bytes. */
+size_t pg_batchnorm_workspace_bytes(int N, int HW, int C, int nseg);
+int pg_batchnorm_act_fwd(const float* y, int ld_y, float* out, int ld_out, const float* weight, const float* bias, float* coef,
+                         double* bstat, int N, int HW, int C, int nseg, int act, float eps, float drop_p, uint64_t seed, void* ws,
+                         size_t ws_bytes, void* stream);
+/* The statistics half of pg_batchnorm_act_fwd (coef, bstat), from the producer's partial sums part[N][chunks][C][2] where the
+ * conv epilogue emitted them (pg_conv_extras.part; y unused), else (part == NULL) from a pass over y. */
+int pg_batchnorm_stats(const float* y, int ld_y, const double* part, int chunks, const float* weight, const float* bias, float* coef,
+                       double* bstat, int N, int HW, int C, int nseg, float eps, void* ws, size_t ws_bytes, void* stream);
+/* The normalise half: out = drop(act(y*scale + shift)) with the coefficients of the sample's segment. */
+int pg_batchnorm_act_apply(const float* y, int ld_y, float* out, int ld_out, const float* coef, int N, int HW, int C, int nseg,
+                           int act, float drop_p, uint64_t seed, void* stream);
+/* Evaluation mode (module.eval()): coef[C][4] from the running statistics, on the device; apply with nseg = 1. */
+int pg_batchnorm_eval_coef(const float* running_mean, const float* running_var, const float* weight, const float* bias, int C,
+                           float eps, float* coef, void* stream);
+/* Backward (trainer.py:89,106): dz = (g1 + g2) -> dropout mask -> act'(y*scale + shift); per segment
+ *   train != 0:  dy = scale * (dz - sum(dz)/M - xhat * sum(dz*xhat)/M),   xhat = (y - mean) * rstd
+ *   train == 0:  dy = scale * dz  (the running statistics are constants: coef from pg_batchnorm_eval_coef)
+ * dweight[c] = sum over segments of sum(dz*xhat), dbias[c] = of sum(dz) -- both written (not accumulated), or both NULL (skipped). */
+int pg_batchnorm_act_bwd(const float* g1, int ld_g1, const float* g2, int ld_g2, const float* y, int ld_y, const float* coef,
+                         float* dy, int ld_dy, float* dweight, float* dbias, int N, int HW, int C, int nseg, int train, int act,
+                         float drop_p, uint64_t seed, void* ws, size_t ws_bytes, void* stream);
+/* Running statistics of up to PG_BN_MAX_LAYERS BatchNorm layers in ONE launch: per layer, `nslots` batch statistics
+ * bstat[slot][C][2] folded in slot order (running = (1 - momentum) * running + momentum * batch, in double, stored as float after
+ * each), num_batches_tracked += nslots on the device (a replayed hipGraph keeps counting). */
+#define PG_BN_MAX_LAYERS 16
+typedef struct pg_bn_update_item {
+    const double* bstat;
+    float* running_mean;
+    float* running_var;
+    int64_t* num_batches_tracked;
+    int C;
+} pg_bn_update_item;
+int pg_batchnorm_update_running(int n, const pg_bn_update_item* items, int nslots, float momentum, void* stream);
+
 /* ---- losses (losses.py:18-39, trainer.py:71-85,101-103) ------------------------------------------
  * Stage 1 (per rank): pg_loss_reduce accumulates, for each (sample n, channel c), the five sums
  *   S[n][c][0..4] = { sum y*p, sum y, sum p, sum bce_elem(p, y), sum |p - y| }       (double)

@@ -55,6 +55,15 @@ class ConvExtras(ctypes.Structure):
 _X = ctypes.POINTER(ConvExtras)
 
 
+class BnUpdateItem(ctypes.Structure):
+    """struct pg_bn_update_item: one BatchNorm layer of pg_batchnorm_update_running"""
+    _fields_ = [('bstat', ctypes.c_void_p), ('running_mean', ctypes.c_void_p), ('running_var', ctypes.c_void_p),
+                ('num_batches_tracked', ctypes.c_void_p), ('C', ctypes.c_int)]
+
+
+BN_MAX_LAYERS = 16      # PG_BN_MAX_LAYERS
+
+
 class ConvPrepItem(ctypes.Structure):
     """struct pg_conv_prep_item: one layer / direction of pg_conv_prep_batch"""
     _fields_ = [('g', ConvGeom), ('op', ctypes.c_int), ('algo', ctypes.c_int), ('ws_bytes', ctypes.c_size_t), ('P', ctypes.c_void_p),
@@ -98,6 +107,13 @@ SIGNATURES = {
     'pg_softmax_fwd': (_i, [_p, _i, _p, _i, _l, _i, _p]),
     'pg_softmax_bwd': (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _l, _i, _p]),
     'pg_dropout_mask': (_i, [_p, _l, _f, _u64, _p]),
+    'pg_batchnorm_workspace_bytes': (_sz, [_i, _i, _i, _i]),
+    'pg_batchnorm_act_fwd': (_i, [_p, _i, _p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _u64, _p, _sz, _p]),
+    'pg_batchnorm_stats': (_i, [_p, _i, _p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _f, _p, _sz, _p]),
+    'pg_batchnorm_act_apply': (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _f, _u64, _p]),
+    'pg_batchnorm_eval_coef': (_i, [_p, _p, _p, _p, _i, _f, _p, _p]),
+    'pg_batchnorm_act_bwd': (_i, [_p, _i, _p, _i, _p, _i, _p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _f, _u64, _p, _sz, _p]),
+    'pg_batchnorm_update_running': (_i, [_i, ctypes.POINTER(BnUpdateItem), _i, _f, _p]),
     'pg_loss_reduce_doubles': (_l, [_i, _i, _i]),
     'pg_loss_fused_max_nc': (_i, []),
     'pg_loss_reduce': (_i, [_p, _i, _p, _i, _f, _i, _i, _i, _p, _p]),

@@ -37,6 +37,14 @@ class FlatParamModule(nn.Module):
         self._pre_access()
         return super().named_parameters(*args, **kwargs)
 
+    def buffers(self, *args, **kwargs):
+        self._pre_access()
+        return super().buffers(*args, **kwargs)
+
+    def named_buffers(self, *args, **kwargs):
+        self._pre_access()
+        return super().named_buffers(*args, **kwargs)
+
     def get_parameter(self, target):
         self._pre_access()
         return super().get_parameter(target)
@@ -49,9 +57,15 @@ class FlatParamModule(nn.Module):
         self._layers = layers
         flat = torch.zeros(nparams, dtype=torch.float32)
         E.default_init_(flat, layers)
-        self._bind(flat)
+        # BatchNorm layers: running statistics in a BUFFER block (fp32) and their counters (int64) -- module buffers, views of the
+        # two tensors, outside the parameter buffer Adam updates
+        eng = self.engine
+        bufs = torch.zeros(max(eng.nbuf, 1), dtype=torch.float32)
+        counters = torch.zeros(max(eng.nbn, 1), dtype=torch.int64)
+        E.init_buffers_(bufs, counters, layers)
+        self._bind(flat, bufs, counters)
 
-    def _bind(self, flat):
+    def _bind(self, flat, bufs=None, counters=None):
         object.__setattr__(self, 'flat', flat)
         object.__setattr__(self, 'grad_flat', None)
         views = E.torch_views(flat, self._layers)
@@ -61,6 +75,29 @@ class FlatParamModule(nn.Module):
                 mod._parameters[leaf].data = v
             else:
                 mod.register_parameter(leaf, nn.Parameter(v))
+        if bufs is not None:
+            object.__setattr__(self, 'bn_bufs', bufs)
+            object.__setattr__(self, 'bn_counters', counters)
+            # the batch statistics of the passes of one step (E.BNRun), until bn_update() folds them into the running statistics
+            object.__setattr__(self, 'bn_scratch', torch.zeros(max(self.engine.nscratch, 1), dtype=torch.float64, device=bufs.device))
+            for key, v in E.buffer_views(bufs, counters, self._layers).items():
+                mod, leaf = self._owner(key)
+                if leaf in mod._buffers:
+                    mod._buffers[leaf] = v
+                else:
+                    mod.register_buffer(leaf, v)
+
+    def bn_run(self, slot=0, nseg=1):
+        """The BNRun of one pass of this network in its current mode (self.training), or None without BatchNorm layers."""
+        if not self.engine.has_bn:
+            return None
+        return E.BNRun(self.training, self.bn_bufs, self.bn_scratch, slot, nseg)
+
+    def bn_update(self, nslots):
+        """Enqueue the running-statistics update of every BatchNorm layer from the batch statistics of slots [0, nslots) (no-op
+        without BatchNorm layers and in evaluation mode, whose passes use the running statistics and collect none)."""
+        if self.engine.has_bn and self.training:
+            E.bn_update_running(self._layers, self.bn_bufs, self.bn_counters, self.bn_scratch, nslots)
 
     def _owner(self, key):
         parts = key.split('.')
@@ -77,7 +114,10 @@ class FlatParamModule(nn.Module):
         new_flat = fn(self.flat.detach())
         if new_flat.dtype != torch.float32:
             raise TypeError("patchgan_amd networks are fp32 only")
-        self._bind(new_flat.contiguous())
+        # the buffer block moves with the parameters (its dtypes stay: .half() / .double() are refused above)
+        new_bufs = self.bn_bufs.to(new_flat.device).contiguous()
+        new_counters = self.bn_counters.to(new_flat.device).contiguous()
+        self._bind(new_flat.contiguous(), new_bufs, new_counters)
         for p in self.parameters():
             p.grad = None
         return self
@@ -88,6 +128,8 @@ class FlatParamModule(nn.Module):
         HBM.  Master weights, weight gradients, InstanceNorm statistics, losses and Adam stay fp32 either way.  Returns self."""
         from . import _lib as L
         algo = {'fp32': L.ALGO_AUTO, 'bf16': L.ALGO_BF16}[precision]
+        if precision == 'bf16' and self.engine.has_bn:
+            raise NotImplementedError("patchgan_amd: bf16 precision is not implemented for nn.BatchNorm2d networks (fp32 only)")
         self.engine.algo = algo | (self.engine.algo & ~L.ALGO_MASK)
         self.engine._ops = {}
         self.engine._sok = {}

@@ -14,7 +14,8 @@ class _DiscFn(torch.autograd.Function):
         N, C, H, W = x.shape
         dev = module.flat.device
         din = E.View.alloc(N, H, W, C, dev).from_nchw(x.to(device=dev, dtype=torch.float32))
-        c = eng.forward(module.flat, din)
+        c = eng.forward(module.flat, din, bn=module.bn_run())
+        module.bn_update(1)          # training mode: this call's batch statistics into the running statistics, as torch does
         ctx.module, ctx.c = module, c
         ctx.need_dx = x.requires_grad
         return c.out.to_nchw()
@@ -33,18 +34,14 @@ class _DiscFn(torch.autograd.Function):
 
 
 class Discriminator(FlatParamModule, Transferable):
-    """Discriminator(input_nc, ndf=64, n_layers=3, norm=False, norm_layer=InstanceNorm2d) -- reference disc.py:8."""
+    """Discriminator(input_nc, ndf=64, n_layers=3, norm=False, norm_layer=InstanceNorm2d) -- reference disc.py:8.  norm_layer:
+    nn.InstanceNorm2d or nn.BatchNorm2d (its defaults)."""
 
     def __init__(self, input_nc, ndf=64, n_layers=3, norm=False, norm_layer=nn.InstanceNorm2d):
         super().__init__()
-        if norm and norm_layer is not nn.InstanceNorm2d:
-            raise NotImplementedError("patchgan_amd.Discriminator implements nn.InstanceNorm2d only")
-        self.engine = E.DiscriminatorEngine(input_nc, ndf, n_layers, norm)
-        self._param_keys = []
-        for l in self.engine.layers:
-            self._param_keys.append(l.key)
-            if l.bias_key is not None:
-                self._param_keys.append(l.bias_key)
+        kind = E.norm_kind_of(norm_layer, 'patchgan_amd.Discriminator') if norm else 'instance'
+        self.engine = E.DiscriminatorEngine(input_nc, ndf, n_layers, norm, norm_kind=kind)
+        self._param_keys = E.param_keys(self.engine.layers)
         self._init_flat(self.engine.layers, self.engine.nparams)
 
     def forward(self, input):

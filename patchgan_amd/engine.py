@@ -23,6 +23,7 @@ import threading
 import numpy as np
 
 import torch
+from torch import nn
 
 from . import _lib as L
 
@@ -747,6 +748,96 @@ def conv_instnorm_act(op, opcode, src, flat, p_off, y, out, stats, act, drop_p=0
         instnorm_act_fwd(y, out, stats, act, drop_p, seed)
 
 
+class BNRun:
+    """How the BatchNorm layers of one pass normalise -- chosen by module.training, not by Trainer.batch(train=...) (the reference
+    calls .eval() only in its validation loop).  train: batch statistics per SEGMENT (nseg runs of N / nseg consecutive samples: the
+    discriminator's pass over din[2N] stands for two calls of the reference, trainer.py:97,99), segment s's (mean, unbiased var) into
+    the scratch at slot + s, folded into the running statistics later by bn_update_running in slot order.  eval: the running
+    statistics of `bufs`, nothing is written."""
+    __slots__ = ('train', 'bufs', 'scratch', 'slot', 'nseg')
+
+    def __init__(self, train, bufs, scratch, slot=0, nseg=1):
+        self.train, self.bufs, self.scratch, self.slot, self.nseg = bool(train), bufs, scratch, slot, nseg if train else 1
+        assert slot + self.nseg <= BN_SLOTS
+
+
+def _bn_check(y, nseg):
+    if (y.N // nseg) * y.HW <= 1:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size "
+                         f"torch.Size([{y.N // nseg}, {y.C}, {y.H}, {y.W}])")
+
+
+def batchnorm_act_fwd(l, bn, flat, y, out, act, drop_p=0.0, seed=0, part=None, chunks=0):
+    """y -> BatchNorm2d of layer l -> activation -> dropout into out.  Returns the per-(segment, channel) coefficients it normalised
+    with: a tensor of the pass's own, which the backward reads (a later running-statistics update cannot change it)."""
+    lib = L.load()
+    coef = torch.empty(bn.nseg * y.C * 4, dtype=torch.float32, device=y.t.device)
+    w, b = L.ptr(flat, l.g_off), L.ptr(flat, l.be_off)
+    st = _stream()
+    if not bn.train:
+        L.check(lib.pg_batchnorm_eval_coef(L.ptr(bn.bufs, l.rm_off), L.ptr(bn.bufs, l.rv_off), w, b, y.C, BN_EPS, coef.data_ptr(), st),
+                'pg_batchnorm_eval_coef')
+        L.check(lib.pg_batchnorm_act_apply(y.ptr(), y.ld, out.ptr(), out.ld, coef.data_ptr(), y.N, y.HW, y.C, 1, act, drop_p,
+                                           seed & _MASK64, st), 'pg_batchnorm_act_apply')
+        return coef
+    _bn_check(y, bn.nseg)
+    bstat = L.ptr(bn.scratch, l.bs_off + bn.slot * y.C * 2)
+    if part is not None:
+        L.check(lib.pg_batchnorm_stats(None, y.ld, part.data_ptr(), chunks, w, b, coef.data_ptr(), bstat, y.N, y.HW, y.C, bn.nseg,
+                                       BN_EPS, None, 0, st), 'pg_batchnorm_stats')
+        L.check(lib.pg_batchnorm_act_apply(y.ptr(), y.ld, out.ptr(), out.ld, coef.data_ptr(), y.N, y.HW, y.C, bn.nseg, act, drop_p,
+                                           seed & _MASK64, st), 'pg_batchnorm_act_apply')
+        return coef
+    ws = _workspace(int(lib.pg_batchnorm_workspace_bytes(y.N, y.HW, y.C, bn.nseg)), y.t.device)
+    L.check(lib.pg_batchnorm_act_fwd(y.ptr(), y.ld, out.ptr(), out.ld, w, b, coef.data_ptr(), bstat, y.N, y.HW, y.C, bn.nseg, act,
+                                     BN_EPS, drop_p, seed & _MASK64, ws.data_ptr(), ws.numel(), st), 'pg_batchnorm_act_fwd')
+    return coef
+
+
+def conv_batchnorm_act(op, opcode, src, flat, l, y, out, bn, act, drop_p=0.0, seed=0, v_keep=None, u_cache=None, u_valid=False):
+    """Conv2d / ConvTranspose2d (no bias) -> BatchNorm2d -> activation -> dropout: the InstanceNorm block's schedule
+    (conv_instnorm_act) -- in training mode the batch statistics come from the conv epilogue's partial sums where it emits them."""
+    conv = op.big2small if opcode == 0 else op.small2big
+    kw = {'v_keep': v_keep} if v_keep is not None else {}
+    if u_cache is not None:
+        kw.update(u_cache=u_cache, u_valid=u_valid)
+    if bn.train:
+        _bn_check(y, bn.nseg)
+    chunks = op.stats_chunks(opcode, src, y) if (FUSE_IN_STATS and bn.train) else 0
+    if chunks:
+        part = torch.empty(y.N * chunks * y.C * 2, dtype=torch.float64, device=y.t.device)
+        conv(src, flat, l.p_off, None, 0, y, part=part, **kw)
+        return batchnorm_act_fwd(l, bn, flat, y, out, act, drop_p, seed, part=part, chunks=chunks)
+    conv(src, flat, l.p_off, None, 0, y, **kw)
+    return batchnorm_act_fwd(l, bn, flat, y, out, act, drop_p, seed)
+
+
+def batchnorm_act_bwd(l, train, nseg, gflat, g1, g2, y, coef, dy, act, drop_p=0.0, seed=0):
+    """Backward of batchnorm_act_fwd (train / nseg: those of its pass).  gflat None: no weight / bias gradients (the generator step's
+    pass through D); else they are WRITTEN into gflat."""
+    lib = L.load()
+    nseg = nseg if train else 1
+    ws = _workspace(int(lib.pg_batchnorm_workspace_bytes(y.N, y.HW, y.C, nseg)), y.t.device)
+    dw, db = (L.ptr(gflat, l.g_off), L.ptr(gflat, l.be_off)) if gflat is not None else (None, None)
+    L.check(lib.pg_batchnorm_act_bwd(g1.ptr(), g1.ld, g2.ptr() if g2 is not None else None, g2.ld if g2 is not None else 0,
+                                     y.ptr(), y.ld, coef.data_ptr(), dy.ptr(), dy.ld, dw, db, y.N, y.HW, y.C, nseg, 1 if train else 0,
+                                     act, drop_p, seed & _MASK64, ws.data_ptr(), ws.numel(), _stream()), 'pg_batchnorm_act_bwd')
+
+
+def bn_update_running(layers, bufs, counters, scratch, nslots):
+    """Fold the batch statistics in slots [0, nslots) of every BatchNorm layer into its running statistics, in slot order, and add
+    nslots to its num_batches_tracked: ONE launch per network."""
+    bl = [l for l in layers if l.bn]
+    if not bl:
+        return
+    items = (L.BnUpdateItem * len(bl))()
+    for it, l in zip(items, bl):
+        it.bstat, it.C = L.ptr(scratch, l.bs_off), l.cout
+        it.running_mean, it.running_var = L.ptr(bufs, l.rm_off), L.ptr(bufs, l.rv_off)
+        it.num_batches_tracked = L.ptr(counters, l.bn_idx)
+    L.check(L.load().pg_batchnorm_update_running(len(bl), items, nslots, BN_MOMENTUM, _stream()), 'pg_batchnorm_update_running')
+
+
 def _exp_env(name, default='1'):
     """A/B switches for same-device timing: honoured only when PATCHGAN_EXPERIMENT is set (like the C side's pg_exp_env)."""
     return os.environ.get(name, default) if 'PATCHGAN_EXPERIMENT' in os.environ else default
@@ -868,13 +959,23 @@ def _mix_seed(base, *vals):
 
 
 class LayerSpec:
-    """One conv layer of a network: state_dict key, torch weight shape [a, b, 4, 4], offsets into the flat buffer."""
-    __slots__ = ('key', 'a', 'b', 'stride', 'transposed', 'p_off', 'bias_key', 'b_off', 'act', 'norm', 'dropout')
+    """One conv layer of a network: state_dict key, torch weight shape [a, b, 4, 4], offsets into the flat buffer.
+    norm: the layer is followed by a norm; norm_kind 'instance' (no parameters) or 'batch' (BatchNorm2d: state_dict prefix
+    norm_key, weight / bias at g_off / be_off of the PARAMETER buffer, running statistics at rm_off / rv_off of the network's
+    BUFFER block, counter bn_idx of its counter tensor, batch statistics at bs_off of its scratch)."""
+    __slots__ = ('key', 'a', 'b', 'stride', 'transposed', 'p_off', 'bias_key', 'b_off', 'act', 'norm', 'dropout', 'norm_kind',
+                 'norm_key', 'g_off', 'be_off', 'rm_off', 'rv_off', 'bn_idx', 'bs_off')
 
-    def __init__(self, key, a, b, stride, transposed, act, norm, dropout=False, bias_key=None):
+    def __init__(self, key, a, b, stride, transposed, act, norm, dropout=False, bias_key=None, norm_kind='instance', norm_key=None):
         self.key, self.a, self.b, self.stride, self.transposed = key, a, b, stride, transposed
         self.act, self.norm, self.dropout, self.bias_key = act, norm, dropout, bias_key
-        self.p_off = self.b_off = -1
+        self.norm_kind = norm_kind if norm else None
+        self.norm_key = norm_key
+        self.p_off = self.b_off = self.g_off = self.be_off = self.rm_off = self.rv_off = self.bn_idx = self.bs_off = -1
+
+    @property
+    def bn(self):
+        return self.norm_kind == 'batch'
 
     @property
     def cout(self):
@@ -894,7 +995,75 @@ def assign_offsets(layers):
         if l.bias_key is not None:
             l.b_off = off
             off += (l.cout + 3) // 4 * 4
+        if l.bn:              # BatchNorm2d weight / bias: parameters like any other (Adam, all-reduce, capture see one buffer)
+            l.g_off = off
+            off += (l.cout + 3) // 4 * 4
+            l.be_off = off
+            off += (l.cout + 3) // 4 * 4
     return off
+
+
+def norm_kind_of(norm_layer, who):
+    """'instance' | 'batch' for a constructor's norm_layer argument; anything else raises NotImplementedError.  BatchNorm2d is taken
+    with its defaults only (eps 1e-5, momentum 0.1, affine, tracked running statistics)."""
+    if norm_layer is nn.InstanceNorm2d:
+        return 'instance'
+    if norm_layer is nn.BatchNorm2d:
+        return 'batch'
+    raise NotImplementedError(f"{who} implements norm_layer=nn.InstanceNorm2d or nn.BatchNorm2d (with their defaults) only, "
+                              f"got {norm_layer!r}")
+
+
+def param_keys(layers):
+    """state_dict keys of a network's parameters, in the reference's order."""
+    keys = []
+    for l in layers:
+        keys.append(l.key)
+        if l.bias_key is not None:
+            keys.append(l.bias_key)
+        if l.bn:
+            keys += [l.norm_key + '.weight', l.norm_key + '.bias']
+    return keys
+
+
+def assign_buffers(layers):
+    """Lay out the BatchNorm running statistics (the network's BUFFER block, which Adam never sees), the counters and the batch
+    statistics scratch (PG_BN_SLOTS slots of fp64 (mean, unbiased var) per channel).  Returns (floats, counters, scratch doubles)."""
+    off = idx = soff = 0
+    for l in layers:
+        if not l.bn:
+            continue
+        C4 = (l.cout + 3) // 4 * 4
+        l.rm_off, l.rv_off, l.bn_idx, l.bs_off = off, off + C4, idx, soff
+        off += 2 * C4
+        idx += 1
+        soff += BN_SLOTS * l.cout * 2
+    return off, idx, soff
+
+
+BN_SLOTS = 3              # running-stat updates per step a network can collect: the discriminator's three passes (trainer.py:66,97,99)
+BN_EPS, BN_MOMENTUM = 1e-5, 0.1
+
+
+def buffer_views(bufs, counters, layers):
+    """{state_dict key: view} of the BatchNorm buffers (running_mean, running_var: [C] fp32; num_batches_tracked: 0-d int64)."""
+    out = {}
+    for l in layers:
+        if l.bn:
+            out[l.norm_key + '.running_mean'] = bufs.as_strided((l.cout,), (1,), l.rm_off)
+            out[l.norm_key + '.running_var'] = bufs.as_strided((l.cout,), (1,), l.rv_off)
+            out[l.norm_key + '.num_batches_tracked'] = counters.as_strided((), (), l.bn_idx)
+    return out
+
+
+def init_buffers_(bufs, counters, layers):
+    """BatchNorm2d's initial state: running_mean 0, running_var 1, num_batches_tracked 0."""
+    with torch.no_grad():
+        bufs.zero_()
+        counters.zero_()
+        for l in layers:
+            if l.bn:
+                bufs[l.rv_off:l.rv_off + l.cout].fill_(1.0)
 
 
 def torch_views(flat, layers):
@@ -905,6 +1074,9 @@ def torch_views(flat, layers):
         out[l.key] = flat.as_strided((l.a, l.b, 4, 4), (l.b, 1, 4 * ab, ab), l.p_off)
         if l.bias_key is not None:
             out[l.bias_key] = flat.as_strided((l.cout,), (1,), l.b_off)
+        if l.bn:
+            out[l.norm_key + '.weight'] = flat.as_strided((l.cout,), (1,), l.g_off)
+            out[l.norm_key + '.bias'] = flat.as_strided((l.cout,), (1,), l.be_off)
     return out
 
 
@@ -921,6 +1093,9 @@ def default_init_(flat, layers, generator=None):
             if l.bias_key is not None:
                 bb = torch.empty(l.cout).uniform_(-bound, bound, generator=generator)
                 views[l.bias_key].copy_(bb)
+            if l.bn:          # BatchNorm2d.reset_parameters: weight 1, bias 0 (draws nothing from the generator)
+                views[l.norm_key + '.weight'].fill_(1.0)
+                views[l.norm_key + '.bias'].zero_()
 
 
 # ------------------------------------------------------------------------------------------------
@@ -928,8 +1103,8 @@ def default_init_(flat, layers, generator=None):
 # ------------------------------------------------------------------------------------------------
 
 
-def unet_layers(input_nc, output_nc, nf, activation, final_act, use_dropout):
-    """Layer plan of reference UNet.__init__ (unet.py:84-107)."""
+def unet_layers(input_nc, output_nc, nf, activation, final_act, use_dropout, norm_kind='instance'):
+    """Layer plan of reference UNet.__init__ (unet.py:84-107).  norm_kind 'batch': nn.BatchNorm2d blocks (DownNorm{i} / UpNorm{i})."""
     if activation not in ('tanh', 'relu', 'leakyrelu'):
         raise ValueError(f"activation must be one of tanh|relu|leakyrelu, got {activation!r}")
     if final_act not in ('tanh', 'relu', 'leakyrelu', 'sigmoid', 'softmax'):
@@ -938,12 +1113,13 @@ def unet_layers(input_nc, output_nc, nf, activation, final_act, use_dropout):
     enc, dec = [], []
     prev = input_nc
     for i, f in enumerate(filts):
-        enc.append(LayerSpec(f'encoder.{i}.model.DownConv{i}.weight', f, prev, 2, False, activation, True, use_dropout))
+        enc.append(LayerSpec(f'encoder.{i}.model.DownConv{i}.weight', f, prev, 2, False, activation, True, use_dropout,
+                             norm_kind=norm_kind, norm_key=f'encoder.{i}.model.DownNorm{i}'))
         prev = f
     for i, f in enumerate(filts[:-1][::-1]):
         cin = prev if i == 0 else prev * 2
         dec.append(LayerSpec(f'decoder.{i}.model.UpConv{i}.weight', cin, f, 2, True, activation, i != 0,
-                             use_dropout and i != 0))
+                             use_dropout and i != 0, norm_kind=norm_kind, norm_key=f'decoder.{i}.model.UpNorm{i}'))
         prev = f
     dec.append(LayerSpec('decoder.6.model.UpConv6.weight', nf * 2, output_nc, 2, True, final_act, False, False))
     return enc, dec
@@ -999,12 +1175,14 @@ class _WeightPrep:
 class GeneratorEngine(_WeightPrep):
     _LD_MULT = 2          # interior tensors are channel slices of the skip-connection buffers cat_i (twice their channels)
 
-    def __init__(self, input_nc, output_nc, nf, activation, final_act, use_dropout, algo=None):
+    def __init__(self, input_nc, output_nc, nf, activation, final_act, use_dropout, algo=None, norm_kind='instance'):
         self.input_nc, self.output_nc, self.nf = input_nc, output_nc, nf
         self.activation, self.final_act, self.use_dropout = activation, final_act, use_dropout
-        self.enc, self.dec = unet_layers(input_nc, output_nc, nf, activation, final_act, use_dropout)
+        self.enc, self.dec = unet_layers(input_nc, output_nc, nf, activation, final_act, use_dropout, norm_kind)
         self.layers = self.enc + self.dec
         self.nparams = assign_offsets(self.layers)
+        self.has_bn = norm_kind == 'batch'
+        self.nbuf, self.nbn, self.nscratch = assign_buffers(self.layers)
         self.algo = DEFAULT_ALGO if algo is None else algo
         self.act_bf = False          # bf16 activation storage (set_precision('bf16'); needs nf % 4 == 0 and nf >= 32)
         self._ops = {}
@@ -1030,7 +1208,8 @@ class GeneratorEngine(_WeightPrep):
                 op = ConvOp(N, h, w, l.a, l.b, 2, self.algo)
                 enc_ops.append(op)
                 h, w = op.Hs, op.Ws
-                if h * w <= 1:     # torch raises from this block's InstanceNorm before the next conv is reached
+                if h * w <= 1 and not self.has_bn:     # torch raises from this block's InstanceNorm before the next conv is reached
+                    # (BatchNorm needs N*H*W > 1 in training mode only: batchnorm_act_fwd checks it per pass)
                     raise ValueError(f"Expected more than 1 spatial element when training, got input size "
                                      f"torch.Size([{N}, {l.a}, {h}, {w}])")
             sizes = [(op.Hs, op.Ws) for op in enc_ops]   # enc i output extent
@@ -1049,20 +1228,23 @@ class GeneratorEngine(_WeightPrep):
             self._ops[key] = (enc_ops, dec_ops)
         return self._ops[key]
 
-    def forward(self, flat, xin, gen_out, train, seed=0, sample0=0, keep_v=False, ucache=None):
+    def forward(self, flat, xin, gen_out, train, seed=0, sample0=0, keep_v=False, ucache=None, bn=None):
         """xin: View [N,H,W,input_nc]; gen_out: View [N,H,W,output_nc] to receive final_act(dec6).
         train selects dropout (InstanceNorm always uses instance statistics, unet.py:77).  sample0 = index of this
         batch's first sample in the global batch (data parallelism: the dropout masks are those of the global batch).
         keep_v: a backward pass follows -- encoder layers on the polyphase Winograd path keep their transformed input for the
         weight gradient (pg_conv_extras.v_keep / v_pre) instead of transforming it again.
         ucache: a dict the caller keeps for as long as `flat` is unchanged (Trainer.batch: forward + backward of one step): on bf16
-        tensors a layer's packed bf16 weights are built once and serve both its forward and its data gradient."""
+        tensors a layer's packed bf16 weights are built once and serve both its forward and its data gradient.
+        bn: a BNRun (BatchNorm networks only)."""
+        assert bn is not None or not self.has_bn, 'a BatchNorm generator pass needs its BNRun'
         N, H, W = xin.N, xin.H, xin.W
         dev = flat.device
         enc_ops, dec_ops = self.ops(N, H, W)
         F = [l.a for l in self.enc]
         c = GenContext()
         c.N, c.H, c.W, c.xin, c.gen_out, c.seed, c.train, c.sample0 = N, H, W, xin, gen_out, seed, train, sample0
+        c.bn_train, c.bn_nseg = (bn.train, bn.nseg) if bn is not None else (False, 1)
         # cat_i (i = 1..6): input of decoder i = [dec_{i-1} out | enc_{6-i} out]
         # bf16 activation storage: every interior activation (conv outputs, normalised outputs, their gradients) is a bf16 tensor;
         # the image-facing tensors (x, enc0's conv output, the generator output and its gradient) stay fp32 and the InstanceNorm /
@@ -1090,13 +1272,18 @@ class GeneratorEngine(_WeightPrep):
                 out = cat.channels(cat.C - l.a, l.a)
             else:
                 out = c.hidden
-            stats = torch.empty(N * l.a * 2, dtype=torch.float32, device=dev)
+            if not l.bn:
+                stats = torch.empty(N * l.a * 2, dtype=torch.float32, device=dev)
             drop = 0.2 if (train and l.dropout) else 0.0
             vb = op.v_bytes() if (keep_v and KEEP_V and ConvOp._aligned(src, y) and ConvOp.fits(src, y)) else 0
             vk = torch.empty(vb, dtype=torch.uint8, device=dev) if vb else None
             u, uv = _ucache(ucache, ('e', i), 0, op, dev, src, y, l.p_off)
-            conv_instnorm_act(op, 0, src, flat, l.p_off, y, out, stats, act, drop, _shift_seed(_mix_seed(seed, 1, i), sample0 * y.HW * y.C),
-                              v_keep=vk, u_cache=u, u_valid=uv)
+            if l.bn:
+                stats = conv_batchnorm_act(op, 0, src, flat, l, y, out, bn, act, drop,
+                                           _shift_seed(_mix_seed(seed, 1, i), sample0 * y.HW * y.C), v_keep=vk, u_cache=u, u_valid=uv)
+            else:
+                conv_instnorm_act(op, 0, src, flat, l.p_off, y, out, stats, act, drop, _shift_seed(_mix_seed(seed, 1, i), sample0 * y.HW * y.C),
+                                  v_keep=vk, u_cache=u, u_valid=uv)
             c.v.append(vk)
             c.y.append(y)
             c.stats.append(stats)
@@ -1120,11 +1307,15 @@ class GeneratorEngine(_WeightPrep):
             out = cat.channels(0, l.b)
             if l.norm:
                 yd = View.alloc(N, op.Hb, op.Wb, l.b, dev, bf=bf)
-                stats = torch.empty(N * l.b * 2, dtype=torch.float32, device=dev)
                 drop = 0.2 if (train and l.dropout) else 0.0
                 u, uv = _ucache(ucache, ('d', i), 1, op, dev, src, yd, l.p_off)
-                conv_instnorm_act(op, 1, src, flat, l.p_off, yd, out, stats, act, drop,
-                                  _shift_seed(_mix_seed(seed, 2, i), sample0 * yd.HW * yd.C), u_cache=u, u_valid=uv)
+                if l.bn:
+                    stats = conv_batchnorm_act(op, 1, src, flat, l, yd, out, bn, act, drop,
+                                               _shift_seed(_mix_seed(seed, 2, i), sample0 * yd.HW * yd.C), u_cache=u, u_valid=uv)
+                else:
+                    stats = torch.empty(N * l.b * 2, dtype=torch.float32, device=dev)
+                    conv_instnorm_act(op, 1, src, flat, l.p_off, yd, out, stats, act, drop,
+                                      _shift_seed(_mix_seed(seed, 2, i), sample0 * yd.HW * yd.C), u_cache=u, u_valid=uv)
                 c.yd[i], c.statsd[i] = yd, stats
             else:
                 op.small2big(src, flat, l.p_off, None, 0, out, act)
@@ -1176,7 +1367,11 @@ class GeneratorEngine(_WeightPrep):
             g = dcat.channels(0, l.b)
             dskip[5 - i] = dcat.channels(l.b, dcat.C - l.b)
             dy = View.alloc(N, op.Hb, op.Wb, l.b, dev, bf=bf)
-            if l.norm:
+            if l.bn:
+                drop = 0.2 if (c.train and l.dropout) else 0.0
+                batchnorm_act_bwd(l, c.bn_train, c.bn_nseg, gflat, g, None, c.yd[i], c.statsd[i], dy, act, drop,
+                                  _shift_seed(_mix_seed(c.seed, 2, i), c.sample0 * dy.HW * dy.C))
+            elif l.norm:
                 drop = 0.2 if (c.train and l.dropout) else 0.0
                 instnorm_act_bwd(g, None, c.yd[i], c.statsd[i], dy, act, drop,
                                  _shift_seed(_mix_seed(c.seed, 2, i), c.sample0 * dy.HW * dy.C))
@@ -1207,8 +1402,12 @@ class GeneratorEngine(_WeightPrep):
             l, op = self.enc[j], enc_ops[j]
             dy = View.alloc(N, op.Hs, op.Ws, l.a, dev, bf=bf and (j > 0 or c.seam8))
             drop = 0.2 if (c.train and l.dropout) else 0.0
-            instnorm_act_bwd(g_main, dskip[j] if j < 6 else None, c.y[j], c.stats[j], dy, act, drop,
-                             _shift_seed(_mix_seed(c.seed, 1, j), c.sample0 * dy.HW * dy.C))
+            if l.bn:
+                batchnorm_act_bwd(l, c.bn_train, c.bn_nseg, gflat, g_main, dskip[j] if j < 6 else None, c.y[j], c.stats[j], dy, act, drop,
+                                  _shift_seed(_mix_seed(c.seed, 1, j), c.sample0 * dy.HW * dy.C))
+            else:
+                instnorm_act_bwd(g_main, dskip[j] if j < 6 else None, c.y[j], c.stats[j], dy, act, drop,
+                                 _shift_seed(_mix_seed(c.seed, 1, j), c.sample0 * dy.HW * dy.C))
             src = (c.xin8 if c.seam8 else c.xin) if j == 0 else c.enc_out[j - 1]
             op.wgrad(dy, src, gflat, l.p_off, v_pre=c.v[j] if ConvOp._aligned(dy, src) else None)
             done(l)
@@ -1227,8 +1426,9 @@ class GeneratorEngine(_WeightPrep):
 # ------------------------------------------------------------------------------------------------
 
 
-def disc_layers(input_nc, ndf, n_layers, norm):
-    """Layer plan of reference Discriminator.__init__ (disc.py:19-46); keys are nn.Sequential indices."""
+def disc_layers(input_nc, ndf, n_layers, norm, norm_kind='instance'):
+    """Layer plan of reference Discriminator.__init__ (disc.py:19-46); keys are nn.Sequential indices (a norm is the third module
+    of its block: Conv, Tanh, norm)."""
     layers = []
     idx = 0
     layers.append(LayerSpec(f'model.{idx}.weight', ndf, input_nc, 2, False, 'leakyrelu', False, bias_key=f'model.{idx}.bias'))
@@ -1236,10 +1436,12 @@ def disc_layers(input_nc, ndf, n_layers, norm):
     mult = 1
     for n in range(1, n_layers):
         prev, mult = mult, min(2 ** n, 8)
-        layers.append(LayerSpec(f'model.{idx}.weight', ndf * mult, ndf * prev, 2, False, 'tanh', norm))
+        layers.append(LayerSpec(f'model.{idx}.weight', ndf * mult, ndf * prev, 2, False, 'tanh', norm, norm_kind=norm_kind,
+                                norm_key=f'model.{idx + 2}'))
         idx += 3 if norm else 2
     prev, mult = mult, min(2 ** n_layers, 8)
-    layers.append(LayerSpec(f'model.{idx}.weight', ndf * mult, ndf * prev, 1, False, 'tanh', norm))
+    layers.append(LayerSpec(f'model.{idx}.weight', ndf * mult, ndf * prev, 1, False, 'tanh', norm, norm_kind=norm_kind,
+                            norm_key=f'model.{idx + 2}'))
     idx += 3 if norm else 2
     layers.append(LayerSpec(f'model.{idx}.weight', 1, ndf * mult, 1, False, 'sigmoid', False, bias_key=f'model.{idx}.bias'))
     return layers
@@ -1252,10 +1454,12 @@ class DiscContext:
 class DiscriminatorEngine(_WeightPrep):
     _LD_MULT = 1
 
-    def __init__(self, input_nc, ndf, n_layers, norm, algo=None):
+    def __init__(self, input_nc, ndf, n_layers, norm, algo=None, norm_kind='instance'):
         self.input_nc, self.ndf, self.n_layers, self.norm = input_nc, ndf, n_layers, norm
-        self.layers = disc_layers(input_nc, ndf, n_layers, norm)
+        self.layers = disc_layers(input_nc, ndf, n_layers, norm, norm_kind)
         self.nparams = assign_offsets(self.layers)
+        self.has_bn = bool(norm) and norm_kind == 'batch'
+        self.nbuf, self.nbn, self.nscratch = assign_buffers(self.layers)
         self.algo = DEFAULT_ALGO if algo is None else algo
         self.act_bf = False          # bf16 activation storage (set_precision('bf16'); needs ndf % 4 == 0 and ndf >= 32)
         self._ops = {}
@@ -1286,15 +1490,18 @@ class DiscriminatorEngine(_WeightPrep):
         op = self.ops(N, H, W)[-1]
         return (N, 1, op.Hs, op.Ws)
 
-    def forward(self, flat, din, ucache=None, keep_v=False):
+    def forward(self, flat, din, ucache=None, keep_v=False, bn=None):
         """din: View [N,H,W,input_nc].  Returns a context; ctx.out is the sigmoid patch map View [N,h,w,1].
         ucache: a dict owned by the caller that lives exactly as long as the weights in `flat` stay unchanged (Trainer.batch: one
         step) -- the Winograd-transformed weights are computed once per (layer, direction) and reused by every pass that
-        shares the dict.  keep_v: a backward pass with weight gradients follows (see GeneratorEngine.forward)."""
+        shares the dict.  keep_v: a backward pass with weight gradients follows (see GeneratorEngine.forward).  bn: a BNRun (BatchNorm
+        networks only)."""
+        assert bn is not None or not self.has_bn, 'a BatchNorm discriminator pass needs its BNRun'
         ops = self.ops(din.N, din.H, din.W)
         dev = flat.device
         c = DiscContext()
         c.din, c.N, c.H, c.W = din, din.N, din.H, din.W
+        c.bn_train, c.bn_nseg = (bn.train, bn.nseg) if bn is not None else (False, 1)
         c.t, c.stats, c.a, c.v, c.src = [], [], [], [], []
         # bf16 activation storage: the tensors between the first and the last layer are bf16; the input (x | mask), the first
         # layer's conv output (4-channel input: generic kernel) and the 1-channel head stay fp32
@@ -1319,8 +1526,11 @@ class DiscriminatorEngine(_WeightPrep):
             op.big2small(src, flat, l.p_off, bias, l.b_off, t, L.ACT_CODES[l.act], v_keep=vk, u_cache=u, u_valid=uv)   # conv + bias + act fused
             if l.norm:                                                              # disc.py:31-32: Conv -> Tanh -> IN
                 a = View.alloc(din.N, op.Hs, op.Ws, l.a, dev, bf=bf and li < last)
-                stats = torch.empty(din.N * l.a * 2, dtype=torch.float32, device=dev)
-                instnorm_act_fwd(t, a, stats, L.ACT_NONE)
+                if l.bn:
+                    stats = batchnorm_act_fwd(l, bn, flat, t, a, L.ACT_NONE)
+                else:
+                    stats = torch.empty(din.N * l.a * 2, dtype=torch.float32, device=dev)
+                    instnorm_act_fwd(t, a, stats, L.ACT_NONE)
             else:
                 if bf and li == 0 and not seam8:
                     t = t.converted(True)          # the next layer's kernel reads bf16
@@ -1357,7 +1567,11 @@ class DiscriminatorEngine(_WeightPrep):
             else:
                 if l.norm:
                     dt = View.alloc(c.N, op.Hs, op.Ws, l.a, dev, bf=inner)
-                    instnorm_act_bwd(g, None, c.t[li], c.stats[li], dt, L.ACT_NONE)
+                    if l.bn:
+                        batchnorm_act_bwd(l, c.bn_train, c.bn_nseg, gflat if need_wgrad else None, g, None, c.t[li], c.stats[li], dt,
+                                          L.ACT_NONE)
+                    else:
+                        instnorm_act_bwd(g, None, c.t[li], c.stats[li], dt, L.ACT_NONE)
                     g = dt
                 dy = View.alloc(c.N, op.Hs, op.Ws, l.a, dev, bf=inner)
                 act_bwd(g, None, c.t[li], dy, L.ACT_CODES[l.act])

@@ -71,13 +71,18 @@ def predict_image(generator, image, size, overlap, threshold, max_tiles=None):
     4096 x 4096 one (324 tiles) six -- activation memory and every tensor's byte extent stay bounded whatever the image size."""
     from . import engine as E
     eng = generator.engine
+    if eng.has_bn and generator.training:
+        # batch statistics would depend on how the tiles are grouped into passes (max_tiles); the reference's patchgan_infer
+        # always calls .eval()
+        raise ValueError("predict_image: a BatchNorm2d generator in training mode would normalise each pass of tiles with its own "
+                         "batch statistics -- call generator.eval() first (the running statistics are used then)")
     tiles = E.tiles_gather(image, size, overlap)
     pred = E.View.alloc(tiles.N, size, size, eng.output_nc, image.device)
     if max_tiles is None:
         max_tiles = max(1, (64 * 256 * 256) // (size * size))
     for t0 in range(0, tiles.N, max_tiles):
         n = min(max_tiles, tiles.N - t0)
-        eng.forward(generator.flat, tiles.samples(t0, n), pred.samples(t0, n), False, 0)
+        eng.forward(generator.flat, tiles.samples(t0, n), pred.samples(t0, n), False, 0, bn=generator.bn_run())
     mask = E.tiles_blend(pred, tuple(image.shape[1:]), threshold, overlap)
     # device -> host through a pinned block of torch's caching host allocator (the numpy array keeps it alive; it returns to the cache when
     # the caller drops the mask): a pageable .cpu() of the 8-MB float64 mask took 0.3-1.2 ms of the 3-ms image, this one 0.15

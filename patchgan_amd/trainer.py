@@ -245,6 +245,9 @@ class Trainer:
         if dev.type != 'cuda':
             raise RuntimeError("patchgan_amd.Trainer needs the networks on a HIP device (generator.to('cuda')); "
                                "there is no CPU path")
+        if (G.engine.has_bn or D.engine.has_bn) and _dist().on:
+            # per-rank batch statistics would break "the sum over ranks is the large batch's step" (parallel.py); no SyncBatchNorm
+            raise NotImplementedError("patchgan_amd: data parallelism is not implemented for nn.BatchNorm2d networks")
         # device-side input pipeline (opt-in, beyond the reference): decoded bytes x uint8 [N,H,W,Cin] + label map y uint8
         # [N,H,W]; `/255.` and the one-hot mask over self.label_values (io.py:42-56) run on the GPU after a 4x smaller H2D
         u8 = isinstance(x, torch.Tensor) and x.dtype == torch.uint8
@@ -370,7 +373,9 @@ class Trainer:
         # G's weights are constant from here to its Adam step: its Winograd-transformed / packed bf16 weights for this step are made by
         # one batched launch (from the second step on; engine._WeightPrep), shared by forward and backward where one copy serves both
         gcache = ge.ucache_begin(G.flat, N, H, W) if train else None
-        gc = ge.forward(G.flat, xin, gen, G.training, seed, sample0=dist.rank * N, keep_v=train, ucache=gcache)   # trainer.py:63
+        gc = ge.forward(G.flat, xin, gen, G.training, seed, sample0=dist.rank * N, keep_v=train, ucache=gcache,
+                        bn=G.bn_run())                                                        # trainer.py:63
+        G.bn_update(1)        # BatchNorm generator in training mode: its one running-statistics update of the step
         self._mark('G fwd done')
         self.flush()          # D's deferred all-reduce + Adam from the previous step ran under this G forward
         self._mark('flushed')
@@ -389,13 +394,15 @@ class Trainer:
         if ex.enabled and E.PROFILER is None and EARLY_D_FWD:      # (bf16 networks too: 5.93 -> 5.84 ms at cfg4)
             n_prepared = len(ucache)
             with E.on_side():
-                dc2 = de.forward(D.flat, din, ucache=ucache, keep_v=train)
+                dc2 = de.forward(D.flat, din, ucache=ucache, keep_v=train, bn=D.bn_run(1, 2))
                 self._mark('side: dc2 fwd done')
             if len(ucache) != n_prepared:
                 # (a transformed-weight entry the batched preparation did not cover was made by a kernel on the second stream -- the
                 #  first steps after a change of tuning: the passes below would take it as ready, so they wait for it this once)
                 E.side_join()
-        dc = de.forward(D.flat, fake, ucache=ucache)                                          # trainer.py:66
+        # (BatchNorm discriminator: this pass's batch statistics go to slot 0, the 2N pass's halves to slots 1 and 2 -- the order of the
+        #  reference's three calls, trainer.py:66,97,99, whichever pass runs first here)
+        dc = de.forward(D.flat, fake, ucache=ucache, bn=D.bn_run(0, 1))                       # trainer.py:66
         gseg = E.View.alloc(N, H, W, Cout, dev) if train else None
         E.loss_finish(seg_pending, _LOSS_MODES[self.loss_type], float(self.seg_alpha), gseg, losses, 0, Bglobal,
                       self.tversky_gamma)                                                     # trainer.py:71-82
@@ -433,9 +440,10 @@ class Trainer:
 
         # ---- discriminator step: real and (pre-update, detached) fake in one 2N batch        trainer.py:96-99
         if dc2 is None:
-            dc2 = de.forward(D.flat, din, ucache=ucache, keep_v=train)
+            dc2 = de.forward(D.flat, din, ucache=ucache, keep_v=train, bn=D.bn_run(1, 2))
         if ex.pending or ex.keep:
             E.side_join()
+        D.bn_update(3)        # BatchNorm discriminator in training mode: the three passes' updates in the reference's order (on this stream, after the join)
         self._mark('joined')
         capturing = self._adam_dev is not None      # (a step being captured ends with every chain joined: nothing is deferred across its end)
         adam_g_behind_fork = bool(train and late_adam_g and ex.enabled and E.PROFILER is None and DEFER_D_BWD and ADAM_G_BESIDE and not capturing)

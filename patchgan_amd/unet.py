@@ -19,7 +19,8 @@ class _UNetFn(torch.autograd.Function):
         xin = E.View.alloc(N, H, W, C, dev).from_nchw(x.to(device=dev, dtype=torch.float32))
         gen = E.View.alloc(N, H, W, eng.output_nc, dev)
         seed = module._next_seed() if module.training else 0
-        c = eng.forward(module.flat, xin, gen, module.training, seed)
+        c = eng.forward(module.flat, xin, gen, module.training, seed, bn=module.bn_run())
+        module.bn_update(1)          # training mode: this call's batch statistics into the running statistics, as torch does
         ctx.module, ctx.c = module, c
         ctx.need_dx = x.requires_grad
         out = gen.to_nchw()
@@ -36,7 +37,7 @@ class _UNetFn(torch.autograd.Function):
         dev = module.flat.device
         g = E.View.alloc(c.N, c.H, c.W, eng.output_nc, dev).from_nchw(gout.to(torch.float32))
         gflat = torch.zeros_like(module.flat)
-        dx = eng.backward(module.flat, gflat, c, g, None, need_dx=ctx.need_dx)
+        dx = eng.backward(module.flat, gflat, c, g, None, need_dx=ctx.need_dx)      # (BatchNorm: with the coefficients saved in c)
         views = E.torch_views(gflat, eng.layers)
         grads = tuple(views[k] for k in module._param_keys)
         return (None, dx.to_nchw() if dx is not None else None, None) + grads
@@ -44,15 +45,14 @@ class _UNetFn(torch.autograd.Function):
 
 class UNet(FlatParamModule, Transferable):
     """UNet(input_nc, output_nc, nf=64, norm_layer=InstanceNorm2d, use_dropout=False, activation='tanh',
-    final_act='softmax') -- reference unet.py:76-78.  Only nn.InstanceNorm2d is supported as norm_layer."""
+    final_act='softmax') -- reference unet.py:76-78.  norm_layer: nn.InstanceNorm2d or nn.BatchNorm2d (its defaults)."""
 
     def __init__(self, input_nc, output_nc, nf=64, norm_layer=nn.InstanceNorm2d, use_dropout=False,
                  activation='tanh', final_act='softmax'):
         super().__init__()
-        if norm_layer is not nn.InstanceNorm2d:
-            raise NotImplementedError("patchgan_amd.UNet implements nn.InstanceNorm2d blocks only")
-        self.engine = E.GeneratorEngine(input_nc, output_nc, nf, activation, final_act, use_dropout)
-        self._param_keys = [l.key for l in self.engine.layers]
+        kind = E.norm_kind_of(norm_layer, 'patchgan_amd.UNet')
+        self.engine = E.GeneratorEngine(input_nc, output_nc, nf, activation, final_act, use_dropout, norm_kind=kind)
+        self._param_keys = E.param_keys(self.engine.layers)
         self._seed_base = int(torch.initial_seed()) & 0xFFFFFFFF
         self._calls = 0
         self._init_flat(self.engine.layers, self.engine.nparams)
