@@ -132,11 +132,13 @@ size_t pg_conv_workspace_bytes(const pg_conv_geom* g, int op);   /* op 3 = pg_co
  * channels).  Codes >= 1000: 1000 + 100 * ring + 10 * dir + tile = the LDS-DMA bf16 kernels k_conv_bf16x on bf16 tensors, 1020 + tile =
  * k_wgrad_bf16x, 1030 + tile = bf16 row GEMM + col2im, 1040 + tile = k_conv_bf16x on 8-channel pixels, 1050 = the one-channel head's data
  * gradient k_s2b_ca1 / k_s2b_ca1_s1, 1060 + Cb (1070 + Cb: from a bf16 tensor) = the one-pass transposed convolution onto <= 8 channels
- * k_s2b_tapnf<Cb> (Cb > 4: two launches, <4> + <Cb - 4>).  For profiling only. */
+ * k_s2b_tapnf<Cb> (Cb > 4: two launches, <4> + <Cb - 4>).  The numbers are encoded from the plan of the one planner that the entry points
+ * launch from, made for 16-byte-aligned contiguous tensors.  For profiling only. */
 int pg_conv_describe(const pg_conv_geom* g, int op, size_t ws_bytes, int* tile_id, int* split, long* workgroups);
 
 /* The kernel symbol (as rocprofv3 prints it, without the namespace / argument list) of the main GEMM kernel that op would
- * launch -- the same decision code as the entry points, so profiles can be attributed without re-deriving the dispatch --
+ * launch -- read from the plan of the same planner call the entry points make (with the views of a 16-byte-aligned contiguous call), so
+ * profiles can be attributed without re-deriving the dispatch --
  * its split-K factor, and the FLOPs that kernel executes on the MFMA pipe (the direct-convolution count 2*N*Hs*Ws*16*Ca*Cb
  * for the implicit-GEMM kernels, 2.25-4x fewer for the Winograd kernels, ragged tiles included).  `op` as in
  * pg_conv_describe.  For profiling only. */

@@ -17,8 +17,7 @@
 #include <stdio.h>
 #include <stdint.h>
 #include <stdlib.h>
-#include <alloca.h>
-#include <new>
+#include <type_traits>
 #include <vector>
 #include "patchgan_hip.h"
 #include "pg_common.h"
@@ -3227,6 +3226,8 @@ Plan plan_wgrad(const pg_conv_geom* g) {
 
 constexpr int DIRECT_WGRAD_SLICES = 64;
 constexpr int COLSUM_CHUNKS = 1024;
+// the bias gradient's partial column sums, reserved at the head of the weight gradient's workspace
+inline size_t colsum_bytes(int Ca) { return ((size_t)COLSUM_CHUNKS * Ca * sizeof(float) + 255) & ~(size_t)255; }
 
 void clamp_split(Plan& p, size_t ws_bytes, size_t reserved) {
     size_t avail = ws_bytes > reserved ? ws_bytes - reserved : 0;
@@ -3263,23 +3264,29 @@ int launch_reduce(const float* slabs, long slab_stride, int S, float* out, int l
     return hipGetLastError() == hipSuccess ? PG_OK : PG_ELAUNCH;
 }
 
-#define PG_DISPATCH_TILE(KERNEL, tile_id, grid, st, ...)                                                   \
-    switch (tile_id) {                                                                                     \
-        case 0: hipLaunchKernelGGL((KERNEL<2, 2, 2, 2>), grid, dim3(256), 0, st, __VA_ARGS__); break;      \
-        case 1: hipLaunchKernelGGL((KERNEL<2, 1, 2, 2>), grid, dim3(256), 0, st, __VA_ARGS__); break;      \
-        case 2: hipLaunchKernelGGL((KERNEL<1, 1, 4, 1>), grid, dim3(256), 0, st, __VA_ARGS__); break;      \
-        case 3: hipLaunchKernelGGL((KERNEL<1, 2, 2, 2>), grid, dim3(256), 0, st, __VA_ARGS__); break;      \
-        default: hipLaunchKernelGGL((KERNEL<1, 1, 2, 2>), grid, dim3(256), 0, st, __VA_ARGS__); break;     \
+// the five <MR,NR,WM,WN> tilings behind the tile ids of pick_tile(): f receives the tuple as a type,
+//     for_tile(id, [&](auto t) { using T = decltype(t); hipLaunchKernelGGL((k<PG_TILE(T), ...>), ...); });
+template <int MR_, int NR_, int WM_, int WN_>
+struct TileT {
+    static constexpr int MR = MR_, NR = NR_, WM = WM_, WN = WN_;
+};
+#define PG_TILE(T) T::MR, T::NR, T::WM, T::WN
+template <class F>
+inline void for_tile(int tile_id, F&& f) {
+    switch (tile_id) {
+        case 0: f(TileT<2, 2, 2, 2>{}); break;
+        case 1: f(TileT<2, 1, 2, 2>{}); break;
+        case 2: f(TileT<1, 1, 4, 1>{}); break;
+        case 3: f(TileT<1, 2, 2, 2>{}); break;
+        default: f(TileT<1, 1, 2, 2>{}); break;
     }
-
-#define PG_DISPATCH_TAPN(MODE, tile_id, grid, st, ...)                                                              \
-    switch (tile_id) {                                                                                             \
-        case 0: hipLaunchKernelGGL((k_wgrad_tapn<2, 2, 2, 2, MODE>), grid, dim3(256), 0, st, __VA_ARGS__); break;  \
-        case 1: hipLaunchKernelGGL((k_wgrad_tapn<2, 1, 2, 2, MODE>), grid, dim3(256), 0, st, __VA_ARGS__); break;  \
-        case 2: hipLaunchKernelGGL((k_wgrad_tapn<1, 1, 4, 1, MODE>), grid, dim3(256), 0, st, __VA_ARGS__); break;  \
-        case 3: hipLaunchKernelGGL((k_wgrad_tapn<1, 2, 2, 2, MODE>), grid, dim3(256), 0, st, __VA_ARGS__); break;  \
-        default: hipLaunchKernelGGL((k_wgrad_tapn<1, 1, 2, 2, MODE>), grid, dim3(256), 0, st, __VA_ARGS__); break; \
-    }
+}
+// a run-time flag as a template argument: f(std::true_type{}) / f(std::false_type{})
+template <class F>
+inline void for_bool(bool b, F&& f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
 
 // taps-folded-into-N forward paths: eligibility and workspace (floats)
 inline bool s2b_tapn_ok(const Geom& g) { return g.Cb <= 8 && g.Ca % KC == 0 && !force_generic(); }
@@ -3291,59 +3298,11 @@ inline bool tapnf_enabled() {
 inline bool s2b_tapnf_ok(const Geom& g) {
     return g.s == 2 && g.Cb <= 8 && (g.Ca == 32 || g.Ca == 64 || g.Ca == 128) && !force_generic() && tapnf_enabled();
 }
-struct Tune;
-inline bool s2b_tapnf_bf_ok(const Geom& g, int algo_full, const Tune& t);      // the same kernel on a bf16 `small` (PG_ALGO_BF16), below Tune
-// one launch of k_s2b_tapnf (the caller has checked eligibility, alignment and the 32-bit offset limits)
-static int launch_tapnf(bool bf, const void* small, int ld_small, const float* P, const float* bias, float* big, int ld_big, const Geom& g,
-                        int act, long small_bytes, long big_bytes, hipStream_t st);
 inline bool b2s_tapn_ok(const Geom& g) { return g.Ca <= 8 && g.Cb % KC == 0 && !force_generic(); }
 inline size_t s2b_tapn_ws(const Geom& g) {
     return ((size_t)16 * g.Cb * g.Ca + (size_t)g.N * g.Hs * g.Ws * 16 * g.Cb) * sizeof(float) + 256;
 }
 inline size_t b2s_tapn_ws(const Geom& g) { return (size_t)g.N * g.Hb * g.Wb * 16 * g.Ca * sizeof(float); }
-
-#define PG_DISPATCH_B2SF(ONE, tile_id, grid, st, ...)                                                              \
-    switch (tile_id) {                                                                                            \
-        case 0: hipLaunchKernelGGL((k_b2s_fast<2, 2, 2, 2, ONE>), grid, dim3(256), 0, st, __VA_ARGS__); break;    \
-        case 1: hipLaunchKernelGGL((k_b2s_fast<2, 1, 2, 2, ONE>), grid, dim3(256), 0, st, __VA_ARGS__); break;    \
-        case 2: hipLaunchKernelGGL((k_b2s_fast<1, 1, 4, 1, ONE>), grid, dim3(256), 0, st, __VA_ARGS__); break;    \
-        case 3: hipLaunchKernelGGL((k_b2s_fast<1, 2, 2, 2, ONE>), grid, dim3(256), 0, st, __VA_ARGS__); break;    \
-        default: hipLaunchKernelGGL((k_b2s_fast<1, 1, 2, 2, ONE>), grid, dim3(256), 0, st, __VA_ARGS__); break;   \
-    }
-
-#define PG_DISPATCH_B2SH(HIN, tile_id, grid, st, ...)                                                                    \
-    switch (tile_id) {                                                                                                  \
-        case 0: hipLaunchKernelGGL((k_b2s_bf16<2, 2, 2, 2, false, HIN>), grid, dim3(256), 0, st, __VA_ARGS__); break;   \
-        case 1: hipLaunchKernelGGL((k_b2s_bf16<2, 1, 2, 2, false, HIN>), grid, dim3(256), 0, st, __VA_ARGS__); break;   \
-        case 2: hipLaunchKernelGGL((k_b2s_bf16<1, 1, 4, 1, false, HIN>), grid, dim3(256), 0, st, __VA_ARGS__); break;   \
-        case 3: hipLaunchKernelGGL((k_b2s_bf16<1, 2, 2, 2, false, HIN>), grid, dim3(256), 0, st, __VA_ARGS__); break;   \
-        default: hipLaunchKernelGGL((k_b2s_bf16<1, 1, 2, 2, false, HIN>), grid, dim3(256), 0, st, __VA_ARGS__); break;  \
-    }
-#define PG_DISPATCH_S2BH(HIN, tile_id, grid, st, ...)                                                              \
-    switch (tile_id) {                                                                                            \
-        case 0: hipLaunchKernelGGL((k_s2b_bf16<2, 2, 2, 2, HIN>), grid, dim3(256), 0, st, __VA_ARGS__); break;    \
-        case 1: hipLaunchKernelGGL((k_s2b_bf16<2, 1, 2, 2, HIN>), grid, dim3(256), 0, st, __VA_ARGS__); break;    \
-        case 2: hipLaunchKernelGGL((k_s2b_bf16<1, 1, 4, 1, HIN>), grid, dim3(256), 0, st, __VA_ARGS__); break;    \
-        case 3: hipLaunchKernelGGL((k_s2b_bf16<1, 2, 2, 2, HIN>), grid, dim3(256), 0, st, __VA_ARGS__); break;    \
-        default: hipLaunchKernelGGL((k_s2b_bf16<1, 1, 2, 2, HIN>), grid, dim3(256), 0, st, __VA_ARGS__); break;   \
-    }
-#define PG_DISPATCH_WGH(POW2, HIN, tile_id, grid, st, ...)                                                              \
-    switch (tile_id) {                                                                                                 \
-        case 0: hipLaunchKernelGGL((k_wgrad_bf16<2, 2, 2, 2, POW2, HIN>), grid, dim3(256), 0, st, __VA_ARGS__); break;  \
-        case 1: hipLaunchKernelGGL((k_wgrad_bf16<2, 1, 2, 2, POW2, HIN>), grid, dim3(256), 0, st, __VA_ARGS__); break;  \
-        case 2: hipLaunchKernelGGL((k_wgrad_bf16<1, 1, 4, 1, POW2, HIN>), grid, dim3(256), 0, st, __VA_ARGS__); break;  \
-        case 3: hipLaunchKernelGGL((k_wgrad_bf16<1, 2, 2, 2, POW2, HIN>), grid, dim3(256), 0, st, __VA_ARGS__); break;  \
-        default: hipLaunchKernelGGL((k_wgrad_bf16<1, 1, 2, 2, POW2, HIN>), grid, dim3(256), 0, st, __VA_ARGS__); break; \
-    }
-
-#define PG_DISPATCH_WGF(POW2, tile_id, grid, st, ...)                                                              \
-    switch (tile_id) {                                                                                            \
-        case 0: hipLaunchKernelGGL((k_wgrad_fast<2, 2, 2, 2, POW2>), grid, dim3(256), 0, st, __VA_ARGS__); break;  \
-        case 1: hipLaunchKernelGGL((k_wgrad_fast<2, 1, 2, 2, POW2>), grid, dim3(256), 0, st, __VA_ARGS__); break;  \
-        case 2: hipLaunchKernelGGL((k_wgrad_fast<1, 1, 4, 1, POW2>), grid, dim3(256), 0, st, __VA_ARGS__); break;  \
-        case 3: hipLaunchKernelGGL((k_wgrad_fast<1, 2, 2, 2, POW2>), grid, dim3(256), 0, st, __VA_ARGS__); break;  \
-        default: hipLaunchKernelGGL((k_wgrad_fast<1, 1, 2, 2, POW2>), grid, dim3(256), 0, st, __VA_ARGS__); break; \
-    }
 
 inline bool tapkp_enabled() {          // PATCHGAN_TAPK_ONESHOT=1 (experiment): the one-shot k_b2s_tapk instead of the persistent k_b2s_tapkp
     static const bool off = [] {
@@ -3424,7 +3383,7 @@ inline Tune tune_of(int algo) {
     if (algo & PG_TUNE_BF16X_RING) t.bf16ring = 1;
     if (algo & PG_TUNE_BF16X_FLAT) t.bf16ring = 0;
     if (algo & PG_TUNE_S3_OFF) t.s3 = t.s3w = t.s3r = false;
-    if (force_generic()) t.wino = false;
+    if (force_generic()) t.wino = t.bf16x = false;
     return t;
 }
 // every path on, for sizing a workspace that serves any tuning
@@ -3476,7 +3435,7 @@ inline bool s2b_ca1_ok(const Geom& g, int algo_full) {
 }
 // PG_ALGO_BF16 with the input activation stored as bf16: the LDS-DMA kernels of conv_bf16.hip (dir 0: big -> small, 1: small -> big)
 inline bool bf16x_ok(const Geom& g, int dir, int algo_full, const Tune& t) {
-    if ((algo_full & PG_ALGO_MASK) != PG_ALGO_BF16 || !t.bf16x || force_generic()) return false;
+    if ((algo_full & PG_ALGO_MASK) != PG_ALGO_BF16 || !t.bf16x) return false;
     if (!(algo_full & (dir == 0 ? PG_IO_BIG_BF16 : PG_IO_SMALL_BF16))) return false;
     // big -> small from a few-channel `big`: the 8-channel-pixel form (dir 2; the caller also checks ld_big == 8)
     if (dir == 0 && g.Cb <= 8) return pg_bf16x_geom_ok(2, g.N, g.Hb, g.Wb, g.Hs, g.Ws, g.Ca, g.Cb, g.s);
@@ -3484,7 +3443,7 @@ inline bool bf16x_ok(const Geom& g, int dir, int algo_full, const Tune& t) {
 }
 // small -> big onto a few-channel `big` from a bf16 `small`: row GEMM on the bf16 kernels (dir 3) + k_col2im_small2big; fp32 output
 inline bool bf16x_s2b_tapn_ok(const Geom& g, int algo_full, const Tune& t) {
-    if ((algo_full & PG_ALGO_MASK) != PG_ALGO_BF16 || !t.bf16x || force_generic()) return false;
+    if ((algo_full & PG_ALGO_MASK) != PG_ALGO_BF16 || !t.bf16x) return false;
     if ((algo_full & PG_IO_MASK) != PG_IO_SMALL_BF16 || g.Cb > 8) return false;
     return pg_bf16x_geom_ok(3, g.N, g.Hb, g.Wb, g.Hs, g.Ws, g.Ca, 16 * g.Cb, g.s);
 }
@@ -3492,15 +3451,21 @@ inline bool s2b_tapnf_bf_ok(const Geom& g, int algo_full, const Tune& t) {
     if ((algo_full & PG_ALGO_MASK) != PG_ALGO_BF16 || !t.bf16x || (algo_full & PG_IO_MASK) != PG_IO_SMALL_BF16) return false;
     return s2b_tapnf_ok(g);
 }
+inline long tapnf_blocks(const Geom& g) {
+    return (long)g.N * ((g.Hb + 2 * TF_H - 2) / (2 * TF_H - 2)) * ((g.Wb + 2 * TF_W - 2) / (2 * TF_W - 2));
+}
+// its workgroups per chip by LDS and registers: 2 per CU for 128 fp32 input channels, else 3
+inline int tapnf_wgs(const Geom& g, bool bf) {
+    static const int wgs_env = pg_exp_env("PATCHGAN_TAPNF_WG") ? atoi(pg_exp_env("PATCHGAN_TAPNF_WG")) : 0;
+    return wgs_env > 0 ? wgs_env : (g.Ca == 128 && !bf) ? 512 : 768;
+}
+// one launch of k_s2b_tapnf (the planner has checked eligibility, alignment and the 32-bit offset limits)
 static int launch_tapnf(bool bf, const void* small, int ld_small, const float* P, const float* bias, float* big, int ld_big, const Geom& g,
                         int act, long small_bytes, long big_bytes, hipStream_t st) {
     const int nbh = (g.Hb + 2 * TF_H - 2) / (2 * TF_H - 2), nbw = (g.Wb + 2 * TF_W - 2) / (2 * TF_W - 2);
-    const long nb = (long)g.N * nbh * nbw;
+    const long nb = tapnf_blocks(g);
     if (nb >= 0x7fffffffL) return PG_EINVAL;
-    // workgroups per CU by LDS and registers: 2 for 128 fp32 input channels, else 3
-    static const int wgs_env = pg_exp_env("PATCHGAN_TAPNF_WG") ? atoi(pg_exp_env("PATCHGAN_TAPNF_WG")) : 0;
-    const int wgs = wgs_env > 0 ? wgs_env : (g.Ca == 128 && !bf) ? 512 : 768;
-    const dim3 grid((unsigned)std::min<long>(nb, wgs));
+    const dim3 grid((unsigned)std::min<long>(nb, tapnf_wgs(g, bf)));
     const int v4 = (g.Cb % 4 == 0 && ld_big % 4 == 0 && aligned16(big)) ? 1 : 0;
     const int sb = (int)small_bytes, bb = (int)big_bytes;
     TimedLaunch timed(st);
@@ -3544,67 +3509,513 @@ inline size_t bf16x_ws(const Geom& g, int dir) {
     return pg_bf16x_w_bytes(g.Ca, g.Cb) + (p.split > 1 ? (size_t)p.split * p.out_elems * sizeof(float) : 0);
 }
 inline bool bf16x_wgrad_ok(const Geom& g, int algo_full, const Tune& t) {
-    if ((algo_full & PG_ALGO_MASK) != PG_ALGO_BF16 || !t.bf16x || force_generic() || (algo_full & PG_IO_MASK) != PG_IO_MASK) return false;
+    if ((algo_full & PG_ALGO_MASK) != PG_ALGO_BF16 || !t.bf16x || (algo_full & PG_IO_MASK) != PG_IO_MASK) return false;
     return pg_bf16x_wgrad_geom_ok(g.N, g.Hb, g.Wb, g.Hs, g.Ws, g.Ca, g.Cb, g.s);
 }
 inline bool aligned_bf_view(const void* p, int ld, bool bf) {
     return (reinterpret_cast<uintptr_t>(p) & 15) == 0 && (ld % (bf ? 8 : 4)) == 0;
 }
 
-// the whole bf16x call: pack (or reuse) the weights, main kernel, split-K reduce.  Returns PG_EINVAL + 1000 when the call is not
-// eligible after all (alignment, workspace): the caller then falls through to the register-staged kernels.
-constexpr int BF16X_SKIP = -1000;
-int bf16x_run(int dir, const void* in, int ld_in, const float* P, const float* bias, void* out, int ld_out, const Geom& g, int act,
-              bool out_bf, void* ws, size_t ws_bytes, hipStream_t st, const pg_conv_extras& x, int ring) {
-    const pg_epi_mul mul{x.mul_t, x.mul_ld, x.mul_act};
-    if (mul.t && (dir != 1 || (reinterpret_cast<uintptr_t>(mul.t) & 15) || mul.ld % (out_bf ? 8 : 4))) return PG_EINVAL;
-    if (x.part && (mul.t || bias || act != PG_ACT_NONE)) return PG_EINVAL;
-    if (dir == 0 && g.Cb <= 8) {       // few-channel big: only in 8-channel pixels (16 bytes = one DMA piece per pixel)
-        if (ld_in != 8) return BF16X_SKIP;
-        dir = 2;
-    }
-    const int Cin = dir == 0 ? g.Cb : dir == 2 ? 8 : g.Ca, Cout = dir == 1 ? g.Cb : g.Ca;
-    const long in_pix = (long)g.N * (dir != 1 ? g.Hb * g.Wb : g.Hs * g.Ws), out_pix = (long)g.N * (dir != 1 ? g.Hs * g.Ws : g.Hb * g.Wb);
-    const long in_bytes = tensor_bytes(in_pix, ld_in, Cin, true);
-    if (!aligned_bf_view(in, ld_in, true) || !aligned_bf_view(out, ld_out, out_bf) || !aligned16(P) || (bias && !aligned16(bias)) ||
-        in_bytes >= FAST_LIMIT)
-        return BF16X_SKIP;
+// ------------------------------------------------------------------------------------------------
+// The planner: which path a call takes is decided HERE, once, in launch order.  The entry points plan with the views of the
+// call and switch on ConvPlan::path; the pg_conv_* queries plan with Views == nullptr (16-byte-aligned contiguous tensors
+// below pg_conv_max_tensor_bytes, no bias, identity activation -- what the header promises for them) and read fields.
+// ------------------------------------------------------------------------------------------------
+enum class Path {
+    Direct,                                                                                    // PG_ALGO_DIRECT
+    Ca1, Wino1, Wino2, Bf16x, Bf16xTapn, TapnfBf, Tapnf, TapnRowGemm, Tapkp, Tapk, Gemm,       // big -> small / small -> big
+    WinoWgrad, Wino2Wgrad, Bf16xWgrad, WgradTapnp, WgradTapn                                   // weight gradient (and Gemm)
+};
+
+// what only a launch knows
+struct Views {
+    const void *small, *big;
+    int ld_small, ld_big;
+    const float *P, *bias;     // ops 0 / 1: the packed weights and the epilogue's bias; op 2: dP and dbias
+    int act;
+    void* ws;
+    const pg_conv_extras* x;   // never null
+};
+static const pg_conv_extras NO_EXTRAS = {nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, 0};
+// hand-overs a query asks about (a launch reads them from Views::x)
+enum { OFFER_PART = 1, OFFER_U = 2, OFFER_V = 4, OFFER_MUL = 8 };
+
+struct ConvPlan {
+    int rc = PG_OK;            // PG_EINVAL: the call passes a hand-over (or bf16 tensors) to a path that has no use for it
+    Path path = Path::Gemm;    // what the entry point launches
+    Path mfma = Path::Gemm;    // ... if it were not PG_ALGO_DIRECT (pg_conv_describe documents "the MFMA path"); else == path
+    Plan gemm{};               // the implicit-GEMM plan, split clamped to the workspace (pg_conv_describe reports it beside Wino1 / WgradTapnp)
+    pg_bf16x_plan bx{};        // Bf16x / Bf16xTapn / Bf16xWgrad
+    int xdir = 0;              // Bf16x: direction of conv_bf16.h (2: 8-channel pixels)
+    Tile tile{};               // Gemm / WgradTapn / TapnRowGemm: output tile of the main kernel
+    int split = 1;             // split-K factor (slabs) of the main kernel
+    long workgroups = 0;
+    bool fast = false, pow2 = false;    // implicit GEMM: buffer-load variant, its power-of-two pixel decode (op 2)
+    int veck = 0, vecn = 0, mode = 0;   // its vector-access flags (op 2: of `small` / `big`); op 2: wgrad_mode()
+    int mo = 0;                         // Wino1: output tile edge
+    bool small_tile = false, mz = false;   // Wino1: 64-tile rows, Wino2: 64-row tiles, Wino*Wgrad: 64x64 output tiles; Wino2: k_wino_bgemm_mz
+    bool ca1_s1 = false;                // Ca1: the LDS-staged per-sample form
+    int vec4 = 0, vec_out = 0;          // Tapk / Tapkp
+    size_t reserved = 0;       // op 2: bytes of the workspace that hold the bias gradient's column sums
+    size_t ws_needed = 0;      // the largest workspace any path this geometry / algo is eligible for asks for
+    size_t u_bytes = 0;        // cached weight transform / pack the path reads (0: none)
+    int stats_chunks = 0;      // InstanceNorm partial-sum chunks per sample its epilogue writes (0: none)
+    bool mul_ok = false;       // its epilogue takes pg_conv_extras.mul_t
+};
+
+// which pack of the weights a Bf16x call reads.  small -> big reads the SAME packed copy as big -> small (transposed staging in the
+// kernel): one pack per layer serves both -- not the ring-staged variant (PG_TUNE_BF16X_RING: it keeps the per-tap transposed pack;
+// callers that share one cache entry between the two directions of a layer must not set that bit, engine._ucache checks it), and not
+// the window-staged kernel, which reads weight fragments straight from global memory (K contiguous per output channel)
+inline int bf16x_pack_dir(const ConvPlan& p, int ring) { return p.bx.win ? 4 + p.xdir : p.xdir == 1 ? (ring > 0 ? 1 : 0) : p.xdir; }
+
+struct PlanCtx {
+    const Geom& g;
+    int algo, io;
+    const Tune& tune;
+    size_t ws_bytes;
+    const Views* v;        // nullptr: a query
+    bool part, has_u, has_v, mul;
+};
+inline void need(ConvPlan& p, size_t bytes) { p.ws_needed = std::max(p.ws_needed, bytes); }
+inline ConvPlan& take(ConvPlan& p, Path w) {
+    p.mfma = w;
+    if (p.path != Path::Direct) p.path = w;
+    return p;
+}
+inline ConvPlan& fail(ConvPlan& p) {
+    p.rc = PG_EINVAL;
+    return p;
+}
+inline long gemm_workgroups(const Plan& q) { return (long)q.tiles_m * q.tiles_n * q.ncls * q.split; }
+inline bool mul_misaligned(const PlanCtx& c, int elems) {
+    return c.v && c.v->x->mul_t && (!aligned16(c.v->x->mul_t) || c.v->x->mul_ld % elems);
+}
+
+// the LDS-DMA bf16 kernels (ops 0 / 1).  false: not eligible after all (alignment, workspace) -- the chain goes on to the
+// register-staged kernels
+bool plan_bf16x(ConvPlan& p, const PlanCtx& c, int dir) {
+    const Geom& g = c.g;
+    const Views* v = c.v;
+    const bool out_bf = c.io & (dir == 0 ? PG_IO_SMALL_BF16 : PG_IO_BIG_BF16);
     const size_t wb = pg_bf16x_w_bytes(g.Ca, g.Cb);
-    void* W = x.u_cache;
-    char* rest = (char*)ws;
-    size_t avail = ws_bytes;
-    if (!W) {
-        if (!ws || !aligned16(ws) || ws_bytes < wb) return BF16X_SKIP;
-        W = ws;
-        rest += wb;
-        avail -= wb;
+    p.u_bytes = wb;
+    need(p, bf16x_ws(g, dir));
+    if (c.mul && (dir != 1 || mul_misaligned(c, out_bf ? 8 : 4))) return fail(p), true;
+    if (v && c.part && (c.mul || v->bias || v->act != PG_ACT_NONE)) return fail(p), true;
+    p.xdir = (dir == 0 && g.Cb <= 8) ? 2 : dir;     // few-channel big: only in 8-channel pixels (16 bytes = one DMA piece per pixel)
+    if (v) {
+        const void* in = dir == 0 ? v->big : v->small;
+        const void* out = dir == 0 ? v->small : v->big;
+        const int ld_in = dir == 0 ? v->ld_big : v->ld_small, ld_out = dir == 0 ? v->ld_small : v->ld_big;
+        if (p.xdir == 2 && ld_in != 8) return false;
+        const long in_pix = (long)g.N * (dir == 0 ? g.Hb * g.Wb : g.Hs * g.Ws);
+        if (!aligned_bf_view(in, ld_in, true) || !aligned_bf_view(out, ld_out, out_bf) || !aligned16(v->P) || (v->bias && !aligned16(v->bias)) ||
+            tensor_bytes(in_pix, ld_in, p.xdir == 0 ? g.Cb : p.xdir == 2 ? 8 : g.Ca, true) >= FAST_LIMIT)
+            return false;
+        if (!c.has_u && (!v->ws || !aligned16(v->ws))) return false;
     }
-    // small -> big reads the SAME packed copy as big -> small (transposed staging in the kernel): one pack per layer serves both
-    // (not the ring-staged variant, PG_TUNE_BF16X_RING: it keeps the per-tap transposed pack; callers that share one cache entry
-    // between the two directions of a layer must not set that bit -- engine._ucache checks it)
-    pg_bf16x_plan p = pg_bf16x_plan_of(dir, g.N, g.Hb, g.Wb, g.Hs, g.Ws, g.Ca, g.Cb, g.s, ring);
-    // (the window-staged kernel reads weight fragments straight from global memory: K contiguous per output channel = the per-tap
-    //  transposed pack for small -> big; pg_conv_prep_batch and pg_bf16x_own_pack() follow the same rule)
-    const int bt = (dir == 1 && !(ring > 0) && !p.win) ? 1 : 0;
-    if (!(x.u_cache && x.u_valid)) {
-        int rc = pg_bf16x_pack(P, W, g.Ca, g.Cb, p.win ? 4 + dir : bt ? 0 : dir, st);
-        if (rc != PG_OK) return rc;
+    if (!c.has_u && c.ws_bytes < wb) return false;     // (a cached pack leaves the whole workspace to the slabs)
+    p.bx = pg_bf16x_plan_of(p.xdir, g.N, g.Hb, g.Wb, g.Hs, g.Ws, g.Ca, g.Cb, g.s, c.tune.bf16ring);
+    pg_bf16x_clamp(&p.bx, c.has_u ? c.ws_bytes : c.ws_bytes - wb);
+    const int chunks = pg_bf16x_stats_chunks(p.xdir, &p.bx, g.N, g.Hb, g.Wb, g.Hs, g.Ws);
+    // the queries promise the statistics epilogue and the multiplier only with the full workspace of the path (unsplit K), and the
+    // statistics only between bf16 tensors of more than 8 channels
+    const bool full_ws = c.ws_bytes >= bf16x_ws(g, dir);
+    p.stats_chunks = v ? chunks : (c.io == PG_IO_MASK && p.xdir != 2 && full_ws) ? chunks : 0;
+    p.mul_ok = dir == 1 && (v || full_ws);
+    if (c.part && (!p.stats_chunks || !out_bf)) return fail(p), true;
+    p.split = p.bx.split;
+    p.workgroups = (long)p.bx.tiles_m * p.bx.tiles_n * p.bx.ncls * p.bx.split;
+    take(p, Path::Bf16x);
+    return true;
+}
+
+// the Winograd paths of ops 0 / 1 (PG_ALGO_AUTO): F(2x2,4x4) / F(3x3,4x4) of a stride-1 layer, polyphase F(3x3,2x2) of a stride-2 layer.
+// true: taken (or the call fails on it)
+bool plan_wino(ConvPlan& p, const PlanCtx& c, int op) {
+    const Geom& g = c.g;
+    const Views* v = c.v;
+    if (c.algo != PG_ALGO_AUTO) return false;
+    const int Ho = op == 0 ? g.Hs : g.Hb, Wo = op == 0 ? g.Ws : g.Wb, Ci = op == 0 ? g.Cb : g.Ca, Co = op == 0 ? g.Ca : g.Cb, mo1 = c.tune.mo1;
+    if (op == 0 ? wino_b2s_ok(g, c.tune) : wino_s2b_ok(g, c.tune)) {
+        const size_t wsb = pg_wino_ws_bytes(g.N, Ho, Wo, Ci, Co, mo1);
+        need(p, wsb);
+        if (c.ws_bytes >= wsb &&
+            (!v || (aligned16(v->P) && aligned16(v->ws) &&
+                    (op == 0 ? pg_wino_eligible(g.N, g.Hb, g.Wb, g.Cb, g.Hs, g.Ws, g.Ca, v->ld_big, v->big, mo1)
+                             : pg_wino_eligible(g.N, g.Hs, g.Ws, g.Ca, g.Hb, g.Wb, g.Cb, v->ld_small, v->small, mo1))))) {
+            if (c.part || (op == 1 && mul_misaligned(c, 4))) return fail(p), true;
+            if (c.has_v && !(wino_wgrad_ok(g, c.tune) && pg_wino_wgrad_v_bytes(g.N, g.Hs, g.Ws, g.Ca, g.Cb, mo1))) return fail(p), true;
+            p.u_bytes = pg_wino_u_bytes(g.N, Ho, Wo, Ci, Co, mo1);
+            p.mo = pg_wino_mo(g.N, Ho, Wo, Ci, Co, mo1);
+            p.small_tile = pg_wino_small_tile(g.N, Ho, Wo, Ci, Co, mo1);
+            p.mul_ok = op == 1;
+            return take(p, Path::Wino1), true;
+        }
     }
-    pg_bf16x_clamp(&p, avail);
-    const int chunks = x.part ? pg_bf16x_stats_chunks(dir, &p, g.N, g.Hb, g.Wb, g.Hs, g.Ws) : 0;
-    if (x.part && (!chunks || !out_bf)) return PG_EINVAL;
-    int rc;
-    {
-        TimedLaunch timed(st);
-        if (p.split == 1)
-            rc = pg_bf16x_conv(dir, in, ld_in, in_bytes, W, out, ld_out, 0L, g.N, g.Hb, g.Wb, g.Hs, g.Ws, g.Ca, g.Cb, g.s, &p, bias, act,
-                               out_bf ? 1 : 0, st, mul, x.part, chunks, bt);
-        else
-            rc = pg_bf16x_conv(dir, in, ld_in, in_bytes, W, rest, Cout, p.out_elems, g.N, g.Hb, g.Wb, g.Hs, g.Ws, g.Ca, g.Cb, g.s, &p,
-                               nullptr, 0, 0, st, pg_epi_mul{nullptr, 0, 0}, nullptr, 0, bt);
+    if (op == 0 ? wino2_b2s_ok(g, c.tune) : wino2_s2b_ok(g, c.tune)) {
+        const size_t wsb = op == 0 ? pg_wino2_ws_bytes(g.N, g.Hs, g.Ws, g.Ca, g.Cb) : pg_wino2c_ws_bytes(g.N, g.Hb, g.Wb, g.Ca, g.Cb);
+        need(p, wsb);
+        if (c.ws_bytes >= wsb && (!v || ((v->ld_big % 4 == 0) && (v->ld_small % 4 == 0) && aligned16(v->big) && aligned16(v->P) &&
+                                         aligned16(v->small) && aligned16(v->ws) && (!v->bias || aligned16(v->bias))))) {
+            p.stats_chunks = op == 0 ? pg_wino2_b2s_stats_chunks(g.N, g.Hs, g.Ws, g.Ca) : pg_wino2_s2b_stats_chunks(g.N, g.Hb, g.Wb, g.Cb);
+            if ((c.part && !p.stats_chunks) || (op == 1 && mul_misaligned(c, 4)) || (c.has_v && pg_wino2_mo() != 3)) return fail(p), true;
+            p.u_bytes = pg_wino2_u_bytes(g.Ca, g.Cb);
+            const long T = op == 0 ? pg_wino2_tiles_b2s(g.N, g.Hs, g.Ws) : pg_wino2_tiles_s2b(g.N, g.Hb, g.Wb);
+            const long X = (long)(pg_wino2_mo() + 1) * (pg_wino2_mo() + 1);
+            p.small_tile = T < 1024;
+            p.mz = !c.tune.s3 && (op == 0 ? pg_wino2_b2s_zb(g.N, g.Hs, g.Ws, g.Ca) : pg_wino2_s2b_zb(g.N, g.Hb, g.Wb, g.Cb)) > 1;
+            p.workgroups = X * ((T + (T >= 1024 ? 127 : 63)) / (T >= 1024 ? 128 : 64)) * (((op == 0 ? g.Ca : 4 * g.Cb) + 127) / 128);
+            p.mul_ok = op == 1;
+            return take(p, Path::Wino2), true;
+        }
     }
-    if (rc != PG_OK || p.split == 1) return rc;
-    return launch_reduce((const float*)rest, p.out_elems, p.split, (float*)out, ld_out, out_pix, Cout, bias, act, st, out_bf ? 1 : 0, mul);
+    return false;
+}
+
+// the row GEMM D[input pixel][(tap, output channel)] of the taps-folded-into-N paths, Nc = 16 * output channels wide
+inline ConvPlan& take_row_gemm(ConvPlan& p, long rows, int Nc) {
+    p.tile = pick_tile(rows, Nc);
+    p.workgroups = ((rows + p.tile.bm - 1) / p.tile.bm) * ((Nc + p.tile.bn - 1) / p.tile.bn);
+    return take(p, Path::TapnRowGemm);
+}
+
+ConvPlan plan_big2small(const pg_conv_geom* gg, const PlanCtx& c) {
+    ConvPlan p;
+    const Geom& g = c.g;
+    const Views* v = c.v;
+    const bool q = !v;
+    p.gemm = plan_b2s(gg);
+    if (p.gemm.split > 1) need(p, (size_t)p.gemm.split * p.gemm.out_elems * sizeof(float));
+    clamp_split(p.gemm, c.ws_bytes, 0);
+    const bool in_bf = c.io & PG_IO_BIG_BF16;
+    const long p_bytes = 16L * g.Ca * g.Cb * 4;
+    p.veck = (g.Cb % 4 == 0) && (q || ((v->ld_big % 4 == 0) && aligned_io(v->big, in_bf) && aligned16(v->P)));
+    p.fast = p.veck && g.Cb >= KC && (q || tensor_bytes((long)g.N * g.Hb * g.Wb, v->ld_big, g.Cb, in_bf) < FAST_LIMIT) &&
+             p_bytes < FAST_P_LIMIT && !force_generic();
+    if (c.algo == PG_ALGO_DIRECT) {
+        p.path = Path::Direct;
+        if (v) return p;
+    }
+    if (plan_wino(p, c, 0)) return p;
+    if (bf16x_ok(g, 0, c.algo | c.io, c.tune) && !c.has_v && plan_bf16x(p, c, 0)) return p;
+    p.u_bytes = 0;
+    // only the Winograd and Bf16x paths (and, for the partial sums, the persistent image-facing kernel below) have operands to hand over
+    if (c.has_v || c.has_u) return fail(p);
+    const int kp_chunks = (c.algo == PG_ALGO_AUTO && tapk_enabled() && tapkp_enabled()) ? tapkp_stats_chunks(g) : 0;
+    if (c.part && !(kp_chunks > 0 && (q || (!v->bias && v->act == PG_ACT_NONE)))) return fail(p);
+    // (the queries report the row-GEMM path whatever the tensor storage, as they always have: engine._bf16_tensors_ok reads "no bf16
+    //  kernel" from it and keeps such a layer's tensors fp32; a launch on bf16 tensors goes on to the k_*_bf16 implicit GEMM)
+    if ((q || !c.io) && b2s_tapn_ok(g)) {
+        need(p, b2s_tapn_ws(g));
+        if (c.ws_bytes >= b2s_tapn_ws(g) && (q || ((v->ld_big % 4 == 0) && aligned16(v->big) && aligned16(v->P) && aligned16(v->ws) &&
+                                                   tensor_bytes((long)g.N * g.Hb * g.Wb, v->ld_big, g.Cb) < FAST_LIMIT))) {
+            // D[big pixel][(tap, a)] = big . P^T (row GEMM over the pixels), then gather the 16 taps per output pixel
+            return take_row_gemm(p, (long)g.N * g.Hb * g.Wb, 16 * g.Ca);
+        }
+    }
+    if (g.Cb <= 5 && !c.io && !force_generic() && tapk_enabled()) {     // (6..8 channels: measured slower than the generic kernel)
+        // K = 16*Cb <= 48: one-shot kernel (with 4 channels the pipelined generic kernel is as fast: 46 TFLOP/s both)
+        const long pix = (long)g.N * g.Hs * g.Ws;
+        p.vec4 = (g.Cb == 4) && (q || ((v->ld_big % 4 == 0) && aligned16(v->big)));
+        p.vec_out = (g.Ca % 4 == 0) && (q || ((v->ld_small % 4 == 0) && aligned16(v->small) && (!v->bias || aligned16(v->bias))));
+        const int tmk = g.Cb <= 4 ? 128 : 64;
+        p.workgroups = ((pix + tmk - 1) / tmk) * ((g.Ca + 63) / 64);      // (tiles: the persistent form walks them with fewer workgroups)
+        const bool persistent =
+            g.Cb <= 4 && tapkp_enabled() && p.vec_out && (g.Cb != 4 || p.vec4) && pix < 0x3fffffL * 64 &&
+            (q || ((v->act == PG_ACT_NONE || v->act == PG_ACT_LEAKY) && tensor_bytes((long)g.N * g.Hb * g.Wb, v->ld_big, g.Cb) < FAST_LIMIT &&
+                   tensor_bytes(pix, v->ld_small, g.Ca) < FAST_LIMIT));
+        if (c.part && !persistent) return fail(p);       // (a view the persistent kernel does not take: unaligned output, tensor beyond 32-bit offsets)
+        p.stats_chunks = persistent ? kp_chunks : 0;
+        return take(p, persistent ? Path::Tapkp : Path::Tapk);
+    }
+    if (v && c.io && !p.fast) return fail(p);               // bf16 tensors only on the fast bf16 kernels
+    p.tile = p.gemm.t;
+    p.split = p.gemm.split;
+    p.workgroups = gemm_workgroups(p.gemm);
+    return take(p, Path::Gemm);
+}
+
+ConvPlan plan_small2big(const pg_conv_geom* gg, const PlanCtx& c) {
+    ConvPlan p;
+    const Geom& g = c.g;
+    const Views* v = c.v;
+    const bool q = !v;
+    p.gemm = plan_s2b(gg);
+    if (p.gemm.split > 1) need(p, (size_t)p.gemm.split * p.gemm.out_elems * sizeof(float));
+    clamp_split(p.gemm, c.ws_bytes, 0);
+    const bool in_bf = c.io & PG_IO_SMALL_BF16, out_bf = c.io & PG_IO_BIG_BF16;
+    const long p_bytes = 16L * g.Ca * g.Cb * 4;
+    const long small_pix = (long)g.N * g.Hs * g.Ws, big_pix = (long)g.N * g.Hb * g.Wb;
+    p.veck = (g.Ca % 4 == 0) && (q || ((v->ld_small % 4 == 0) && aligned_io(v->small, in_bf)));
+    p.vecn = (g.Cb % 4 == 0) && (q || aligned16(v->P));
+    p.fast = p.veck && g.Ca >= KC && (q || tensor_bytes(small_pix, v->ld_small, g.Ca, in_bf) < FAST_LIMIT) && p_bytes < FAST_P_LIMIT &&
+             !force_generic();
+    if (c.algo == PG_ALGO_DIRECT) {
+        p.path = Path::Direct;
+        if (v) return c.mul ? fail(p) : p;
+    }
+    if (s2b_ca1_ok(g, c.algo | c.io) && !c.part && !c.has_u &&
+        (q || (aligned16(v->P) && (!v->bias || aligned16(v->bias)) && aligned_bf_view(v->big, v->ld_big, out_bf) &&
+               (!c.mul || aligned_bf_view(v->x->mul_t, v->x->mul_ld, out_bf))))) {
+        static const bool no_s1 = pg_exp_env("PATCHGAN_NO_CA1S1") != nullptr;
+        p.ca1_s1 = !no_s1 && g.s == 1 && (size_t)(g.Hs + 4) * (g.Ws + 4) * sizeof(float) <= 48 * 1024 && g.Hb == g.Hs + 1 && g.Wb == g.Ws + 1;
+        p.mul_ok = true;
+        p.workgroups = 2048;       // (nominal: the launch sizes ~1536 workgroups of whole pixel trips)
+        return take(p, Path::Ca1);
+    }
+    if (plan_wino(p, c, 1)) return p;
+    // the two row-GEMM + col2im paths are what the one-pass kernels (k_s2b_tapnf) fall back to on a view they do not take: sized first
+    const bool tapn = (q || !c.io) && s2b_tapn_ok(g) /* q: as in plan_big2small */, tapn_bf = bf16x_s2b_tapn_ok(g, c.algo | c.io, c.tune);
+    if (tapn) need(p, s2b_tapn_ws(g) + 256);
+    if (tapn_bf) need(p, bf16x_s2b_tapn_ws(g) + 256);
+    const bool no_extras = !c.part && !c.has_u && !c.mul;
+    // the one-pass kernel on a bf16 / an fp32 `small` (the latter below the bf16 row GEMMs in launch order)
+    auto tapnf_views = [&](bool bf) {
+        return q || ((v->ld_small % (bf ? 8 : 4) == 0) && aligned16(v->small) && tensor_bytes(small_pix, v->ld_small, g.Ca, bf) < FAST_LIMIT &&
+                     tensor_bytes(big_pix, v->ld_big, g.Cb) < FAST_LIMIT);
+    };
+    auto take_tapnf = [&](bool bf) -> ConvPlan& {
+        p.workgroups = std::min<long>(tapnf_blocks(g), tapnf_wgs(g, bf));
+        return take(p, bf ? Path::TapnfBf : Path::Tapnf);
+    };
+    if (s2b_tapnf_bf_ok(g, c.algo | c.io, c.tune) && no_extras && tapnf_views(true)) return take_tapnf(true);
+    if (tapn_bf && no_extras && c.ws_bytes >= bf16x_s2b_tapn_ws(g) &&
+        (q || (v->ws && aligned16(v->ws) && aligned_bf_view(v->small, v->ld_small, true) && aligned16(v->P) &&
+               tensor_bytes(small_pix, v->ld_small, g.Ca, true) < FAST_LIMIT))) {
+        // D[small pixel][(tap, b)] = small . W' (bf16 row GEMM), then col2im: each big pixel sums the taps that reach it
+        p.bx = pg_bf16x_plan_of(3, g.N, g.Hb, g.Wb, g.Hs, g.Ws, g.Ca, 16 * g.Cb, g.s, 0);
+        p.workgroups = (long)p.bx.tiles_m * p.bx.tiles_n;
+        return take(p, Path::Bf16xTapn);
+    }
+    if (bf16x_ok(g, 1, c.algo | c.io, c.tune) && plan_bf16x(p, c, 1)) return p;
+    p.u_bytes = 0;
+    p.mul_ok = false;
+    if (!no_extras) return fail(p);
+    if (!c.io && s2b_tapnf_ok(g) && tapnf_views(false)) return take_tapnf(false);
+    if (tapn && c.ws_bytes >= s2b_tapn_ws(g) &&
+        (q || ((v->ld_small % 4 == 0) && aligned16(v->small) && aligned16(v->P) && aligned16(v->ws) &&
+               tensor_bytes(small_pix, v->ld_small, g.Ca) < FAST_LIMIT))) {
+        // D[small pixel][(tap, b)] = small . W' (row GEMM), then col2im: each big pixel sums the taps that reach it
+        return take_row_gemm(p, small_pix, 16 * g.Cb);
+    }
+    if (v && c.io && !p.fast) return fail(p);
+    p.tile = p.gemm.t;
+    p.split = p.gemm.split;
+    p.workgroups = gemm_workgroups(p.gemm);
+    return take(p, Path::Gemm);
+}
+
+// c.has_v: v_pre is passed; Views::bias: dbias (the queries plan with the column sums reserved)
+ConvPlan plan_wgrad_conv(const pg_conv_geom* gg, const PlanCtx& c) {
+    ConvPlan p;
+    const Geom& g = c.g;
+    const Views* v = c.v;
+    const bool q = !v;
+    const size_t colsum = colsum_bytes(g.Ca);
+    p.reserved = (q || v->bias) ? colsum : 0;
+    p.gemm = plan_wgrad(gg);
+    p.mode = wgrad_mode(gg);
+    need(p, colsum + (p.gemm.split > 1 ? (size_t)p.gemm.split * p.gemm.out_elems * sizeof(float) : 0));
+    clamp_split(p.gemm, c.ws_bytes, p.reserved);
+    const long Kp = (long)g.N * g.Hs * g.Ws, big_pix = (long)g.N * g.Hb * g.Wb;
+    const bool in_bf = c.io != 0;
+    const bool al4 = q || ((v->ld_small % 4 == 0) && (v->ld_big % 4 == 0) && aligned16(v->small) && aligned16(v->big) && aligned16(v->ws));
+    if (c.algo == PG_ALGO_DIRECT) {
+        need(p, colsum + (size_t)DIRECT_WGRAD_SLICES * p.gemm.out_elems * sizeof(float));
+        p.path = Path::Direct;
+        if (v) return p;
+    }
+    // F(4x4,2x2) / F(4x4,3x3) of a stride-1 layer (w1), polyphase F(2x2,3x3) of a stride-2 layer
+    const bool w1 = c.algo == PG_ALGO_AUTO && wino_wgrad_ok(g, c.tune), w2 = c.algo == PG_ALGO_AUTO && wino2_wgrad_ok(g, c.tune);
+    if (w1 || w2) {
+        const size_t wsb = w1 ? pg_wino_wgrad_ws_bytes(g.N, g.Hs, g.Ws, g.Ca, g.Cb) : pg_wino2_wgrad_ws_bytes(g.N, g.Hs, g.Ws, g.Ca, g.Cb);
+        need(p, colsum + wsb);
+        if (al4 && (w1 || q || aligned16(v->P)) && c.ws_bytes >= p.reserved + wsb) {
+            if (w1 && c.has_v && !pg_wino_wgrad_v_bytes(g.N, g.Hs, g.Ws, g.Ca, g.Cb, c.tune.mo1)) return fail(p);
+            p.small_tile = w1 ? pg_wino_wgrad_tile64(g.Ca, g.Cb, c.tune.s3w) : pg_wino2_wgrad_tile64(g.Ca, g.Cb, c.tune.s3w);
+            p.split = w1 ? pg_wino_wgrad_slices(g.N, g.Hs, g.Ws, g.Ca, g.Cb, c.tune.s3w) : pg_wino2_wgrad_slices(g.N, g.Hs, g.Ws, g.Ca, g.Cb, c.tune.s3w);
+            const int tt = p.small_tile ? 64 : 128;
+            p.workgroups = (w1 ? 25L * ((g.Ca + tt - 1) / tt) * ((g.Cb + tt - 1) / tt) : 16L * ((g.Ca + 127) / 128) * ((4 * g.Cb + 127) / 128)) * p.split;
+            return take(p, w1 ? Path::WinoWgrad : Path::Wino2Wgrad);
+        }
+    }
+    if (c.has_v) return fail(p);     // pg_conv_v_bytes said 0 for this call: there is no transformed operand to reuse
+    if (bf16x_wgrad_ok(g, c.algo | c.io, c.tune)) {
+        p.bx = pg_bf16x_wgrad_plan(g.N, g.Hb, g.Wb, g.Hs, g.Ws, g.Ca, g.Cb, g.s);
+        need(p, colsum + (p.bx.split > 1 ? (size_t)p.bx.split * p.bx.out_elems * sizeof(float) : 0));
+        if (q || ((g.Cb > 8 || v->ld_big == 8) && aligned_bf_view(v->small, v->ld_small, true) && aligned_bf_view(v->big, v->ld_big, true) &&
+                  aligned16(v->P) && (c.ws_bytes <= p.reserved || aligned16(v->ws)) && tensor_bytes(Kp, v->ld_small, g.Ca, true) < FAST_LIMIT &&
+                  tensor_bytes(big_pix, v->ld_big, g.Cb > 8 ? g.Cb : 8, true) < FAST_LIMIT)) {
+            // (the queries describe this kernel without a bias gradient: the bf16 networks' convolutions that reach it have no bias)
+            const size_t res = q ? 0 : p.reserved;
+            pg_bf16x_clamp(&p.bx, c.ws_bytes > res ? c.ws_bytes - res : 0);
+            p.split = p.bx.split;
+            p.workgroups = (long)p.bx.tiles_m * p.bx.tiles_n * 16 * p.bx.split;
+            return take(p, Path::Bf16xWgrad);
+        }
+    }
+    if (v && c.io && p.mode != 0) return fail(p);
+    p.tile = p.gemm.t;
+    p.split = p.gemm.split;
+    p.workgroups = gemm_workgroups(p.gemm);
+    p.veck = (g.Ca % 4 == 0) && (q || ((v->ld_small % 4 == 0) && aligned_io(v->small, in_bf)));
+    p.vecn = (g.Cb % 4 == 0) && (q || ((v->ld_big % 4 == 0) && aligned_io(v->big, in_bf)));
+    if (p.mode == 0) {
+        p.pow2 = ((g.Hs & (g.Hs - 1)) == 0) && ((g.Ws & (g.Ws - 1)) == 0);
+        p.fast = p.veck && p.vecn && !force_generic() && (p.pow2 || (g.Ws >= 16 && g.Hs >= 2)) &&
+                 (q || (tensor_bytes(Kp, v->ld_small, g.Ca, in_bf) < FAST_LIMIT && tensor_bytes(big_pix, v->ld_big, g.Cb, in_bf) < FAST_LIMIT));
+        if (v && c.io && !p.fast) return fail(p);
+        return take(p, Path::Gemm);
+    }
+    if (p.mode == 1 && !c.io && wgrad_tapnp_ok(g)) {
+        // persistent form: one slab per workgroup column, reduced in workgroup order
+        const int G = wgrad_tapnp_slabs(g);
+        // (not sized for: it runs where the workspace that the layer's other paths asked for happens to hold its slabs)
+        const size_t wsb = (size_t)G * p.gemm.out_elems * sizeof(float);
+        if (p.veck && c.ws_bytes >= p.reserved + wsb &&
+            (q || (aligned16(v->ws) && (g.Cb != 4 || ((v->ld_big % 4 == 0) && aligned16(v->big))) &&
+                   tensor_bytes(Kp, v->ld_small, g.Ca) < FAST_LIMIT && tensor_bytes(big_pix, v->ld_big, g.Cb) < FAST_LIMIT))) {
+            p.split = G;
+            return take(p, Path::WgradTapnp);
+        }
+    }
+    return take(p, Path::WgradTapn);
+}
+
+ConvPlan plan_conv(const pg_conv_geom* gg, int op, int algo_full, const Tune& tune, size_t ws_bytes, const Views* v, int offer = 0) {
+    const Geom g = to_geom(gg);
+    const pg_conv_extras* x = v ? v->x : &NO_EXTRAS;
+    const PlanCtx c{g, algo_full & PG_ALGO_MASK, algo_full & PG_IO_MASK, tune, ws_bytes, v,
+                    v ? x->part != nullptr : (offer & OFFER_PART) != 0, v ? x->u_cache != nullptr : (offer & OFFER_U) != 0,
+                    v ? (x->v_keep || x->v_pre) : (offer & OFFER_V) != 0, v ? x->mul_t != nullptr : (offer & OFFER_MUL) != 0};
+    return op == 0 ? plan_big2small(gg, c) : op == 1 ? plan_small2big(gg, c) : plan_wgrad_conv(gg, c);
+}
+
+// pg_conv4x4_bwd_big: V(big) computed once for the polyphase weight gradient and data gradient of a stride-2 layer
+bool plan_share_v(const Geom& g, int algo_full, const Tune& tune, size_t ws_bytes, bool views_ok, size_t* needed) {
+    if (!(wino2_b2s_ok(g, tune) && wino2_wgrad_ok(g, tune))) return false;
+    const size_t wsb = pg_wino2_v_bytes(g.N, g.Hs, g.Ws, g.Cb) +
+                       std::max(pg_wino2_ws_bytes(g.N, g.Hs, g.Ws, g.Ca, g.Cb), pg_wino2_wgrad_ws_bytes(g.N, g.Hs, g.Ws, g.Ca, g.Cb));
+    if (needed) *needed = wsb;
+    return (algo_full & PG_ALGO_MASK) == PG_ALGO_AUTO && pg_wino2_mo() == 3 && views_ok && ws_bytes >= wsb;
+}
+
+// ---- what the queries report of a plan ----
+// pg_conv_describe's documented numbers
+void describe_plan(const ConvPlan& p, const Geom& g, int op, int* tile_id, int* split, long* workgroups) {
+    const int gemm_code = p.gemm.t.id + (op == 2 ? 10 * p.mode : 0) + (p.fast ? (p.pow2 ? 200 : 100) : 0);
+    // beside the Wino1 codes, and for the persistent form of k_wgrad_tapn, the tile / split / workgroups are those of the implicit-GEMM plan
+    const bool of_gemm = p.mfma == Path::Wino1 || p.mfma == Path::WgradTapnp;
+    int code = gemm_code;
+    switch (p.mfma) {
+        case Path::Bf16xWgrad: code = 1020 + p.bx.tile; break;
+        case Path::Ca1: code = 1050; break;
+        case Path::TapnfBf: code = 1070 + g.Cb; break;
+        case Path::Tapnf: code = 1060 + g.Cb; break;
+        case Path::Bf16xTapn: code = 1030 + p.bx.tile; break;
+        case Path::Bf16x: code = p.xdir == 2 ? 1040 + p.bx.tile : 1000 + 100 * (p.bx.win ? 2 : p.bx.ring) + 10 * op + p.bx.tile; break;
+        case Path::TapnRowGemm: code = p.tile.id + 30; break;
+        case Path::Wino1: code = gemm_code + (p.mo == 3 ? 90 : p.small_tile ? 50 : 40); break;
+        case Path::Tapk:
+        case Path::Tapkp: code = 80 + g.Cb; break;
+        case Path::Wino2: code = (p.small_tile ? 71 : 70) + (p.mz ? 2 : 0); break;
+        case Path::Wino2Wgrad: code = p.small_tile ? 62 : 61; break;
+        case Path::WinoWgrad: code = p.small_tile ? 63 : 60; break;
+        default: break;
+    }
+    if (tile_id) *tile_id = code;
+    if (split) *split = of_gemm ? p.gemm.split : p.split;
+    if (workgroups) *workgroups = of_gemm ? gemm_workgroups(p.gemm) : p.workgroups;
+}
+
+// FLOPs of the main kernel: executed (ragged tiles padded to whole ones) / useful (the algorithm's count on the exact extents)
+void flops_of(const ConvPlan& p, const Geom& g, int op, double* executed, double* useful) {
+    // the Winograd kernels' counts, given how many tiles cover an extent (tiles(extent, tile edge)); halo: the polyphase data gradient's
+    // extra window per class, counted with the whole tiles only
+    auto count = [&](auto tiles, int halo) -> double {
+        const int m2 = pg_wino2_mo(), m1 = p.mo == 3 ? 3 : 2, wr = pg_wino_wgrad_r(g.N, g.Hs, g.Ws);
+        const int ho = op == 0 ? g.Hs : g.Hb, wo = op == 0 ? g.Ws : g.Wb;
+        switch (p.path) {
+            case Path::WinoWgrad: return 2.0 * (wr + 3) * (wr + 3) * g.N * tiles(g.Hs, wr) * tiles(g.Ws, wr) * g.Ca * g.Cb;
+            case Path::Wino2Wgrad: return 2.0 * 16 * g.N * tiles(g.Hs, 3) * tiles(g.Ws, 3) * g.Ca * 4.0 * g.Cb;
+            case Path::Wino2:
+                return op == 0 ? 2.0 * (m2 + 1) * (m2 + 1) * g.N * tiles(g.Hs, m2) * tiles(g.Ws, m2) * 4.0 * g.Cb * g.Ca
+                               : 2.0 * 4 * (m2 + 1) * (m2 + 1) * g.N * tiles(tiles(g.Hb, 2) + halo, m2) * tiles(tiles(g.Wb, 2) + halo, m2) * (double)g.Ca * g.Cb;
+            case Path::Wino1: return 2.0 * (m1 + 3) * (m1 + 3) * g.N * tiles(ho, m1) * tiles(wo, m1) * (double)g.Ca * g.Cb;
+            default: return 2.0 * g.N * g.Hs * g.Ws * 16.0 * g.Ca * g.Cb;
+        }
+    };
+    if (executed)
+        *executed = p.path == Path::WinoWgrad ? pg_wino_wgrad_flops(g.N, g.Hs, g.Ws, g.Ca, g.Cb) : count([](long a, long b) { return (a + b - 1) / b; }, 1);
+    if (useful) *useful = count([](double a, double b) { return a / b; }, 0);
+}
+
+// the kernel symbol of the main kernel (profiling only: the one place that formats text)
+void name_of(const ConvPlan& p, const Geom& g, int op, int algo_full, const Tune& tune, char* buf, size_t len) {
+    static const char* const TILE[5] = {"2,2,2,2", "2,1,2,2", "1,1,4,1", "1,2,2,2", "1,1,2,2"};
+    const char* tl = TILE[p.tile.id];
+    const bool bf = p.path == Path::TapnfBf;
+    switch (p.path) {
+        case Path::Direct: snprintf(buf, len, "%s", op == 0 ? "k_big2small_direct" : op == 1 ? "k_small2big_direct" : "k_wgrad_direct"); break;
+        case Path::Tapnf:
+        case Path::TapnfBf:       // one-pass taps-in-N ConvTranspose2d onto <= 4 channels; 5 .. 8 channels: two launches
+            if (g.Cb <= 4) snprintf(buf, len, "k_s2b_tapnf<%d%s>", g.Cb, bf ? ",bf16" : "");
+            else snprintf(buf, len, "k_s2b_tapnf<4%s>+k_s2b_tapnf<%d%s>", bf ? ",bf16" : "", g.Cb - 4, bf ? ",bf16" : "");
+            break;
+        case Path::Ca1: snprintf(buf, len, p.ca1_s1 ? "k_s2b_ca1_s1" : "k_s2b_ca1"); break;
+        case Path::Bf16xWgrad: snprintf(buf, len, "%s", pg_bf16x_wgrad_kernel_name(p.bx.tile)); break;
+        case Path::Bf16xTapn: snprintf(buf, len, "%s+k_col2im_small2big", pg_bf16x_kernel_name(3, p.bx.tile, 0)); break;
+        case Path::Bf16x:
+            snprintf(buf, len, "%s", p.xdir == 2 ? pg_bf16x_kernel_name(2, p.bx.tile, 0) : pg_bf16x_kernel_name(op, p.bx.tile, p.bx.win ? 2 : p.bx.ring));
+            break;
+        case Path::WinoWgrad:
+        case Path::Wino2Wgrad:
+            if (tune.s3w) snprintf(buf, len, "k_wino_wgrad_gemm_s3<%s>", p.small_tile ? "1,1,2,2,2,3" : "2,2,2,2,1,2");
+            else snprintf(buf, len, "k_wino_wgrad_gemm<%s>", p.small_tile ? "1,1,2,2" : "2,2,2,2");
+            break;
+        case Path::Tapkp:
+        case Path::Tapk: snprintf(buf, len, p.path == Path::Tapkp ? "k_b2s_tapkp<%d>" : "k_b2s_tapk<%d>", g.Cb); break;
+        case Path::Wino2:
+            if (tune.s3)       // split-bf16 form (the default): 128-row tiles at two waves per SIMD, 64-row tiles at three
+                snprintf(buf, len, "k_wino_bgemm_s3<%s>", p.small_tile ? "1,2,2,2,3" : "2,2,2,2,2");
+            else
+                snprintf(buf, len, "k_wino_bgemm%s<%s>", p.mz ? "_mz" : "", p.small_tile ? "1,2,2,2" : "2,2,2,2");
+            break;
+        case Path::Wino1:
+            if (p.mo == 3 && tune.dma) snprintf(buf, len, "k_wino_gemm_dma<3,4,2>");
+            else if (p.mo != 3 && p.small_tile && tune.dma == 2) snprintf(buf, len, "k_wino_gemm_dma<2,3,3>");
+            else if (p.mo == 3 && pg_wino_row_on())
+                snprintf(buf, len, (tune.s3r && (op == 0 ? g.Cb : g.Ca) % 32 == 0) ? "k_wino_gemm_row_s3<2>" : "k_wino_gemm_row<4,1>");
+            else snprintf(buf, len, "k_wino_gemm<%s>", p.mo == 3 ? "1,1,2,2,2,3" : p.small_tile ? "1,1,2,2,4,2" : "2,1,2,2,2,2");
+            break;
+        case Path::TapnRowGemm: snprintf(buf, len, "k_b2s_fast<%s,true>+%s", tl, op == 0 ? "k_gather_big2small" : "k_col2im_small2big"); break;
+        case Path::WgradTapnp: snprintf(buf, len, "k_wgrad_tapnp<%d>", g.Cb); break;
+        case Path::WgradTapn: snprintf(buf, len, "k_wgrad_tapn<%s,%d>", tl, p.mode); break;
+        case Path::Gemm: {
+            const bool half = (algo_full & PG_ALGO_MASK) == PG_ALGO_BF16 && p.fast;
+            // bf16 kernels: the trailing template argument says whether the activation operand(s) are stored as bf16 (PG_IO_* bits)
+            const int io = algo_full & PG_IO_MASK;
+            const char* hin = (op == 0 ? (io & PG_IO_BIG_BF16) : op == 1 ? (io & PG_IO_SMALL_BF16) : io == PG_IO_MASK) ? "true" : "false";
+            const char* p2 = p.pow2 ? "true" : "false";
+            if (half && op == 0) snprintf(buf, len, "k_b2s_bf16<%s,false,%s>", tl, hin);
+            else if (half && op == 1) snprintf(buf, len, "k_s2b_bf16<%s,%s>", tl, hin);
+            else if (half) snprintf(buf, len, "k_wgrad_bf16<%s,%s,%s>", tl, p2, hin);
+            else if (p.fast && op == 0) snprintf(buf, len, "k_b2s_fast<%s,false>", tl);
+            else if (p.fast && op == 1) snprintf(buf, len, "k_s2b_fast<%s>", tl);
+            else if (p.fast) snprintf(buf, len, "k_wgrad_fast<%s,%s>", tl, p2);
+            else snprintf(buf, len, "%s<%s>", op == 0 ? "k_big2small" : op == 1 ? "k_small2big" : "k_wgrad", tl);
+        } break;
+    }
+}
+
+// a query's plan: `op` carries the algorithm as opcode + 16 * (PG_ALGO_* | PG_IO_* | PG_TUNE_*)
+bool query_plan(const pg_conv_geom* g, int op, int algo_full, size_t ws_bytes, int offer, ConvPlan* p) {
+    const int algo = algo_full & PG_ALGO_MASK;
+    if (!geom_ok(g) || op < 0 || op > 2 || algo < PG_ALGO_AUTO || algo > PG_ALGO_BF16) return false;
+    *p = plan_conv(g, op, algo_full, tune_of(algo_full), ws_bytes, nullptr, offer);
+    return true;
 }
 
 }  // namespace
@@ -3614,46 +4025,20 @@ extern "C" {
 size_t pg_conv_max_tensor_bytes(void) { return (size_t)FAST_LIMIT; }
 
 size_t pg_conv_workspace_bytes(const pg_conv_geom* g, int op) {
-    if (!geom_ok(g)) return 0;
-    if (op == 3) {      // pg_conv4x4_bwd_big: its two halves back to back, or V shared + the larger of the two remainders
-        size_t bytes = std::max(pg_conv_workspace_bytes(g, 0), pg_conv_workspace_bytes(g, 2));
-        const Geom gq = to_geom(g);
-        const Tune tw = tune_widest(0);
-        if (wino2_b2s_ok(gq, tw) && wino2_wgrad_ok(gq, tw))
-            bytes = std::max(bytes, pg_wino2_v_bytes(gq.N, gq.Hs, gq.Ws, gq.Cb) +
-                                        std::max(pg_wino2_ws_bytes(gq.N, gq.Hs, gq.Ws, gq.Ca, gq.Cb),
-                                                 pg_wino2_wgrad_ws_bytes(gq.N, gq.Hs, gq.Ws, gq.Ca, gq.Cb)));
-        return (bytes + 255) & ~(size_t)255;
-    }
-    Plan p = (op == 0) ? plan_b2s(g) : (op == 1) ? plan_s2b(g) : plan_wgrad(g);
+    if (!geom_ok(g) || op < 0 || op > 3) return 0;
     size_t bytes = 0;
-    int split = p.split;
-    if (op == 2 && split < DIRECT_WGRAD_SLICES) split = DIRECT_WGRAD_SLICES;   // the direct algo's slices
-    if (split > 1) bytes = (size_t)split * p.out_elems * sizeof(float);
-    if (op == 2) bytes += ((size_t)COLSUM_CHUNKS * g->Ca * sizeof(float) + 255) & ~(size_t)255;
-    const Geom gq = to_geom(g);
-    if (op == 0 && b2s_tapn_ok(gq)) bytes = std::max(bytes, b2s_tapn_ws(gq));
-    if (op == 1 && s2b_tapn_ok(gq)) bytes = std::max(bytes, s2b_tapn_ws(gq) + 256);
-    // enough for whichever Winograd path a PG_TUNE_* combination selects
-    for (int mo1 = 2; mo1 <= 3; ++mo1) {
-        const Tune t = tune_widest(mo1);
-        if (op == 0 && wino_b2s_ok(gq, t)) bytes = std::max(bytes, pg_wino_ws_bytes(gq.N, gq.Hs, gq.Ws, gq.Cb, gq.Ca, mo1));
-        if (op == 1 && wino_s2b_ok(gq, t)) bytes = std::max(bytes, pg_wino_ws_bytes(gq.N, gq.Hb, gq.Wb, gq.Ca, gq.Cb, mo1));
+    if (op == 3) {      // pg_conv4x4_bwd_big: its two halves back to back, or V shared + the larger of the two remainders
+        bytes = std::max(pg_conv_workspace_bytes(g, 0), pg_conv_workspace_bytes(g, 2));
+        size_t shared = 0;
+        plan_share_v(to_geom(g), PG_ALGO_AUTO, tune_widest(0), 0, true, &shared);
+        return (std::max(bytes, shared) + 255) & ~(size_t)255;
     }
-    if ((op == 0 || op == 1) && pg_bf16x_geom_ok((op == 0 && gq.Cb <= 8) ? 2 : op, gq.N, gq.Hb, gq.Wb, gq.Hs, gq.Ws, gq.Ca, gq.Cb, gq.s))
-        bytes = std::max(bytes, bf16x_ws(gq, op));
-    if (op == 1 && gq.Cb <= 8 && pg_bf16x_geom_ok(3, gq.N, gq.Hb, gq.Wb, gq.Hs, gq.Ws, gq.Ca, 16 * gq.Cb, gq.s)) bytes = std::max(bytes, bf16x_s2b_tapn_ws(gq) + 256);
-    if (op == 2 && pg_bf16x_wgrad_geom_ok(gq.N, gq.Hb, gq.Wb, gq.Hs, gq.Ws, gq.Ca, gq.Cb, gq.s)) {
-        const pg_bf16x_plan wp = pg_bf16x_wgrad_plan(gq.N, gq.Hb, gq.Wb, gq.Hs, gq.Ws, gq.Ca, gq.Cb, gq.s);
-        if (wp.split > 1)
-            bytes = std::max(bytes, (size_t)wp.split * wp.out_elems * sizeof(float) + (((size_t)COLSUM_CHUNKS * g->Ca * sizeof(float) + 255) & ~(size_t)255));
-    }
-    const Tune tw = tune_widest(0);
-    const size_t colsum = ((size_t)COLSUM_CHUNKS * g->Ca * sizeof(float) + 255) & ~(size_t)255;
-    if (op == 0 && wino2_b2s_ok(gq, tw)) bytes = std::max(bytes, pg_wino2_ws_bytes(gq.N, gq.Hs, gq.Ws, gq.Ca, gq.Cb));
-    if (op == 1 && wino2_s2b_ok(gq, tw)) bytes = std::max(bytes, pg_wino2c_ws_bytes(gq.N, gq.Hb, gq.Wb, gq.Ca, gq.Cb));
-    if (op == 2 && wino_wgrad_ok(gq, tw)) bytes = std::max(bytes, pg_wino_wgrad_ws_bytes(gq.N, gq.Hs, gq.Ws, gq.Ca, gq.Cb) + colsum);
-    if (op == 2 && wino2_wgrad_ok(gq, tw)) bytes = std::max(bytes, pg_wino2_wgrad_ws_bytes(gq.N, gq.Hs, gq.Ws, gq.Ca, gq.Cb) + colsum);
+    // what the planner asks for at most, whichever algo, tensor storage and PG_TUNE_* combination the call comes with (every path on;
+    // both tile edges of the stride-1 Winograd paths); PG_ALGO_AUTO covers PG_ALGO_MFMA
+    static const int ALGOS[] = {PG_ALGO_AUTO, PG_ALGO_DIRECT, PG_ALGO_BF16 | PG_IO_BIG_BF16, PG_ALGO_BF16 | PG_IO_SMALL_BF16,
+                                PG_ALGO_BF16 | PG_IO_MASK};
+    for (int mo1 = 2; mo1 <= 3; ++mo1)
+        for (int a : ALGOS) bytes = std::max(bytes, plan_conv(g, op, a, tune_widest(mo1), 0, nullptr).ws_needed);
     return (bytes + 255) & ~(size_t)255;
 }
 
@@ -3673,670 +4058,53 @@ int pg_conv_time_next2(void* ev_start, void* ev_stop, void* ev_start2, void* ev_
 }
 
 int pg_conv_describe(const pg_conv_geom* g, int op, size_t ws_bytes, int* tile_id, int* split, long* workgroups) {
-    const int algo_full = op >> 4;      // op = opcode + 16 * (PG_ALGO_* | PG_TUNE_*): the Winograd codes are reported for PG_ALGO_AUTO only
-    const int algo = algo_full & PG_ALGO_MASK;
-    const Tune tune = tune_of(algo_full);
-    op &= 15;
-    if (!geom_ok(g) || op < 0 || op > 2 || algo < PG_ALGO_AUTO || algo > PG_ALGO_BF16) return PG_EINVAL;
-    Plan p = (op == 0) ? plan_b2s(g) : (op == 1) ? plan_s2b(g) : plan_wgrad(g);
-    // +100: the fast (buffer-load) variant would run for 16-byte-aligned contiguous tensors; +200: its power-of-two
-    // pixel-decode instantiation (wgrad only)
-    int fastcode = 0;
-    if (!force_generic()) {
-        const bool p2 = ((g->Hs & (g->Hs - 1)) == 0) && ((g->Ws & (g->Ws - 1)) == 0);
-        if (op == 0 && g->Cb % 4 == 0 && g->Cb >= KC) fastcode = 100;
-        if (op == 1 && g->Ca % 4 == 0 && g->Ca >= KC) fastcode = 100;
-        if (op == 2 && wgrad_mode(g) == 0 && g->Ca % 4 == 0 && g->Cb % 4 == 0 && (p2 || (g->Ws >= 16 && g->Hs >= 2)))
-            fastcode = p2 ? 200 : 100;
-    }
-    size_t reserved = (op == 2) ? (((size_t)COLSUM_CHUNKS * g->Ca * sizeof(float) + 255) & ~(size_t)255) : 0;
-    clamp_split(p, ws_bytes, reserved);
-    if (tile_id) *tile_id = p.t.id + ((op == 2) ? 10 * wgrad_mode(g) : 0) + fastcode;
-    const Geom gq = to_geom(g);
-    // 1020 + tile: the LDS-DMA bf16 weight-gradient kernel (k_wgrad_bf16x), both operands bf16 tensors
-    if (op == 2 && bf16x_wgrad_ok(gq, algo_full, tune)) {
-        pg_bf16x_plan wp = pg_bf16x_wgrad_plan(gq.N, gq.Hb, gq.Wb, gq.Hs, gq.Ws, gq.Ca, gq.Cb, gq.s);
-        pg_bf16x_clamp(&wp, ws_bytes);
-        if (tile_id) *tile_id = 1020 + wp.tile;
-        if (split) *split = wp.split;
-        if (workgroups) *workgroups = (long)wp.tiles_m * wp.tiles_n * 16 * wp.split;
-        return PG_OK;
-    }
-    // 1000 + 10 * dir + tile: the LDS-DMA bf16 kernels (k_conv_bf16x) on bf16 tensors
-    if (op == 1 && s2b_ca1_ok(gq, algo_full)) {      // 1050: k_s2b_ca1
-        if (tile_id) *tile_id = 1050;
-        if (split) *split = 1;
-        if (workgroups) *workgroups = 2048;
-        return PG_OK;
-    }
-    if (op == 1 && s2b_tapnf_bf_ok(gq, algo_full, tune)) {      // 1070 + Cb: k_s2b_tapnf<Cb, bf16>
-        if (tile_id) *tile_id = 1070 + gq.Cb;
-        if (split) *split = 1;
-        const long nb = (long)gq.N * ((gq.Hb + 2 * TF_H - 2) / (2 * TF_H - 2)) * ((gq.Wb + 2 * TF_W - 2) / (2 * TF_W - 2));
-        if (workgroups) *workgroups = std::min<long>(nb, 768);
-        return PG_OK;
-    }
-    if (op == 1 && bf16x_s2b_tapn_ok(gq, algo_full, tune) && ws_bytes >= bf16x_s2b_tapn_ws(gq)) {
-        const pg_bf16x_plan bp = pg_bf16x_plan_of(3, gq.N, gq.Hb, gq.Wb, gq.Hs, gq.Ws, gq.Ca, 16 * gq.Cb, gq.s, 0);
-        if (tile_id) *tile_id = 1030 + bp.tile;
-        if (split) *split = 1;
-        if (workgroups) *workgroups = (long)bp.tiles_m * bp.tiles_n;
-        return PG_OK;
-    }
-    if ((op == 0 || op == 1) && bf16x_ok(gq, op, algo_full, tune) && ws_bytes >= pg_bf16x_w_bytes(g->Ca, g->Cb)) {
-        const int xdir = (op == 0 && gq.Cb <= 8) ? 2 : op;
-        pg_bf16x_plan bp = pg_bf16x_plan_of(xdir, gq.N, gq.Hb, gq.Wb, gq.Hs, gq.Ws, gq.Ca, gq.Cb, gq.s, tune.bf16ring);
-        pg_bf16x_clamp(&bp, ws_bytes - pg_bf16x_w_bytes(g->Ca, g->Cb));
-        if (tile_id) *tile_id = (xdir == 2) ? 1040 + bp.tile : 1000 + 100 * (bp.win ? 2 : bp.ring) + 10 * op + bp.tile;   // (1200 + ..: k_conv_bf16r)
-        if (split) *split = bp.split;
-        if (workgroups) *workgroups = (long)bp.tiles_m * bp.tiles_n * bp.ncls * bp.split;
-        return PG_OK;
-    }
-    if (op == 1 && !(algo_full & PG_IO_MASK) && s2b_tapnf_ok(gq)) {      // 1060 + Cb: k_s2b_tapnf<Cb>
-        if (tile_id) *tile_id = 1060 + gq.Cb;
-        if (split) *split = 1;
-        const long nb = (long)gq.N * ((gq.Hb + 2 * TF_H - 2) / (2 * TF_H - 2)) * ((gq.Wb + 2 * TF_W - 2) / (2 * TF_W - 2));
-        if (workgroups) *workgroups = std::min<long>(nb, (gq.Ca == 128) ? 512 : 768);
-        return PG_OK;
-    }
-    if ((op == 0 && b2s_tapn_ok(gq) && ws_bytes >= b2s_tapn_ws(gq)) || (op == 1 && s2b_tapn_ok(gq) && ws_bytes >= s2b_tapn_ws(gq))) {
-        const long M1 = (op == 0) ? (long)g->N * g->Hb * g->Wb : (long)g->N * g->Hs * g->Ws;
-        const int Nc = 16 * ((op == 0) ? g->Ca : g->Cb);
-        Tile t = pick_tile(M1, Nc);
-        if (tile_id) *tile_id = t.id + 30;
-        if (split) *split = 1;
-        if (workgroups) *workgroups = ((M1 + t.bm - 1) / t.bm) * ((Nc + t.bn - 1) / t.bn);
-        return PG_OK;
-    }
-    // +40 / +50: under PG_ALGO_AUTO this stride-1 layer runs Winograd F(2x2, 4x4) (k_wino_gemm<2,1,2,2,2> / <1,1,2,2,4>, no
-    // split-K); the tile / split
-    // reported are those of the implicit-GEMM kernel the other algos use
-    if (algo == PG_ALGO_AUTO &&
-        ((op == 0 && wino_b2s_ok(gq, tune) && ws_bytes >= pg_wino_ws_bytes(gq.N, gq.Hs, gq.Ws, gq.Cb, gq.Ca, tune.mo1)) ||
-         (op == 1 && wino_s2b_ok(gq, tune) && ws_bytes >= pg_wino_ws_bytes(gq.N, gq.Hb, gq.Wb, gq.Ca, gq.Cb, tune.mo1)))) {
-        const bool st = (op == 0) ? pg_wino_small_tile(gq.N, gq.Hs, gq.Ws, gq.Cb, gq.Ca, tune.mo1) : pg_wino_small_tile(gq.N, gq.Hb, gq.Wb, gq.Ca, gq.Cb, tune.mo1);
-        const int mo1 = (op == 0) ? pg_wino_mo(gq.N, gq.Hs, gq.Ws, gq.Cb, gq.Ca, tune.mo1) : pg_wino_mo(gq.N, gq.Hb, gq.Wb, gq.Ca, gq.Cb, tune.mo1);
-        if (tile_id) *tile_id += (mo1 == 3) ? 90 : (st ? 50 : 40);     // +90: F(3x3,4x4) variant k_wino_gemm<1,1,2,2,2,3>
-    }
-    // 81..83: one-shot k_b2s_tapk<Cb> for 1..3 big-side channels
-    if (op == 0 && g->Cb <= 5 && !(algo_full & PG_IO_MASK) && !force_generic() && tapk_enabled() &&
-        !(b2s_tapn_ok(gq) && ws_bytes >= b2s_tapn_ws(gq))) {
-        if (tile_id) *tile_id = 80 + g->Cb;
-        if (split) *split = 1;
-        const int tmk = g->Cb <= 4 ? 128 : 64;
-        if (workgroups) *workgroups = (((long)g->N * g->Hs * g->Ws + tmk - 1) / tmk) * ((g->Ca + 63) / 64);
-        return PG_OK;
-    }
-    // 70 / 71: polyphase Winograd of a stride-2 layer (k_wino_bgemm_s3<2,2,2,2,2> / <1,2,2,2,3>; under PG_TUNE_S3_OFF k_wino_bgemm<2,2,2,2> /
-    // <1,2,2,2>, 72 / 73: k_wino_bgemm_mz)
-    if (algo == PG_ALGO_AUTO && op == 0 && wino2_b2s_ok(gq, tune) && ws_bytes >= pg_wino2_ws_bytes(gq.N, gq.Hs, gq.Ws, gq.Ca, gq.Cb)) {
-        const long T = pg_wino2_tiles_b2s(g->N, g->Hs, g->Ws), X = (long)(pg_wino2_mo() + 1) * (pg_wino2_mo() + 1);
-        if (tile_id) *tile_id = (T >= 1024 ? 70 : 71) + ((!tune.s3 && pg_wino2_b2s_zb(g->N, g->Hs, g->Ws, g->Ca) > 1) ? 2 : 0);
-        if (split) *split = 1;
-        if (workgroups) *workgroups = X * ((T + (T >= 1024 ? 127 : 63)) / (T >= 1024 ? 128 : 64)) * ((g->Ca + 127) / 128);
-        return PG_OK;
-    }
-    if (algo == PG_ALGO_AUTO && op == 1 && wino2_s2b_ok(gq, tune) && ws_bytes >= pg_wino2c_ws_bytes(gq.N, gq.Hb, gq.Wb, gq.Ca, gq.Cb)) {
-        const long T = pg_wino2_tiles_s2b(g->N, g->Hb, g->Wb), X = (long)(pg_wino2_mo() + 1) * (pg_wino2_mo() + 1);
-        if (tile_id) *tile_id = (T >= 1024 ? 70 : 71) + ((!tune.s3 && pg_wino2_s2b_zb(g->N, g->Hb, g->Wb, g->Cb) > 1) ? 2 : 0);
-        if (split) *split = 1;
-        if (workgroups) *workgroups = X * ((T + (T >= 1024 ? 127 : 63)) / (T >= 1024 ? 128 : 64)) * ((4 * g->Cb + 127) / 128);
-        return PG_OK;
-    }
-    // 61 / 62: polyphase F(2x2, 3x3) weight gradient of a stride-2 layer (k_wino_wgrad_gemm<2,2,2,2> / <1,1,2,2>)
-    if (algo == PG_ALGO_AUTO && op == 2 && wino2_wgrad_ok(gq, tune) &&
-        ws_bytes >= reserved + pg_wino2_wgrad_ws_bytes(gq.N, gq.Hs, gq.Ws, gq.Ca, gq.Cb)) {
-        const int sl = pg_wino2_wgrad_slices(gq.N, gq.Hs, gq.Ws, gq.Ca, gq.Cb, tune.s3w);
-        if (tile_id) *tile_id = pg_wino2_wgrad_tile64(gq.Ca, gq.Cb, tune.s3w) ? 62 : 61;
-        if (split) *split = sl;
-        if (workgroups) *workgroups = 16L * ((g->Ca + 127) / 128) * ((4 * g->Cb + 127) / 128) * sl;
-        return PG_OK;
-    }
-    // 60 / 63: Winograd F(4x4, 2x2) weight gradient (k_wino_wgrad_gemm<2,2,2,2> / <1,1,2,2>); split = its K slices
-    if (algo == PG_ALGO_AUTO && op == 2 && wino_wgrad_ok(gq, tune) && ws_bytes >= reserved + pg_wino_wgrad_ws_bytes(gq.N, gq.Hs, gq.Ws, gq.Ca, gq.Cb)) {
-        const bool t64 = pg_wino_wgrad_tile64(gq.Ca, gq.Cb, tune.s3w);
-        const int tt = t64 ? 64 : 128;
-        if (tile_id) *tile_id = t64 ? 63 : 60;
-        if (split) *split = pg_wino_wgrad_slices(gq.N, gq.Hs, gq.Ws, gq.Ca, gq.Cb, tune.s3w);
-        if (workgroups) *workgroups = 25L * ((g->Ca + tt - 1) / tt) * ((g->Cb + tt - 1) / tt) * pg_wino_wgrad_slices(gq.N, gq.Hs, gq.Ws, gq.Ca, gq.Cb, tune.s3w);
-        return PG_OK;
-    }
-    if (split) *split = p.split;
-    if (workgroups) *workgroups = (long)p.tiles_m * p.tiles_n * p.ncls * p.split;
-    return PG_OK;
-}
-
-static int conv_kernel_impl(const pg_conv_geom* g, int op, size_t ws_bytes, char* name, size_t name_len, int* split, double* mfma_flops,
-                            double* useful_flops) {
-    int code = 0, sp = 1;
-    long wgs = 0;
-    int rc = pg_conv_describe(g, op, ws_bytes, &code, &sp, &wgs);
-    if (rc != PG_OK) return rc;
-    const int algo_full = op >> 4, algo = algo_full & PG_ALGO_MASK, oc = op & 15;
-    const Tune tune = tune_of(algo_full);
-    static const char* const TILE[5] = {"2,2,2,2", "2,1,2,2", "1,1,4,1", "1,2,2,2", "1,1,2,2"};
-    const int fast = code / 100, rest = code % 100, tid = rest % 10, mode = rest / 10;
-    auto cd = [](long a, long b) { return (a + b - 1) / b; };
-    auto fr = [](double a, double b) { return a / b; };       // the same tile counts without the round-up to whole tiles
-    const double direct = 2.0 * g->N * g->Hs * g->Ws * 16.0 * g->Ca * g->Cb;
-    double fl = direct, fu = direct;      // executed (ragged tiles padded to whole ones) / useful (the algorithm's count on the exact extents)
-    char buf[128];
-    if (code > 1060 && code <= 1064) {
-        snprintf(buf, sizeof buf, "k_s2b_tapnf<%d>", code - 1060);          // one-pass taps-in-N ConvTranspose2d onto <= 4 channels
-    } else if (code > 1064 && code <= 1068) {
-        snprintf(buf, sizeof buf, "k_s2b_tapnf<4>+k_s2b_tapnf<%d>", code - 1064);      // 5 .. 8 channels: two launches
-    } else if (code > 1070 && code <= 1074) {
-        snprintf(buf, sizeof buf, "k_s2b_tapnf<%d,bf16>", code - 1070);     // ... from a bf16 tensor
-    } else if (code > 1074 && code <= 1078) {
-        snprintf(buf, sizeof buf, "k_s2b_tapnf<4,bf16>+k_s2b_tapnf<%d,bf16>", code - 1074);
-    } else if (code == 1050) {
-        snprintf(buf, sizeof buf, (g->stride == 1 && (size_t)(g->Hs + 4) * (g->Ws + 4) * sizeof(float) <= 48 * 1024)
-                                      ? "k_s2b_ca1_s1" : "k_s2b_ca1");      // (the LDS-staged form: stride 1, see s2b_impl)
-    } else if (code >= 1020 && code < 1030) {
-        snprintf(buf, sizeof buf, "%s", pg_bf16x_wgrad_kernel_name(code - 1020));
-    } else if (code >= 1030 && code < 1040) {
-        snprintf(buf, sizeof buf, "%s+k_col2im_small2big", pg_bf16x_kernel_name(3, code - 1030, 0));
-    } else if (code >= 1040 && code < 1050) {
-        snprintf(buf, sizeof buf, "%s", pg_bf16x_kernel_name(2, code - 1040, 0));
-    } else if (code >= 1000) {
-        snprintf(buf, sizeof buf, "%s", pg_bf16x_kernel_name((code / 10) % 10, code % 10, (code / 100) % 10));
-    } else if (algo == PG_ALGO_DIRECT) {
-        snprintf(buf, sizeof buf, "%s", oc == 0 ? "k_big2small_direct" : oc == 1 ? "k_small2big_direct" : "k_wgrad_direct");
-    } else if (mode == 6) {          // Winograd weight gradients: 60 / 63 stride 1 (F(4x4,2x2)), 61 / 62 polyphase stride 2
-        if (tune.s3w) snprintf(buf, sizeof buf, "k_wino_wgrad_gemm_s3<%s>", (tid == 2 || tid == 3) ? "1,1,2,2,2,3" : "2,2,2,2,1,2");
-        else snprintf(buf, sizeof buf, "k_wino_wgrad_gemm<%s>", (tid == 2 || tid == 3) ? "1,1,2,2" : "2,2,2,2");
-        fl = (g->stride == 1) ? pg_wino_wgrad_flops(g->N, g->Hs, g->Ws, g->Ca, g->Cb)
-                              : 2.0 * 16 * g->N * cd(g->Hs, 3) * cd(g->Ws, 3) * g->Ca * 4.0 * g->Cb;
-        const int wr = pg_wino_wgrad_r(g->N, g->Hs, g->Ws);
-        fu = (g->stride == 1) ? 2.0 * (wr + 3) * (wr + 3) * g->N * fr(g->Hs, wr) * fr(g->Ws, wr) * g->Ca * g->Cb
-                              : 2.0 * 16 * g->N * fr(g->Hs, 3) * fr(g->Ws, 3) * g->Ca * 4.0 * g->Cb;
-    } else if (mode == 8) {
-        snprintf(buf, sizeof buf, (tid <= 4 && tapkp_enabled()) ? "k_b2s_tapkp<%d>" : "k_b2s_tapk<%d>", tid);
-        sp = 1;
-    } else if (mode == 7) {          // polyphase Winograd of a stride-2 layer
-        if (tune.s3)       // split-bf16 form (the default): 128-row tiles at two waves per SIMD, 64-row tiles at three
-            snprintf(buf, sizeof buf, "k_wino_bgemm_s3<%s>", (tid & 1) ? "1,2,2,2,3" : "2,2,2,2,2");
-        else
-            snprintf(buf, sizeof buf, "k_wino_bgemm%s<%s>", tid >= 2 ? "_mz" : "", (tid & 1) ? "1,2,2,2" : "2,2,2,2");
-        const int mo = pg_wino2_mo();
-        fl = (oc == 0) ? 2.0 * (mo + 1) * (mo + 1) * g->N * cd(g->Hs, mo) * cd(g->Ws, mo) * 4.0 * g->Cb * g->Ca
-                       : 2.0 * 4 * (mo + 1) * (mo + 1) * g->N * cd(cd(g->Hb, 2) + 1, mo) * cd(cd(g->Wb, 2) + 1, mo) * (double)g->Ca * g->Cb;
-        fu = (oc == 0) ? 2.0 * (mo + 1) * (mo + 1) * g->N * fr(g->Hs, mo) * fr(g->Ws, mo) * 4.0 * g->Cb * g->Ca
-                       : 2.0 * 4 * (mo + 1) * (mo + 1) * g->N * fr(fr(g->Hb, 2), mo) * fr(fr(g->Wb, 2), mo) * (double)g->Ca * g->Cb;
-        sp = 1;
-    } else if (mode == 9 || mode == 4 || mode == 5) {     // stride-1 Winograd forward / data gradient
-        const int mo = mode == 9 ? 3 : 2;
-        const int dm = tune.dma;
-        if (mode == 9 && dm) snprintf(buf, sizeof buf, "k_wino_gemm_dma<3,4,2>");
-        else if (mode == 5 && dm == 2) snprintf(buf, sizeof buf, "k_wino_gemm_dma<2,3,3>");
-        else if (mode == 9 && pg_wino_row_on())
-            snprintf(buf, sizeof buf, (tune.s3r && (oc == 0 ? g->Cb : g->Ca) % 32 == 0) ? "k_wino_gemm_row_s3<2>" : "k_wino_gemm_row<4,1>");
-        else snprintf(buf, sizeof buf, "k_wino_gemm<%s>", mode == 9 ? "1,1,2,2,2,3" : mode == 4 ? "2,1,2,2,2,2" : "1,1,2,2,4,2");
-        const int ho = oc == 0 ? g->Hs : g->Hb, wo = oc == 0 ? g->Ws : g->Wb;
-        fl = 2.0 * (mo + 3) * (mo + 3) * g->N * cd(ho, mo) * cd(wo, mo) * (double)g->Ca * g->Cb;
-        fu = 2.0 * (mo + 3) * (mo + 3) * g->N * fr(ho, mo) * fr(wo, mo) * (double)g->Ca * g->Cb;
-        sp = 1;
-    } else if (mode == 3) {
-        snprintf(buf, sizeof buf, "k_b2s_fast<%s,true>+%s", TILE[tid], oc == 0 ? "k_gather_big2small" : "k_col2im_small2big");
-    } else if (mode == 1 && oc == 2 && wgrad_tapnp_ok(to_geom(g)) && algo != PG_ALGO_BF16) {
-        snprintf(buf, sizeof buf, "k_wgrad_tapnp<%d>", g->Cb);          // persistent taps-in-N weight gradient of the image-facing layers
-        sp = wgrad_tapnp_slabs(to_geom(g));
-    } else if (mode) {
-        snprintf(buf, sizeof buf, "k_wgrad_tapn<%s,%d>", TILE[tid], mode);
-    } else {
-        const bool half = (algo == PG_ALGO_BF16) && fast;
-        // bf16 kernels: the trailing template argument says whether the activation operand(s) are stored as bf16 (PG_IO_* bits)
-        const int io = algo_full & PG_IO_MASK;
-        const char* hin = (oc == 0 ? (io & PG_IO_BIG_BF16) : oc == 1 ? (io & PG_IO_SMALL_BF16) : io == PG_IO_MASK) ? "true" : "false";
-        if (half && oc == 0) snprintf(buf, sizeof buf, "k_b2s_bf16<%s,false,%s>", TILE[tid], hin);
-        else if (half && oc == 1) snprintf(buf, sizeof buf, "k_s2b_bf16<%s,%s>", TILE[tid], hin);
-        else if (half) snprintf(buf, sizeof buf, "k_wgrad_bf16<%s,%s,%s>", TILE[tid], fast == 2 ? "true" : "false", hin);
-        else if (fast && oc == 0) snprintf(buf, sizeof buf, "k_b2s_fast<%s,false>", TILE[tid]);
-        else if (fast && oc == 1) snprintf(buf, sizeof buf, "k_s2b_fast<%s>", TILE[tid]);
-        else if (fast) snprintf(buf, sizeof buf, "k_wgrad_fast<%s,%s>", TILE[tid], fast == 2 ? "true" : "false");
-        else snprintf(buf, sizeof buf, "%s<%s>", oc == 0 ? "k_big2small" : oc == 1 ? "k_small2big" : "k_wgrad", TILE[tid]);
-    }
-    if (name && name_len) snprintf(name, name_len, "%s", buf);
-    if (split) *split = sp;
-    if (mfma_flops) *mfma_flops = fl;
-    if (useful_flops) *useful_flops = fu;
+    ConvPlan p;
+    if (!query_plan(g, op & 15, op >> 4, ws_bytes, 0, &p)) return PG_EINVAL;
+    describe_plan(p, to_geom(g), op & 15, tile_id, split, workgroups);
     return PG_OK;
 }
 
 int pg_conv_kernel(const pg_conv_geom* g, int op, size_t ws_bytes, char* name, size_t name_len, int* split, double* mfma_flops) {
-    return conv_kernel_impl(g, op, ws_bytes, name, name_len, split, mfma_flops, nullptr);
+    ConvPlan p;
+    if (!query_plan(g, op & 15, op >> 4, ws_bytes, 0, &p)) return PG_EINVAL;
+    if (name && name_len) name_of(p, to_geom(g), op & 15, op >> 4, tune_of(op >> 4), name, name_len);
+    if (split && p.path == Path::Direct) describe_plan(p, to_geom(g), op & 15, nullptr, split, nullptr);      // (of the MFMA path, as pg_conv_describe)
+    else if (split) *split = p.split;
+    flops_of(p, to_geom(g), op & 15, mfma_flops, nullptr);
+    return PG_OK;
 }
 
 int pg_conv_kernel_flops(const pg_conv_geom* g, int op, size_t ws_bytes, double* executed, double* useful) {
-    return conv_kernel_impl(g, op, ws_bytes, nullptr, 0, nullptr, executed, useful);
+    ConvPlan p;
+    if (!query_plan(g, op & 15, op >> 4, ws_bytes, 0, &p)) return PG_EINVAL;
+    flops_of(p, to_geom(g), op & 15, executed, useful);
+    return PG_OK;
 }
 
-// the col2im half of the taps-folded-into-N small -> big paths
-static int launch_col2im(const float* D, const float* bias, float* big, int ld_big, const Geom& g, int act, hipStream_t st) {
-    const size_t lds = (size_t)(CT_H + 2) * (CT_W + 2) * 16 * g.Cb * sizeof(float);
-    if (g.s == 2) {                    // (a D row is 16 * Cb floats: always whole float4s)
-        if (lds <= 64 * 1024 && aligned16(D)) {
-            const int tiles_h = (g.Hs + CT_H) / CT_H, tiles_w = (g.Ws + CT_W) / CT_W;      // big rows reach one small row past Hs - 1
-            hipLaunchKernelGGL(k_col2im_s2_lds, dim3((unsigned)(g.N * tiles_h * tiles_w)), dim3(256), lds, st, D, bias, big, ld_big, g, act,
-                               tiles_h, tiles_w);
-            return hipGetLastError() == hipSuccess ? PG_OK : PG_ELAUNCH;
-        }
-    }
-    const long total = (long)g.N * g.Hb * g.Wb * g.Cb;
-    hipLaunchKernelGGL(k_col2im_small2big, dim3((int)std::min<long>((total + 255) / 256, 8192)), dim3(256), 0, st, D, bias, big, ld_big, g, act);
-    return hipGetLastError() == hipSuccess ? PG_OK : PG_ELAUNCH;
+size_t pg_conv_u_bytes(const pg_conv_geom* g, int op, int algo, size_t ws_bytes) {
+    ConvPlan p;
+    if ((op != 0 && op != 1) || !query_plan(g, op, algo, ws_bytes, OFFER_U, &p)) return 0;
+    return p.rc == PG_OK ? p.u_bytes : 0;
 }
 
-static const pg_conv_extras NO_EXTRAS = {nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, 0};
-
-static int b2s_impl(const float* big, int ld_big, const float* P, const float* bias, float* small, int ld_small,
-                    const pg_conv_geom* gg, int act, int algo, void* ws, size_t ws_bytes, void* stream, const pg_conv_extras* xp) {
-    const pg_conv_extras& x = xp ? *xp : NO_EXTRAS;
-    double* part = x.part;
-    if ((x.u_cache && !aligned16(x.u_cache)) || (x.v_keep && !aligned16(x.v_keep)) || x.v_pre) return PG_EINVAL;
-    if (!geom_ok(gg) || !big || !P || !small || ld_big < gg->Cb || ld_small < gg->Ca) return PG_EINVAL;
-    if (act < PG_ACT_NONE || act > PG_ACT_SIGMOID) return PG_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    Geom g = to_geom(gg);
-    const Tune tune = tune_of(algo);
-    const int io = algo & PG_IO_MASK;                 // bf16 activation storage: PG_IO_BIG_BF16 = input, PG_IO_SMALL_BF16 = output
-    algo &= PG_ALGO_MASK;
-    if (io && algo != PG_ALGO_BF16) return PG_EINVAL;
-    if (algo == PG_ALGO_DIRECT) {
-        const long total = (long)g.N * g.Hs * g.Ws * g.Ca;
-        int blocks = (int)std::min<long>((total + 255) / 256, 65536);
-        hipLaunchKernelGGL(k_big2small_direct, dim3(blocks), dim3(256), 0, st, big, ld_big, P, bias, small, ld_small, g,
-                           act);
-        return hipGetLastError() == hipSuccess ? PG_OK : PG_ELAUNCH;
-    }
-    if (!ws) ws_bytes = 0;
-    if (algo == PG_ALGO_AUTO && wino_b2s_ok(g, tune) && aligned16(P) && aligned16(ws) &&
-        ws_bytes >= pg_wino_ws_bytes(g.N, g.Hs, g.Ws, g.Cb, g.Ca, tune.mo1) &&
-        pg_wino_eligible(g.N, g.Hb, g.Wb, g.Cb, g.Hs, g.Ws, g.Ca, ld_big, big, tune.mo1)) {
-        if (part) return PG_EINVAL;
-        if (x.v_keep && !(wino_wgrad_ok(g, tune) && pg_wino_wgrad_v_bytes(g.N, g.Hs, g.Ws, g.Ca, g.Cb, tune.mo1))) return PG_EINVAL;
-        int rc = pg_wino_prepare(big, ld_big, P, 0, g.N, g.Hb, g.Wb, g.Cb, g.Hs, g.Ws, g.Ca, 1, ws, st, tune.mo1, x.u_cache, x.u_valid,
-                                 x.v_keep);
-        if (rc != PG_OK) return rc;
-        const int nsl = pg_wino_gemm_rows(g.N, g.Hs, g.Ws, g.Cb, g.Ca, tune.mo1, tune.dma, small, ld_small, bias, pg_epi_mul{nullptr, 0, 0})
-                            ? 1 : pg_wino_gemm_slices(g.N, g.Hs, g.Ws, g.Cb, g.Ca, tune.mo1);
-        {
-            TimedLaunch timed(st);
-            rc = pg_wino_gemm(bias, small, ld_small, g.N, g.Cb, g.Hs, g.Ws, g.Ca, act, ws, st, tune.mo1, tune.dma, x.u_cache,
-                              pg_epi_mul{nullptr, 0, 0}, x.v_keep, tune.s3r);
-        }
-        if (rc != PG_OK || nsl == 1) return rc;
-        const long pix = (long)g.N * g.Hs * g.Ws;
-        return launch_reduce(pg_wino_gemm_slabs(ws, g.N, g.Hs, g.Ws, g.Cb, g.Ca, tune.mo1), pix * g.Ca, nsl, small, ld_small, pix, g.Ca, bias,
-                             act, st);
-    }
-    if (algo == PG_ALGO_AUTO && wino2_b2s_ok(g, tune) && (ld_big % 4 == 0) && (ld_small % 4 == 0) && aligned16(big) && aligned16(P) &&
-        aligned16(small) && aligned16(ws) && (!bias || aligned16(bias)) &&
-        ws_bytes >= pg_wino2_ws_bytes(g.N, g.Hs, g.Ws, g.Ca, g.Cb)) {
-        hipEvent_t e0 = t_ev0, e1 = t_ev1;
-        t_ev0 = nullptr;
-        t_ev1 = nullptr;
-        if (part && pg_wino2_b2s_stats_chunks(g.N, g.Hs, g.Ws, g.Ca) == 0) return PG_EINVAL;
-        if (x.v_keep && pg_wino2_mo() != 3) return PG_EINVAL;
-        return pg_wino2_b2s(big, ld_big, P, bias, small, ld_small, g.N, g.Hb, g.Wb, g.Hs, g.Ws, g.Ca, g.Cb, act, ws, st, e0, e1, nullptr,
-                            part, x.v_keep, x.u_cache, x.u_valid, tune.s3);
-    }
-    if (bf16x_ok(g, 0, algo | io, tune) && !x.v_keep) {
-        const int rc = bf16x_run(0, big, ld_big, P, bias, small, ld_small, g, act, io & PG_IO_SMALL_BF16, ws, ws_bytes, st, x, tune.bf16ring);
-        if (rc != BF16X_SKIP) return rc;
-    }
-    // only the Winograd paths (and, for the partial sums, the persistent image-facing kernel below) have operands to hand over
-    // (the pg_conv_*_bytes / _chunks queries said 0)
-    if (x.v_keep || x.u_cache) return PG_EINVAL;
-    if (part && !(algo == PG_ALGO_AUTO && !io && tapk_enabled() && tapkp_enabled() && tapkp_stats_chunks(g) > 0 && !bias && act == PG_ACT_NONE))
-        return PG_EINVAL;
-    if (!io && b2s_tapn_ok(g) && (ld_big % 4 == 0) && aligned16(big) && aligned16(P) && aligned16(ws) &&
-        ws_bytes >= b2s_tapn_ws(g) && tensor_bytes((long)g.N * g.Hb * g.Wb, ld_big, g.Cb) < FAST_LIMIT) {
-        // D[big pixel][(tap, a)] = big . P^T (row GEMM over the pixels), then gather the 16 taps per output pixel
-        float* D = (float*)ws;
-        const long Mb = (long)g.N * g.Hb * g.Wb;
-        const int Nc = 16 * g.Ca;
-        Geom g1{g.N, g.Hb, g.Wb, g.Hb, g.Wb, Nc, g.Cb, 1};
-        Tile t = pick_tile(Mb, Nc);
-        dim3 grid((unsigned)((Mb + t.bm - 1) / t.bm), (Nc + t.bn - 1) / t.bn, 1);
-        {
-            TimedLaunch timed(st);
-            PG_DISPATCH_B2SF(true, t.id, grid, st, big, ld_big, P, D, Nc, 0L, g1, g.Cb / KC, (const float*)nullptr, 0,
-                             (int)tensor_bytes(Mb, ld_big, g.Cb), (int)(16L * g.Ca * g.Cb * 4));
-        }
-        if (hipGetLastError() != hipSuccess) return PG_ELAUNCH;
-        const long total = (long)g.N * g.Hs * g.Ws * g.Ca;
-        hipLaunchKernelGGL(k_gather_big2small, dim3((int)std::min<long>((total + 255) / 256, 8192)), dim3(256), 0, st, D, bias,
-                           small, ld_small, g, act);
-        return hipGetLastError() == hipSuccess ? PG_OK : PG_ELAUNCH;
-    }
-    if (g.Cb <= 5 && !io && !force_generic() && tapk_enabled()) {     // (6..8 channels: measured slower than the generic kernel)
-        // K = 16*Cb <= 48: one-shot kernel (with 4 channels the pipelined generic kernel is as fast: 46 TFLOP/s both)
-        const int vec4 = (g.Cb == 4) && (ld_big % 4 == 0) && aligned16(big);
-        const int vec_out = (g.Ca % 4 == 0) && (ld_small % 4 == 0) && aligned16(small) && (!bias || aligned16(bias));
-        const int tmk = g.Cb <= 4 ? 128 : 64;
-        dim3 grid((unsigned)(((long)g.N * g.Hs * g.Ws + tmk - 1) / tmk), (g.Ca + 63) / 64, 1);
-        TimedLaunch timed(st);
-        const long big_b = tensor_bytes((long)g.N * g.Hb * g.Wb, ld_big, g.Cb), out_b = tensor_bytes((long)g.N * g.Hs * g.Ws, ld_small, g.Ca);
-        if (g.Cb <= 4 && tapkp_enabled() && vec_out && (act == PG_ACT_NONE || act == PG_ACT_LEAKY) && big_b < FAST_LIMIT && out_b < FAST_LIMIT &&
-            (g.Cb != 4 || vec4) && (long)g.N * g.Hs * g.Ws < 0x3fffffL * 64) {
-            // persistent form: 2 workgroups per CU (two LDS buffers of 9 .. 35 KB, two accumulator sets), each walking tiles blockIdx.x, + gridDim.x, ...
-            const int ntiles = (int)grid.x;
-            static const int pwg = pg_exp_env("PATCHGAN_TAPKP_WG") ? atoi(pg_exp_env("PATCHGAN_TAPKP_WG")) : 512;
-            const bool wide3 = (g.Cb == 3) && (ld_big % 4 == 0) && (ld_big >= 4) && aligned16(big);
-            dim3 pgrid((unsigned)std::min<long>(ntiles, std::max<long>(1, pwg / (long)grid.y)), grid.y, 1);
-            if (part) {             // (act == none, no bias, whole tiles per sample: checked above); one workgroup per CU (88 .. 104 KB of LDS)
-                pgrid.x = (unsigned)std::min<long>(ntiles, std::max<long>(1, 256 / (long)grid.y));
-                switch (g.Cb) {
-                    case 1: hipLaunchKernelGGL((k_b2s_tapkp<1, 0, false, true>), pgrid, dim3(256), 0, st, big, ld_big, P, small, ld_small, g, bias, (int)big_b, (int)out_b, ntiles, part); break;
-                    case 2: hipLaunchKernelGGL((k_b2s_tapkp<2, 0, false, true>), pgrid, dim3(256), 0, st, big, ld_big, P, small, ld_small, g, bias, (int)big_b, (int)out_b, ntiles, part); break;
-                    case 3:
-                        if (wide3) hipLaunchKernelGGL((k_b2s_tapkp<3, 0, true, true>), pgrid, dim3(256), 0, st, big, ld_big, P, small, ld_small, g, bias, (int)big_b, (int)out_b, ntiles, part);
-                        else hipLaunchKernelGGL((k_b2s_tapkp<3, 0, false, true>), pgrid, dim3(256), 0, st, big, ld_big, P, small, ld_small, g, bias, (int)big_b, (int)out_b, ntiles, part);
-                        break;
-                    default: hipLaunchKernelGGL((k_b2s_tapkp<4, 0, true, true>), pgrid, dim3(256), 0, st, big, ld_big, P, small, ld_small, g, bias, (int)big_b, (int)out_b, ntiles, part); break;
-                }
-                return hipGetLastError() == hipSuccess ? PG_OK : PG_ELAUNCH;
-            }
-#define PG_TAPKP(CB_, WIDE_)                                                                                                            \
-    do {                                                                                                                                \
-        if (act == PG_ACT_LEAKY)                                                                                                        \
-            hipLaunchKernelGGL((k_b2s_tapkp<CB_, 1, WIDE_>), pgrid, dim3(256), 0, st, big, ld_big, P, small, ld_small, g, bias, (int)big_b, \
-                               (int)out_b, ntiles);                                                                                \
-        else                                                                                                                            \
-            hipLaunchKernelGGL((k_b2s_tapkp<CB_, 0, WIDE_>), pgrid, dim3(256), 0, st, big, ld_big, P, small, ld_small, g, bias, (int)big_b, \
-                               (int)out_b, ntiles);                                                                                \
-    } while (0)
-            switch (g.Cb) {
-                case 1: PG_TAPKP(1, false); break;
-                case 2: PG_TAPKP(2, false); break;
-                case 3: if (wide3) PG_TAPKP(3, true); else PG_TAPKP(3, false); break;
-                default: PG_TAPKP(4, true); break;
-            }
-#undef PG_TAPKP
-            return hipGetLastError() == hipSuccess ? PG_OK : PG_ELAUNCH;
-        }
-        if (part) return PG_EINVAL;        // (a view the persistent kernel does not take: unaligned output, tensor beyond 32-bit offsets)
-        switch (g.Cb) {
-            case 1: hipLaunchKernelGGL(k_b2s_tapk<1>, grid, dim3(256), 0, st, big, ld_big, P, small, ld_small, g, bias, act, vec4, vec_out); break;
-            case 2: hipLaunchKernelGGL(k_b2s_tapk<2>, grid, dim3(256), 0, st, big, ld_big, P, small, ld_small, g, bias, act, vec4, vec_out); break;
-            case 3: hipLaunchKernelGGL(k_b2s_tapk<3>, grid, dim3(256), 0, st, big, ld_big, P, small, ld_small, g, bias, act, vec4, vec_out); break;
-            case 5: hipLaunchKernelGGL((k_b2s_tapk<5, 1>), grid, dim3(256), 0, st, big, ld_big, P, small, ld_small, g, bias, act, 0, vec_out); break;
-            case 6: hipLaunchKernelGGL((k_b2s_tapk<6, 1>), grid, dim3(256), 0, st, big, ld_big, P, small, ld_small, g, bias, act, 0, vec_out); break;
-            case 7: hipLaunchKernelGGL((k_b2s_tapk<7, 1>), grid, dim3(256), 0, st, big, ld_big, P, small, ld_small, g, bias, act, 0, vec_out); break;
-            case 8: hipLaunchKernelGGL((k_b2s_tapk<8, 1>), grid, dim3(256), 0, st, big, ld_big, P, small, ld_small, g, bias, act, 0, vec_out); break;
-            default: hipLaunchKernelGGL(k_b2s_tapk<4>, grid, dim3(256), 0, st, big, ld_big, P, small, ld_small, g, bias, act, vec4, vec_out); break;
-        }
-        return hipGetLastError() == hipSuccess ? PG_OK : PG_ELAUNCH;
-    }
-    Plan p = plan_b2s(gg);
-    clamp_split(p, ws_bytes, 0);
-    const bool in_bf = io & PG_IO_BIG_BF16, out_bf = io & PG_IO_SMALL_BF16;
-    const int veck = (g.Cb % 4 == 0) && (ld_big % 4 == 0) && aligned_io(big, in_bf) && aligned16(P);
-    dim3 grid(p.tiles_m, p.tiles_n, p.split);
-    const long big_bytes = tensor_bytes((long)g.N * g.Hb * g.Wb, ld_big, g.Cb, in_bf), p_bytes = 16L * g.Ca * g.Cb * 4;
-    const bool fast = veck && g.Cb >= KC && big_bytes < FAST_LIMIT && p_bytes < FAST_P_LIMIT && !force_generic();
-    if (io && !fast) return PG_EINVAL;               // bf16 tensors only on the fast bf16 kernels
-    if (p.split == 1) {
-        TimedLaunch timed(st);
-        if (fast && algo == PG_ALGO_BF16 && in_bf) {
-            PG_DISPATCH_B2SH(true, p.t.id, grid, st, big, ld_big, P, small, ld_small, 0L, g, p.cps, bias, act, (int)big_bytes,
-                             (int)p_bytes, (int)out_bf);
-        } else if (fast && algo == PG_ALGO_BF16) {
-            PG_DISPATCH_B2SH(false, p.t.id, grid, st, big, ld_big, P, small, ld_small, 0L, g, p.cps, bias, act, (int)big_bytes,
-                             (int)p_bytes, (int)out_bf);
-        } else if (fast) {
-            PG_DISPATCH_B2SF(false, p.t.id, grid, st, big, ld_big, P, small, ld_small, 0L, g, p.cps, bias, act,
-                             (int)big_bytes, (int)p_bytes);
-        } else {
-            PG_DISPATCH_TILE(k_big2small, p.t.id, grid, st, big, ld_big, P, small, ld_small, 0L, g, p.cps, veck, bias,
-                             act);
-        }
-        return hipGetLastError() == hipSuccess ? PG_OK : PG_ELAUNCH;
-    }
-    float* slabs = (float*)ws;
-    {
-        TimedLaunch timed(st);
-        if (fast && algo == PG_ALGO_BF16 && in_bf) {
-            PG_DISPATCH_B2SH(true, p.t.id, grid, st, big, ld_big, P, slabs, g.Ca, p.out_elems, g, p.cps, (const float*)nullptr, 0,
-                             (int)big_bytes, (int)p_bytes, 0);
-        } else if (fast && algo == PG_ALGO_BF16) {
-            PG_DISPATCH_B2SH(false, p.t.id, grid, st, big, ld_big, P, slabs, g.Ca, p.out_elems, g, p.cps, (const float*)nullptr, 0,
-                             (int)big_bytes, (int)p_bytes, 0);
-        } else if (fast) {
-            PG_DISPATCH_B2SF(false, p.t.id, grid, st, big, ld_big, P, slabs, g.Ca, p.out_elems, g, p.cps,
-                             (const float*)nullptr, 0, (int)big_bytes, (int)p_bytes);
-        } else {
-            PG_DISPATCH_TILE(k_big2small, p.t.id, grid, st, big, ld_big, P, slabs, g.Ca, p.out_elems, g, p.cps, veck,
-                             (const float*)nullptr, 0);
-        }
-    }
-    if (hipGetLastError() != hipSuccess) return PG_ELAUNCH;
-    return launch_reduce(slabs, p.out_elems, p.split, small, ld_small, (long)g.N * g.Hs * g.Ws, g.Ca, bias, act, st, out_bf);
+int pg_conv_stats_chunks(const pg_conv_geom* g, int op, int algo, size_t ws_bytes) {
+    ConvPlan p;
+    if ((op != 0 && op != 1) || !query_plan(g, op, algo, ws_bytes, OFFER_PART, &p)) return 0;
+    return p.rc == PG_OK ? p.stats_chunks : 0;
 }
 
-int pg_conv4x4_big2small(const float* big, int ld_big, const float* P, const float* bias, float* small,
-                         int ld_small, const pg_conv_geom* gg, int act, int algo, void* ws, size_t ws_bytes,
-                         void* stream) {
-    return b2s_impl(big, ld_big, P, bias, small, ld_small, gg, act, algo, ws, ws_bytes, stream, nullptr);
+int pg_conv_mul_ok(const pg_conv_geom* g, int algo, size_t ws_bytes) {
+    ConvPlan p;
+    if (!query_plan(g, 1, algo, ws_bytes, 0, &p)) return 0;
+    return p.mul_ok ? 1 : 0;
 }
 
-int pg_conv4x4_big2small_x(const float* big, int ld_big, const float* P, const float* bias, float* small,
-                           int ld_small, const pg_conv_geom* gg, int act, int algo, void* ws, size_t ws_bytes,
-                           void* stream, const pg_conv_extras* x) {
-    return b2s_impl(big, ld_big, P, bias, small, ld_small, gg, act, algo, ws, ws_bytes, stream, x);
-}
-
-static int s2b_impl(const float* small, int ld_small, const float* P, const float* bias, float* big, int ld_big,
-                    const pg_conv_geom* gg, int act, int algo, void* ws, size_t ws_bytes, void* stream, const pg_conv_extras* xp) {
-    const pg_conv_extras& x = xp ? *xp : NO_EXTRAS;
-    double* part = x.part;
-    if ((x.u_cache && !aligned16(x.u_cache)) || x.v_keep || x.v_pre) return PG_EINVAL;
-    const pg_epi_mul mul{x.mul_t, x.mul_ld, x.mul_act};
-    if (mul.t && (mul.ld < gg->Cb || mul.act < PG_ACT_NONE || mul.act > PG_ACT_SIGMOID || part)) return PG_EINVAL;
-    if (!geom_ok(gg) || !big || !P || !small || ld_big < gg->Cb || ld_small < gg->Ca) return PG_EINVAL;
-    if (act < PG_ACT_NONE || act > PG_ACT_SIGMOID) return PG_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    Geom g = to_geom(gg);
-    const Tune tune = tune_of(algo);
-    const int io = algo & PG_IO_MASK;                 // PG_IO_SMALL_BF16 = input, PG_IO_BIG_BF16 = output
-    algo &= PG_ALGO_MASK;
-    if (io && algo != PG_ALGO_BF16) return PG_EINVAL;
-    if (algo == PG_ALGO_DIRECT) {
-        if (mul.t) return PG_EINVAL;
-        const long total = (long)g.N * g.Hb * g.Wb * g.Cb;
-        int blocks = (int)std::min<long>((total + 255) / 256, 65536);
-        hipLaunchKernelGGL(k_small2big_direct, dim3(blocks), dim3(256), 0, st, small, ld_small, P, bias, big, ld_big, g,
-                           act);
-        return hipGetLastError() == hipSuccess ? PG_OK : PG_ELAUNCH;
-    }
-    if (!ws) ws_bytes = 0;
-    if (s2b_ca1_ok(g, algo | io)) {
-        const bool out_bf = io & PG_IO_BIG_BF16;
-        const bool al = aligned16(P) && (!bias || aligned16(bias)) && aligned_bf_view(big, ld_big, out_bf) &&
-                        (!mul.t || aligned_bf_view(mul.t, mul.ld, out_bf));
-        if (al && !part && !x.u_cache) {
-            const long total = (long)g.N * g.Hb * g.Wb;
-            // pixels per workgroup: ~1500 workgroups, whole trips of 2 pixels per thread row (256 / (Cb / 4) pixel rows per workgroup)
-            const int trip = 2 * (256 / (g.Cb / 4));
-            static const int ca1_wgs = pg_exp_env("PATCHGAN_CA1_WGS") ? atoi(pg_exp_env("PATCHGAN_CA1_WGS")) : 1536;
-            const int ppb = (int)std::max<long>(trip, ((total / ca1_wgs + trip - 1) / trip) * trip);
-            TimedLaunch timed(st);
-            const size_t xs_bytes = (size_t)(g.Hs + 4) * (g.Ws + 4) * sizeof(float);
-            static const bool no_s1 = pg_exp_env("PATCHGAN_NO_CA1S1") != nullptr;
-            if (!no_s1 && g.s == 1 && xs_bytes <= 48 * 1024 && g.Hb == g.Hs + 1 && g.Wb == g.Ws + 1) {
-                // per-sample form: ~1536 workgroups in all, whole pixel rows of the workgroup (256 / (Cb / 4) pixels per trip)
-                const int npr = 256 / (g.Cb / 4), hwb = g.Hb * g.Wb;
-                const long per = std::max<long>(1, 1536 / g.N);
-                static const int minpix = pg_exp_env("PATCHGAN_CA1S1_MINPIX") ? atoi(pg_exp_env("PATCHGAN_CA1S1_MINPIX")) : 0;
-                const int ppb1 = std::max(minpix, (int)(((hwb + per - 1) / per + npr - 1) / npr * npr));
-                hipLaunchKernelGGL(k_s2b_ca1_s1, dim3((unsigned)((hwb + ppb1 - 1) / ppb1), g.N), dim3(256), xs_bytes, st, small, ld_small, P, bias,
-                                   big, ld_big, g, act, out_bf ? 1 : 0, mul, ppb1);
-                return hipGetLastError() == hipSuccess ? PG_OK : PG_ELAUNCH;
-            }
-            hipLaunchKernelGGL(k_s2b_ca1, dim3((unsigned)((total + ppb - 1) / ppb)), dim3(256), 0, st, small, ld_small, P, bias, big, ld_big, g,
-                               act, out_bf ? 1 : 0, mul, ppb);
-            return hipGetLastError() == hipSuccess ? PG_OK : PG_ELAUNCH;
-        }
-    }
-    if (algo == PG_ALGO_AUTO && wino_s2b_ok(g, tune) && aligned16(P) && aligned16(ws) &&
-        ws_bytes >= pg_wino_ws_bytes(g.N, g.Hb, g.Wb, g.Ca, g.Cb, tune.mo1) &&
-        pg_wino_eligible(g.N, g.Hs, g.Ws, g.Ca, g.Hb, g.Wb, g.Cb, ld_small, small, tune.mo1)) {
-        if (part) return PG_EINVAL;
-        if (mul.t && (!aligned16(mul.t) || mul.ld % 4)) return PG_EINVAL;
-        int rc = pg_wino_prepare(small, ld_small, P, 1, g.N, g.Hs, g.Ws, g.Ca, g.Hb, g.Wb, g.Cb, 2, ws, st, tune.mo1, x.u_cache, x.u_valid);
-        if (rc != PG_OK) return rc;
-        const int nsl = pg_wino_gemm_rows(g.N, g.Hb, g.Wb, g.Ca, g.Cb, tune.mo1, tune.dma, big, ld_big, bias, mul)
-                            ? 1 : pg_wino_gemm_slices(g.N, g.Hb, g.Wb, g.Ca, g.Cb, tune.mo1);
-        {
-            TimedLaunch timed(st);
-            rc = pg_wino_gemm(bias, big, ld_big, g.N, g.Ca, g.Hb, g.Wb, g.Cb, act, ws, st, tune.mo1, tune.dma, x.u_cache, mul, nullptr, tune.s3r);
-        }
-        if (rc != PG_OK || nsl == 1) return rc;
-        const long pix = (long)g.N * g.Hb * g.Wb;
-        return launch_reduce(pg_wino_gemm_slabs(ws, g.N, g.Hb, g.Wb, g.Ca, g.Cb, tune.mo1), pix * g.Cb, nsl, big, ld_big, pix, g.Cb, bias, act,
-                             st, 0, mul);
-    }
-    if (algo == PG_ALGO_AUTO && wino2_s2b_ok(g, tune) && (ld_big % 4 == 0) && (ld_small % 4 == 0) && aligned16(big) && aligned16(P) &&
-        aligned16(small) && aligned16(ws) && (!bias || aligned16(bias)) &&
-        ws_bytes >= pg_wino2c_ws_bytes(g.N, g.Hb, g.Wb, g.Ca, g.Cb)) {
-        hipEvent_t e0 = t_ev0, e1 = t_ev1;
-        t_ev0 = nullptr;
-        t_ev1 = nullptr;
-        if (part && pg_wino2_s2b_stats_chunks(g.N, g.Hb, g.Wb, g.Cb) == 0) return PG_EINVAL;
-        if (mul.t && (!aligned16(mul.t) || mul.ld % 4)) return PG_EINVAL;
-        return pg_wino2_s2b(small, ld_small, P, bias, big, ld_big, g.N, g.Hb, g.Wb, g.Hs, g.Ws, g.Ca, g.Cb, act, ws, st, e0, e1, part,
-                            x.u_cache, x.u_valid, mul, tune.s3);
-    }
-    if (s2b_tapnf_bf_ok(g, algo | io, tune) && !part && !x.u_cache && !mul.t && (ld_small % 8 == 0) && aligned16(small) &&
-        tensor_bytes((long)g.N * g.Hs * g.Ws, ld_small, g.Ca, true) < FAST_LIMIT && tensor_bytes((long)g.N * g.Hb * g.Wb, ld_big, g.Cb) < FAST_LIMIT)
-        return launch_tapnf(true, small, ld_small, P, bias, big, ld_big, g, act, tensor_bytes((long)g.N * g.Hs * g.Ws, ld_small, g.Ca, true),
-                            tensor_bytes((long)g.N * g.Hb * g.Wb, ld_big, g.Cb), st);
-    if (bf16x_s2b_tapn_ok(g, algo | io, tune) && !part && !x.u_cache && !mul.t && ws && aligned16(ws) && ws_bytes >= bf16x_s2b_tapn_ws(g) &&
-        aligned_bf_view(small, ld_small, true) && aligned16(P) &&
-        tensor_bytes((long)g.N * g.Hs * g.Ws, ld_small, g.Ca, true) < FAST_LIMIT) {
-        // D[small pixel][(tap, b)] = small . W' (bf16 row GEMM), then col2im: each big pixel sums the taps that reach it
-        const int Nc = 16 * g.Cb;
-        const size_t wb = pg_bf16x_w_bytes(g.Ca, g.Cb);
-        float* D = (float*)((char*)ws + wb);
-        int rc = pg_bf16x_pack(P, ws, g.Ca, g.Cb, 1, st);
-        if (rc != PG_OK) return rc;
-        const pg_bf16x_plan bp = pg_bf16x_plan_of(3, g.N, g.Hb, g.Wb, g.Hs, g.Ws, g.Ca, Nc, g.s, 0);
-        {
-            TimedLaunch timed(st);
-            rc = pg_bf16x_conv(3, small, ld_small, tensor_bytes((long)g.N * g.Hs * g.Ws, ld_small, g.Ca, true), ws, D, Nc, 0L, g.N, g.Hb,
-                               g.Wb, g.Hs, g.Ws, g.Ca, Nc, g.s, &bp, nullptr, 0, 0, st);
-        }
-        if (rc != PG_OK) return rc;
-        return launch_col2im(D, bias, big, ld_big, g, act, st);
-    }
-    if (bf16x_ok(g, 1, algo | io, tune)) {
-        const int rc = bf16x_run(1, small, ld_small, P, bias, big, ld_big, g, act, io & PG_IO_BIG_BF16, ws, ws_bytes, st, x, tune.bf16ring);
-        if (rc != BF16X_SKIP) return rc;
-    }
-    if (part || x.u_cache || mul.t) return PG_EINVAL;
-    if (!io && s2b_tapnf_ok(g) && (ld_small % 4 == 0) && aligned16(small) &&
-        tensor_bytes((long)g.N * g.Hs * g.Ws, ld_small, g.Ca) < FAST_LIMIT && tensor_bytes((long)g.N * g.Hb * g.Wb, ld_big, g.Cb) < FAST_LIMIT)
-        return launch_tapnf(false, small, ld_small, P, bias, big, ld_big, g, act, tensor_bytes((long)g.N * g.Hs * g.Ws, ld_small, g.Ca),
-                            tensor_bytes((long)g.N * g.Hb * g.Wb, ld_big, g.Cb), st);
-    if (!io && s2b_tapn_ok(g) && (ld_small % 4 == 0) && aligned16(small) && aligned16(P) && aligned16(ws) &&
-        ws_bytes >= s2b_tapn_ws(g) && tensor_bytes((long)g.N * g.Hs * g.Ws, ld_small, g.Ca) < FAST_LIMIT) {
-        // D[small pixel][(tap, b)] = small . W' (row GEMM), then col2im: each big pixel sums the taps that reach it
-        const int Nc = 16 * g.Cb;
-        float* Wp = (float*)ws;
-        float* D = Wp + (((size_t)Nc * g.Ca + 63) & ~(size_t)63);
-        const float* W = P;
-        if (g.Cb > 1) {
-            hipLaunchKernelGGL(k_pack_taps_b, dim3((Nc * g.Ca + 255) / 256), dim3(256), 0, st, P, Wp, g.Ca, g.Cb);
-            if (hipGetLastError() != hipSuccess) return PG_ELAUNCH;
-            W = Wp;
-        }
-        const long Ms = (long)g.N * g.Hs * g.Ws;
-        Geom g1{g.N, g.Hs, g.Ws, g.Hs, g.Ws, Nc, g.Ca, 1};
-        Tile t = pick_tile(Ms, Nc);
-        dim3 grid((unsigned)((Ms + t.bm - 1) / t.bm), (Nc + t.bn - 1) / t.bn, 1);
-        {
-            TimedLaunch timed(st);
-            PG_DISPATCH_B2SF(true, t.id, grid, st, small, ld_small, W, D, Nc, 0L, g1, g.Ca / KC, (const float*)nullptr, 0,
-                             (int)tensor_bytes(Ms, ld_small, g.Ca), (int)((long)Nc * g.Ca * 4));
-        }
-        if (hipGetLastError() != hipSuccess) return PG_ELAUNCH;
-        return launch_col2im(D, bias, big, ld_big, g, act, st);
-    }
-    Plan p = plan_s2b(gg);
-    clamp_split(p, ws_bytes, 0);
-    const bool in_bf = io & PG_IO_SMALL_BF16, out_bf = io & PG_IO_BIG_BF16;
-    const int veck = (g.Ca % 4 == 0) && (ld_small % 4 == 0) && aligned_io(small, in_bf);
-    const int vecn = (g.Cb % 4 == 0) && aligned16(P);
-    dim3 grid(p.tiles_m, p.tiles_n, p.ncls * p.split);
-    const long small_bytes = tensor_bytes((long)g.N * g.Hs * g.Ws, ld_small, g.Ca, in_bf), p_bytes = 16L * g.Ca * g.Cb * 4;
-    const bool fast = veck && g.Ca >= KC && small_bytes < FAST_LIMIT && p_bytes < FAST_P_LIMIT && !force_generic();
-    if (io && !fast) return PG_EINVAL;
-    if (p.split == 1) {
-        TimedLaunch timed(st);
-        if (fast && algo == PG_ALGO_BF16 && in_bf) {
-            PG_DISPATCH_S2BH(true, p.t.id, grid, st, small, ld_small, P, big, ld_big, 0L, g, p.cps, bias, act,
-                             (int)small_bytes, (int)p_bytes, (int)out_bf);
-        } else if (fast && algo == PG_ALGO_BF16) {
-            PG_DISPATCH_S2BH(false, p.t.id, grid, st, small, ld_small, P, big, ld_big, 0L, g, p.cps, bias, act,
-                             (int)small_bytes, (int)p_bytes, (int)out_bf);
-        } else if (fast) {
-            PG_DISPATCH_TILE(k_s2b_fast, p.t.id, grid, st, small, ld_small, P, big, ld_big, 0L, g, p.cps, bias, act,
-                             (int)small_bytes, (int)p_bytes);
-        } else {
-            PG_DISPATCH_TILE(k_small2big, p.t.id, grid, st, small, ld_small, P, big, ld_big, 0L, g, p.cps, veck, vecn,
-                             bias, act);
-        }
-        return hipGetLastError() == hipSuccess ? PG_OK : PG_ELAUNCH;
-    }
-    float* slabs = (float*)ws;
-    {
-        TimedLaunch timed(st);
-        if (fast && algo == PG_ALGO_BF16 && in_bf) {
-            PG_DISPATCH_S2BH(true, p.t.id, grid, st, small, ld_small, P, slabs, g.Cb, p.out_elems, g, p.cps,
-                             (const float*)nullptr, 0, (int)small_bytes, (int)p_bytes, 0);
-        } else if (fast && algo == PG_ALGO_BF16) {
-            PG_DISPATCH_S2BH(false, p.t.id, grid, st, small, ld_small, P, slabs, g.Cb, p.out_elems, g, p.cps,
-                             (const float*)nullptr, 0, (int)small_bytes, (int)p_bytes, 0);
-        } else if (fast) {
-            PG_DISPATCH_TILE(k_s2b_fast, p.t.id, grid, st, small, ld_small, P, slabs, g.Cb, p.out_elems, g, p.cps,
-                             (const float*)nullptr, 0, (int)small_bytes, (int)p_bytes);
-        } else {
-            PG_DISPATCH_TILE(k_small2big, p.t.id, grid, st, small, ld_small, P, slabs, g.Cb, p.out_elems, g, p.cps, veck,
-                             vecn, (const float*)nullptr, 0);
-        }
-    }
-    if (hipGetLastError() != hipSuccess) return PG_ELAUNCH;
-    return launch_reduce(slabs, p.out_elems, p.split, big, ld_big, (long)g.N * g.Hb * g.Wb, g.Cb, bias, act, st, out_bf);
-}
-
-int pg_conv4x4_small2big(const float* small, int ld_small, const float* P, const float* bias, float* big,
-                         int ld_big, const pg_conv_geom* gg, int act, int algo, void* ws, size_t ws_bytes,
-                         void* stream) {
-    return s2b_impl(small, ld_small, P, bias, big, ld_big, gg, act, algo, ws, ws_bytes, stream, nullptr);
-}
-
-int pg_conv4x4_small2big_x(const float* small, int ld_small, const float* P, const float* bias, float* big,
-                           int ld_big, const pg_conv_geom* gg, int act, int algo, void* ws, size_t ws_bytes,
-                           void* stream, const pg_conv_extras* x) {
-    return s2b_impl(small, ld_small, P, bias, big, ld_big, gg, act, algo, ws, ws_bytes, stream, x);
-}
-
-size_t pg_conv_u_bytes(const pg_conv_geom* gg, int op, int algo, size_t ws_bytes) {
-    if (!geom_ok(gg) || (op != 0 && op != 1)) return 0;
-    const Geom g = to_geom(gg);
-    const Tune tune = tune_of(algo);
-    if (bf16x_ok(g, op, algo, tune)) return pg_bf16x_w_bytes(g.Ca, g.Cb);
-    if ((algo & PG_ALGO_MASK) != PG_ALGO_AUTO) return 0;
-    if (op == 0) {
-        if (wino_b2s_ok(g, tune) && ws_bytes >= pg_wino_ws_bytes(g.N, g.Hs, g.Ws, g.Cb, g.Ca, tune.mo1))
-            return pg_wino_u_bytes(g.N, g.Hs, g.Ws, g.Cb, g.Ca, tune.mo1);
-        if (wino2_b2s_ok(g, tune) && ws_bytes >= pg_wino2_ws_bytes(g.N, g.Hs, g.Ws, g.Ca, g.Cb)) return pg_wino2_u_bytes(g.Ca, g.Cb);
-        return 0;
-    }
-    if (wino_s2b_ok(g, tune) && ws_bytes >= pg_wino_ws_bytes(g.N, g.Hb, g.Wb, g.Ca, g.Cb, tune.mo1))
-        return pg_wino_u_bytes(g.N, g.Hb, g.Wb, g.Ca, g.Cb, tune.mo1);
-    if (wino2_s2b_ok(g, tune) && ws_bytes >= pg_wino2c_ws_bytes(g.N, g.Hb, g.Wb, g.Ca, g.Cb)) return pg_wino2_u_bytes(g.Ca, g.Cb);
+// kept V: where the forward call and the weight gradient of the layer both take a Winograd path of the same family
+size_t pg_conv_v_bytes(const pg_conv_geom* g, int algo, size_t ws_bytes) {
+    ConvPlan f, w;
+    if (!query_plan(g, 0, algo, ws_bytes, OFFER_V, &f) || f.rc != PG_OK || !query_plan(g, 2, algo, ws_bytes, 0, &w)) return 0;
+    if (f.path == Path::Wino1 && w.path == Path::WinoWgrad) return pg_wino_wgrad_v_bytes(g->N, g->Hs, g->Ws, g->Ca, g->Cb, tune_of(algo).mo1);
+    if (f.path == Path::Wino2 && w.path == Path::Wino2Wgrad) return pg_wino2_v_bytes(g->N, g->Hs, g->Ws, g->Cb);
     return 0;
 }
 
@@ -4345,32 +4113,16 @@ int pg_conv_prep_batch(int n, const pg_conv_prep_item* items, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     std::vector<pg_wino_prep> wv;
     std::vector<pg_bf16x_pack_item> bv;
-    for (int i = 0; i < n; ++i) {      // mirrors pg_conv_u_bytes / the dispatch of b2s_impl and s2b_impl
+    for (int i = 0; i < n; ++i) {
         const pg_conv_prep_item& it = items[i];
-        if (!geom_ok(&it.g) || (it.op != 0 && it.op != 1) || !it.P || !it.u || !aligned16(it.P) || !aligned16(it.u)) return PG_EINVAL;
-        const Geom g = to_geom(&it.g);
-        const Tune tune = tune_of(it.algo);
-        const int op = it.op;
-        if ((it.algo & PG_ALGO_MASK) == PG_ALGO_AUTO) {
-            if (op == 0 && wino_b2s_ok(g, tune) && it.ws_bytes >= pg_wino_ws_bytes(g.N, g.Hs, g.Ws, g.Cb, g.Ca, tune.mo1))
-                wv.push_back(pg_wino_prep{it.P, (float*)it.u, g.Ca, g.Cb, 0, pg_wino_mo(g.N, g.Hs, g.Ws, g.Cb, g.Ca, tune.mo1), 0});
-            else if (op == 0 && wino2_b2s_ok(g, tune) && it.ws_bytes >= pg_wino2_ws_bytes(g.N, g.Hs, g.Ws, g.Ca, g.Cb))
-                wv.push_back(pg_wino_prep{it.P, (float*)it.u, g.Ca, g.Cb, 1, 0, 0});
-            else if (op == 1 && wino_s2b_ok(g, tune) && it.ws_bytes >= pg_wino_ws_bytes(g.N, g.Hb, g.Wb, g.Ca, g.Cb, tune.mo1))
-                wv.push_back(pg_wino_prep{it.P, (float*)it.u, g.Cb, g.Ca, 0, pg_wino_mo(g.N, g.Hb, g.Wb, g.Ca, g.Cb, tune.mo1), 1});
-            else if (op == 1 && wino2_s2b_ok(g, tune) && it.ws_bytes >= pg_wino2c_ws_bytes(g.N, g.Hb, g.Wb, g.Ca, g.Cb))
-                wv.push_back(pg_wino_prep{it.P, (float*)it.u, g.Ca, g.Cb, 2, 0, 0});
-            else
-                return PG_EINVAL;
-        } else if (bf16x_ok(g, op, it.algo, tune)) {
-            // big -> small: [tap][a][b] (8-channel-pixel form for a few-channel big); small -> big: the same pack (transposed staging in
-            // the kernel) unless the ring-staged variant is pinned (bf16x_run)
-            const bool own = g.Cb > 8 && pg_bf16x_plan_of(op, g.N, g.Hb, g.Wb, g.Hs, g.Ws, g.Ca, g.Cb, g.s, tune.bf16ring).win;
-            const int dir = own ? 4 + op : (op == 0) ? (g.Cb <= 8 ? 2 : 0) : (tune.bf16ring > 0 ? 1 : 0);
-            bv.push_back(pg_bf16x_pack_item{it.P, it.u, g.Ca, g.Cb, dir});
-        } else {
+        ConvPlan p;
+        if ((it.op != 0 && it.op != 1) || !it.P || !it.u || !aligned16(it.P) || !aligned16(it.u) ||
+            !query_plan(&it.g, it.op, it.algo, it.ws_bytes, OFFER_U, &p) || p.rc != PG_OK || !p.u_bytes)
             return PG_EINVAL;
-        }
+        const int Ca = it.g.Ca, Cb = it.g.Cb;
+        if (p.path == Path::Wino1) wv.push_back(it.op == 0 ? pg_wino_prep{it.P, (float*)it.u, Ca, Cb, 0, p.mo, 0} : pg_wino_prep{it.P, (float*)it.u, Cb, Ca, 0, p.mo, 1});
+        else if (p.path == Path::Wino2) wv.push_back(pg_wino_prep{it.P, (float*)it.u, Ca, Cb, it.op == 0 ? 1 : 2, 0, 0});
+        else bv.push_back(pg_bf16x_pack_item{it.P, it.u, Ca, Cb, bf16x_pack_dir(p, tune_of(it.algo).bf16ring)});
     }
     for (size_t o = 0; o < wv.size(); o += PG_WINO_PREP_MAX) {
         const int rc = pg_wino_prep_batch((int)std::min<size_t>(PG_WINO_PREP_MAX, wv.size() - o), wv.data() + o, st);
@@ -4383,59 +4135,483 @@ int pg_conv_prep_batch(int n, const pg_conv_prep_item* items, void* stream) {
     return PG_OK;
 }
 
-int pg_conv_mul_ok(const pg_conv_geom* gg, int algo, size_t ws_bytes) {
-    if (!geom_ok(gg)) return 0;
-    const Geom g = to_geom(gg);
-    const Tune tune = tune_of(algo);
-    // mirrors the dispatch of s2b_impl for 16-byte-aligned tensors
-    if (s2b_ca1_ok(g, algo)) return 1;
-    if ((algo & PG_ALGO_MASK) == PG_ALGO_AUTO) {
-        if (wino_s2b_ok(g, tune) && ws_bytes >= pg_wino_ws_bytes(g.N, g.Hb, g.Wb, g.Ca, g.Cb, tune.mo1)) return 1;
-        if (wino2_s2b_ok(g, tune) && ws_bytes >= pg_wino2c_ws_bytes(g.N, g.Hb, g.Wb, g.Ca, g.Cb)) return 1;
-        return 0;
+}  // extern "C"
+
+namespace {
+
+// ---- one launch function per path ----
+struct Call {       // a planned call
+    ConvPlan p;
+    Views v;
+    Geom g;
+    int algo, io;   // PG_ALGO_*, PG_IO_* bits
+    Tune tune;
+    size_t ws_bytes;
+    hipStream_t st;
+};
+inline int launched() { return hipGetLastError() == hipSuccess ? PG_OK : PG_ELAUNCH; }
+inline pg_epi_mul mul_of(const Call& c) { return pg_epi_mul{c.v.x->mul_t, c.v.x->mul_ld, c.v.x->mul_act}; }
+
+// Path::Bf16x (dir 0: big -> small, 1: small -> big): pack (or reuse) the weights, main kernel, split-K reduce
+int launch_bf16x(const Call& c, int dir) {
+    const Geom& g = c.g;
+    const ConvPlan& p = c.p;
+    const pg_conv_extras& x = *c.v.x;
+    const void* in = dir == 0 ? c.v.big : c.v.small;
+    void* out = const_cast<void*>(dir == 0 ? c.v.small : c.v.big);
+    const int ld_in = dir == 0 ? c.v.ld_big : c.v.ld_small, ld_out = dir == 0 ? c.v.ld_small : c.v.ld_big;
+    const bool out_bf = c.io & (dir == 0 ? PG_IO_SMALL_BF16 : PG_IO_BIG_BF16);
+    const int Cin = p.xdir == 0 ? g.Cb : p.xdir == 2 ? 8 : g.Ca, Cout = dir == 1 ? g.Cb : g.Ca;
+    const long in_pix = (long)g.N * (dir == 0 ? g.Hb * g.Wb : g.Hs * g.Ws), out_pix = (long)g.N * (dir == 0 ? g.Hs * g.Ws : g.Hb * g.Wb);
+    const long in_bytes = tensor_bytes(in_pix, ld_in, Cin, true);
+    void* W = x.u_cache ? (void*)x.u_cache : c.v.ws;
+    float* slabs = (float*)((char*)c.v.ws + (x.u_cache ? 0 : pg_bf16x_w_bytes(g.Ca, g.Cb)));
+    const int pack = bf16x_pack_dir(p, c.tune.bf16ring), bt = (p.xdir == 1 && pack == 0) ? 1 : 0;
+    if (!(x.u_cache && x.u_valid)) {
+        int rc = pg_bf16x_pack(c.v.P, W, g.Ca, g.Cb, pack, c.st);
+        if (rc != PG_OK) return rc;
     }
-    if (bf16x_s2b_tapn_ok(g, algo, tune) && ws_bytes >= bf16x_s2b_tapn_ws(g)) return 0;
-    return bf16x_ok(g, 1, algo, tune) && ws_bytes >= bf16x_ws(g, 1) ? 1 : 0;
+    const pg_epi_mul mul = mul_of(c);
+    int rc;
+    {
+        TimedLaunch timed(c.st);
+        if (p.split == 1)
+            rc = pg_bf16x_conv(p.xdir, in, ld_in, in_bytes, W, out, ld_out, 0L, g.N, g.Hb, g.Wb, g.Hs, g.Ws, g.Ca, g.Cb, g.s, &p.bx, c.v.bias, c.v.act,
+                               out_bf ? 1 : 0, c.st, mul, x.part, x.part ? p.stats_chunks : 0, bt);
+        else
+            rc = pg_bf16x_conv(p.xdir, in, ld_in, in_bytes, W, slabs, Cout, p.bx.out_elems, g.N, g.Hb, g.Wb, g.Hs, g.Ws, g.Ca, g.Cb, g.s, &p.bx,
+                               nullptr, 0, 0, c.st, pg_epi_mul{nullptr, 0, 0}, nullptr, 0, bt);
+    }
+    if (rc != PG_OK || p.split == 1) return rc;
+    return launch_reduce(slabs, p.bx.out_elems, p.split, (float*)out, ld_out, out_pix, Cout, c.v.bias, c.v.act, c.st, out_bf ? 1 : 0, mul);
 }
 
-size_t pg_conv_v_bytes(const pg_conv_geom* gg, int algo, size_t ws_bytes) {
-    if (!geom_ok(gg) || (algo & PG_ALGO_MASK) != PG_ALGO_AUTO) return 0;
-    const Geom g = to_geom(gg);
-    const Tune tune = tune_of(algo);
-    // stride-1 layer: forward on F(3x3,4x4), weight gradient on F(4x4,3x3) -- one transformed input
-    if (wino_b2s_ok(g, tune) && wino_wgrad_ok(g, tune) && ws_bytes >= pg_wino_ws_bytes(g.N, g.Hs, g.Ws, g.Cb, g.Ca, tune.mo1) &&
-        ws_bytes >= (((size_t)COLSUM_CHUNKS * g.Ca * sizeof(float) + 255) & ~(size_t)255) + pg_wino_wgrad_ws_bytes(g.N, g.Hs, g.Ws, g.Ca, g.Cb))
-        return pg_wino_wgrad_v_bytes(g.N, g.Hs, g.Ws, g.Ca, g.Cb, tune.mo1);
-    if (pg_wino2_mo() != 3) return 0;
-    const size_t colsum = ((size_t)COLSUM_CHUNKS * g.Ca * sizeof(float) + 255) & ~(size_t)255;
-    if (wino2_b2s_ok(g, tune) && ws_bytes >= pg_wino2_ws_bytes(g.N, g.Hs, g.Ws, g.Ca, g.Cb) && wino2_wgrad_ok(g, tune) &&
-        ws_bytes >= colsum + pg_wino2_wgrad_ws_bytes(g.N, g.Hs, g.Ws, g.Ca, g.Cb))
-        return pg_wino2_v_bytes(g.N, g.Hs, g.Ws, g.Cb);
-    return 0;
+// Path::Wino1 (ops 0 / 1): F(2x2,4x4) / F(3x3,4x4) of a stride-1 layer; (Hi, Wi, Ci) the input side, (Ho, Wo, Co) the output side
+int launch_wino1(const Call& c, int op) {
+    const Geom& g = c.g;
+    const pg_conv_extras& x = *c.v.x;
+    const int mo1 = c.tune.mo1;
+    const float* in = (const float*)(op == 0 ? c.v.big : c.v.small);
+    float* out = (float*)const_cast<void*>(op == 0 ? c.v.small : c.v.big);
+    const int ld_in = op == 0 ? c.v.ld_big : c.v.ld_small, ld_out = op == 0 ? c.v.ld_small : c.v.ld_big;
+    const int Hi = op == 0 ? g.Hb : g.Hs, Wi = op == 0 ? g.Wb : g.Ws, Ci = op == 0 ? g.Cb : g.Ca;
+    const int Ho = op == 0 ? g.Hs : g.Hb, Wo = op == 0 ? g.Ws : g.Wb, Co = op == 0 ? g.Ca : g.Cb;
+    const pg_epi_mul mul = op == 0 ? pg_epi_mul{nullptr, 0, 0} : mul_of(c);
+    int rc = op == 0 ? pg_wino_prepare(in, ld_in, c.v.P, 0, g.N, Hi, Wi, Ci, Ho, Wo, Co, 1, c.v.ws, c.st, mo1, x.u_cache, x.u_valid, x.v_keep)
+                     : pg_wino_prepare(in, ld_in, c.v.P, 1, g.N, Hi, Wi, Ci, Ho, Wo, Co, 2, c.v.ws, c.st, mo1, x.u_cache, x.u_valid);
+    if (rc != PG_OK) return rc;
+    const int nsl = pg_wino_gemm_rows(g.N, Ho, Wo, Ci, Co, mo1, c.tune.dma, out, ld_out, c.v.bias, mul) ? 1 : pg_wino_gemm_slices(g.N, Ho, Wo, Ci, Co, mo1);
+    {
+        TimedLaunch timed(c.st);
+        rc = pg_wino_gemm(c.v.bias, out, ld_out, g.N, Ci, Ho, Wo, Co, c.v.act, c.v.ws, c.st, mo1, c.tune.dma, x.u_cache, mul, op == 0 ? x.v_keep : nullptr,
+                          c.tune.s3r);
+    }
+    if (rc != PG_OK || nsl == 1) return rc;
+    const long pix = (long)g.N * Ho * Wo;
+    return launch_reduce(pg_wino_gemm_slabs(c.v.ws, g.N, Ho, Wo, Ci, Co, mo1), pix * Co, nsl, out, ld_out, pix, Co, c.v.bias, c.v.act, c.st, 0, mul);
 }
 
-int pg_conv_stats_chunks(const pg_conv_geom* gg, int op, int algo, size_t ws_bytes) {
-    if (!geom_ok(gg) || (op != 0 && op != 1)) return 0;
-    const Geom g = to_geom(gg);
-    const Tune tune = tune_of(algo);
-    if ((algo & PG_IO_MASK) == PG_IO_MASK && bf16x_ok(g, op, algo, tune) && !(op == 0 && g.Cb <= 8) && ws_bytes >= bf16x_ws(g, op)) {
-        pg_bf16x_plan bp = pg_bf16x_plan_of(op, g.N, g.Hb, g.Wb, g.Hs, g.Ws, g.Ca, g.Cb, g.s, tune.bf16ring);
-        pg_bf16x_clamp(&bp, ws_bytes - pg_bf16x_w_bytes(g.Ca, g.Cb));
-        return pg_bf16x_stats_chunks(op, &bp, g.N, g.Hb, g.Wb, g.Hs, g.Ws);
+// Path::Wino2 (ops 0 / 1): polyphase Winograd of a stride-2 layer (times its own main GEMM)
+int launch_wino2(const Call& c, int op) {
+    const Geom& g = c.g;
+    const pg_conv_extras& x = *c.v.x;
+    hipEvent_t e0 = t_ev0, e1 = t_ev1;
+    t_ev0 = nullptr;
+    t_ev1 = nullptr;
+    if (op == 0)
+        return pg_wino2_b2s((const float*)c.v.big, c.v.ld_big, c.v.P, c.v.bias, (float*)const_cast<void*>(c.v.small), c.v.ld_small, g.N, g.Hb, g.Wb, g.Hs,
+                            g.Ws, g.Ca, g.Cb, c.v.act, c.v.ws, c.st, e0, e1, nullptr, x.part, x.v_keep, x.u_cache, x.u_valid, c.tune.s3);
+    return pg_wino2_s2b((const float*)c.v.small, c.v.ld_small, c.v.P, c.v.bias, (float*)const_cast<void*>(c.v.big), c.v.ld_big, g.N, g.Hb, g.Wb, g.Hs, g.Ws,
+                        g.Ca, g.Cb, c.v.act, c.v.ws, c.st, e0, e1, x.part, x.u_cache, x.u_valid, mul_of(c), c.tune.s3);
+}
+
+// Path::TapnRowGemm (ops 0 / 1): D[input pixel][(tap, output channel)] = in . W (row GEMM over the pixels) into the workspace; the
+// caller gathers (op 0) / scatters (op 1) the 16 taps
+int launch_row_gemm(const Call& c, const float* in, int ld_in, const float* W, float* D, long M, int Hi, int Wi, int Cin, int Nc) {
+    const Tile& t = c.p.tile;
+    Geom g1{c.g.N, Hi, Wi, Hi, Wi, Nc, Cin, 1};
+    dim3 grid((unsigned)((M + t.bm - 1) / t.bm), (Nc + t.bn - 1) / t.bn, 1);
+    TimedLaunch timed(c.st);
+    for_tile(t.id, [&](auto tt) {
+        using T = decltype(tt);
+        hipLaunchKernelGGL((k_b2s_fast<PG_TILE(T), true>), grid, dim3(256), 0, c.st, in, ld_in, W, D, Nc, 0L, g1, Cin / KC, (const float*)nullptr, 0,
+                           (int)tensor_bytes(M, ld_in, Cin), (int)((long)Nc * Cin * 4));
+    });
+    return launched();
+}
+
+// Path::Gemm of ops 0 / 1: the implicit GEMM straight into the output, or split-K slabs + reduce
+int launch_gemm(const Call& c, int op) {
+    const Geom& g = c.g;
+    const ConvPlan& p = c.p;
+    const Plan& q = p.gemm;
+    hipStream_t st = c.st;
+    const float* in = (const float*)(op == 0 ? c.v.big : c.v.small);
+    float* out = (float*)const_cast<void*>(op == 0 ? c.v.small : c.v.big);
+    const int ld_in = op == 0 ? c.v.ld_big : c.v.ld_small, ld_out = op == 0 ? c.v.ld_small : c.v.ld_big, Cout = op == 0 ? g.Ca : g.Cb;
+    const long in_pix = (long)g.N * (op == 0 ? g.Hb * g.Wb : g.Hs * g.Ws), out_pix = (long)g.N * (op == 0 ? g.Hs * g.Ws : g.Hb * g.Wb);
+    const bool in_bf = c.io & (op == 0 ? PG_IO_BIG_BF16 : PG_IO_SMALL_BF16), out_bf = c.io & (op == 0 ? PG_IO_SMALL_BF16 : PG_IO_BIG_BF16);
+    const bool split = q.split > 1;
+    float* dst = split ? (float*)c.v.ws : out;
+    const int ld_dst = split ? Cout : ld_out, act = split ? 0 : c.v.act, obf = split ? 0 : (int)out_bf;
+    const long stride = split ? q.out_elems : 0L;
+    const float *P = c.v.P, *bias = split ? nullptr : c.v.bias;
+    const int in_bytes = (int)tensor_bytes(in_pix, ld_in, op == 0 ? g.Cb : g.Ca, in_bf), p_bytes = (int)(16L * g.Ca * g.Cb * 4);
+    dim3 grid(q.tiles_m, q.tiles_n, q.ncls * q.split);
+    {
+        TimedLaunch timed(st);
+        for_tile(q.t.id, [&](auto tt) {
+            using T = decltype(tt);
+            if (p.fast && c.algo == PG_ALGO_BF16)
+                for_bool(in_bf, [&](auto hin) {
+                    constexpr bool HIN = decltype(hin)::value;
+                    if (op == 0)
+                        hipLaunchKernelGGL((k_b2s_bf16<PG_TILE(T), false, HIN>), grid, dim3(256), 0, st, in, ld_in, P, dst, ld_dst, stride, g, q.cps, bias, act,
+                                           in_bytes, p_bytes, obf);
+                    else
+                        hipLaunchKernelGGL((k_s2b_bf16<PG_TILE(T), HIN>), grid, dim3(256), 0, st, in, ld_in, P, dst, ld_dst, stride, g, q.cps, bias, act, in_bytes,
+                                           p_bytes, obf);
+                });
+            else if (p.fast && op == 0)
+                hipLaunchKernelGGL((k_b2s_fast<PG_TILE(T), false>), grid, dim3(256), 0, st, in, ld_in, P, dst, ld_dst, stride, g, q.cps, bias, act,
+                                   in_bytes, p_bytes);
+            else if (p.fast)
+                hipLaunchKernelGGL((k_s2b_fast<PG_TILE(T)>), grid, dim3(256), 0, st, in, ld_in, P, dst, ld_dst, stride, g, q.cps, bias, act, in_bytes,
+                                   p_bytes);
+            else if (op == 0)
+                hipLaunchKernelGGL((k_big2small<PG_TILE(T)>), grid, dim3(256), 0, st, in, ld_in, P, dst, ld_dst, stride, g, q.cps, p.veck, bias, act);
+            else
+                hipLaunchKernelGGL((k_small2big<PG_TILE(T)>), grid, dim3(256), 0, st, in, ld_in, P, dst, ld_dst, stride, g, q.cps, p.veck, p.vecn, bias,
+                                   act);
+        });
     }
-    if ((algo & PG_ALGO_MASK) != PG_ALGO_AUTO) return 0;
-    // mirrors the dispatch of b2s_impl / s2b_impl for 16-byte-aligned tensors: the stride-1 Winograd path comes first
-    if (op == 0) {
-        if (wino_b2s_ok(g, tune) && ws_bytes >= pg_wino_ws_bytes(g.N, g.Hs, g.Ws, g.Cb, g.Ca, tune.mo1)) return 0;
-        if (wino2_b2s_ok(g, tune) && ws_bytes >= pg_wino2_ws_bytes(g.N, g.Hs, g.Ws, g.Ca, g.Cb))
-            return pg_wino2_b2s_stats_chunks(g.N, g.Hs, g.Ws, g.Ca);
-        if (tapk_enabled() && tapkp_enabled()) return tapkp_stats_chunks(g);      // image-facing layer (enc0): k_b2s_tapkp<.., STATS>
-        return 0;
+    if (hipGetLastError() != hipSuccess) return PG_ELAUNCH;
+    if (!split) return PG_OK;
+    return launch_reduce(dst, q.out_elems, q.split, out, ld_out, out_pix, Cout, c.v.bias, c.v.act, st, out_bf);
+}
+
+int launch_b2s(const Call& c) {
+    const Geom& g = c.g;
+    const ConvPlan& p = c.p;
+    const pg_conv_extras& x = *c.v.x;
+    hipStream_t st = c.st;
+    const float* big = (const float*)c.v.big;
+    float* small = (float*)const_cast<void*>(c.v.small);
+    const float *P = c.v.P, *bias = c.v.bias;
+    const int ld_big = c.v.ld_big, ld_small = c.v.ld_small, act = c.v.act;
+    const long pix = (long)g.N * g.Hs * g.Ws, big_pix = (long)g.N * g.Hb * g.Wb;
+    switch (p.path) {
+        case Path::Direct:
+            hipLaunchKernelGGL(k_big2small_direct, dim3((int)std::min<long>((pix * g.Ca + 255) / 256, 65536)), dim3(256), 0, st, big, ld_big, P, bias, small,
+                               ld_small, g, act);
+            return launched();
+        case Path::Wino1: return launch_wino1(c, 0);
+        case Path::Wino2: return launch_wino2(c, 0);
+        case Path::Bf16x: return launch_bf16x(c, 0);
+        case Path::TapnRowGemm: {
+            float* D = (float*)c.v.ws;
+            int rc = launch_row_gemm(c, big, ld_big, P, D, big_pix, g.Hb, g.Wb, g.Cb, 16 * g.Ca);
+            if (rc != PG_OK) return rc;
+            hipLaunchKernelGGL(k_gather_big2small, dim3((int)std::min<long>((pix * g.Ca + 255) / 256, 8192)), dim3(256), 0, st, D, bias, small, ld_small, g,
+                               act);
+            return launched();
+        }
+        case Path::Tapkp: {
+            // persistent form: 2 workgroups per CU (two LDS buffers of 9 .. 35 KB, two accumulator sets), each walking tiles blockIdx.x, + gridDim.x, ...
+            const int ntiles = (int)((pix + 127) / 128), gy = (g.Ca + 63) / 64;
+            static const int pwg = pg_exp_env("PATCHGAN_TAPKP_WG") ? atoi(pg_exp_env("PATCHGAN_TAPKP_WG")) : 512;
+            const bool wide = g.Cb == 4 || ((g.Cb == 3) && (ld_big % 4 == 0) && (ld_big >= 4) && aligned16(big));
+            // with the statistics epilogue: one workgroup per CU (88 .. 104 KB of LDS); act == none, no bias, whole tiles per sample (planner)
+            dim3 pgrid((unsigned)std::min<long>(ntiles, std::max<long>(1, (x.part ? 256 : pwg) / (long)gy)), gy, 1);
+            const int big_b = (int)tensor_bytes(big_pix, ld_big, g.Cb), out_b = (int)tensor_bytes(pix, ld_small, g.Ca);
+            TimedLaunch timed(st);
+            auto go = [&](auto cb, auto wd) {
+                constexpr int CB = decltype(cb)::value;
+                constexpr bool WD = decltype(wd)::value;
+                if (x.part)
+                    hipLaunchKernelGGL((k_b2s_tapkp<CB, 0, WD, true>), pgrid, dim3(256), 0, st, big, ld_big, P, small, ld_small, g, bias, big_b, out_b, ntiles,
+                                       x.part);
+                else if (act == PG_ACT_LEAKY)
+                    hipLaunchKernelGGL((k_b2s_tapkp<CB, 1, WD>), pgrid, dim3(256), 0, st, big, ld_big, P, small, ld_small, g, bias, big_b, out_b, ntiles);
+                else
+                    hipLaunchKernelGGL((k_b2s_tapkp<CB, 0, WD>), pgrid, dim3(256), 0, st, big, ld_big, P, small, ld_small, g, bias, big_b, out_b, ntiles);
+            };
+            using std::integral_constant;
+            switch (g.Cb) {
+                case 1: go(integral_constant<int, 1>{}, std::false_type{}); break;
+                case 2: go(integral_constant<int, 2>{}, std::false_type{}); break;
+                case 3: wide ? go(integral_constant<int, 3>{}, std::true_type{}) : go(integral_constant<int, 3>{}, std::false_type{}); break;
+                default: go(integral_constant<int, 4>{}, std::true_type{}); break;
+            }
+            return launched();
+        }
+        case Path::Tapk: {
+            const int tmk = g.Cb <= 4 ? 128 : 64, vec4 = p.vec4, vec_out = p.vec_out;
+            dim3 grid((unsigned)((pix + tmk - 1) / tmk), (g.Ca + 63) / 64, 1);
+            TimedLaunch timed(st);
+            switch (g.Cb) {
+                case 1: hipLaunchKernelGGL(k_b2s_tapk<1>, grid, dim3(256), 0, st, big, ld_big, P, small, ld_small, g, bias, act, vec4, vec_out); break;
+                case 2: hipLaunchKernelGGL(k_b2s_tapk<2>, grid, dim3(256), 0, st, big, ld_big, P, small, ld_small, g, bias, act, vec4, vec_out); break;
+                case 3: hipLaunchKernelGGL(k_b2s_tapk<3>, grid, dim3(256), 0, st, big, ld_big, P, small, ld_small, g, bias, act, vec4, vec_out); break;
+                case 5: hipLaunchKernelGGL((k_b2s_tapk<5, 1>), grid, dim3(256), 0, st, big, ld_big, P, small, ld_small, g, bias, act, 0, vec_out); break;
+                case 6: hipLaunchKernelGGL((k_b2s_tapk<6, 1>), grid, dim3(256), 0, st, big, ld_big, P, small, ld_small, g, bias, act, 0, vec_out); break;
+                case 7: hipLaunchKernelGGL((k_b2s_tapk<7, 1>), grid, dim3(256), 0, st, big, ld_big, P, small, ld_small, g, bias, act, 0, vec_out); break;
+                case 8: hipLaunchKernelGGL((k_b2s_tapk<8, 1>), grid, dim3(256), 0, st, big, ld_big, P, small, ld_small, g, bias, act, 0, vec_out); break;
+                default: hipLaunchKernelGGL(k_b2s_tapk<4>, grid, dim3(256), 0, st, big, ld_big, P, small, ld_small, g, bias, act, vec4, vec_out); break;
+            }
+            return launched();
+        }
+        default: break;
     }
-    if (wino_s2b_ok(g, tune) && ws_bytes >= pg_wino_ws_bytes(g.N, g.Hb, g.Wb, g.Ca, g.Cb, tune.mo1)) return 0;
-    if (wino2_s2b_ok(g, tune) && ws_bytes >= pg_wino2c_ws_bytes(g.N, g.Hb, g.Wb, g.Ca, g.Cb))
-        return pg_wino2_s2b_stats_chunks(g.N, g.Hb, g.Wb, g.Cb);
-    return 0;
+    return launch_gemm(c, 0);
+}
+
+// the col2im half of the taps-folded-into-N small -> big paths
+int launch_col2im(const float* D, const float* bias, float* big, int ld_big, const Geom& g, int act, hipStream_t st) {
+    const size_t lds = (size_t)(CT_H + 2) * (CT_W + 2) * 16 * g.Cb * sizeof(float);
+    if (g.s == 2) {                    // (a D row is 16 * Cb floats: always whole float4s)
+        if (lds <= 64 * 1024 && aligned16(D)) {
+            const int tiles_h = (g.Hs + CT_H) / CT_H, tiles_w = (g.Ws + CT_W) / CT_W;      // big rows reach one small row past Hs - 1
+            hipLaunchKernelGGL(k_col2im_s2_lds, dim3((unsigned)(g.N * tiles_h * tiles_w)), dim3(256), lds, st, D, bias, big, ld_big, g, act,
+                               tiles_h, tiles_w);
+            return launched();
+        }
+    }
+    const long total = (long)g.N * g.Hb * g.Wb * g.Cb;
+    hipLaunchKernelGGL(k_col2im_small2big, dim3((int)std::min<long>((total + 255) / 256, 8192)), dim3(256), 0, st, D, bias, big, ld_big, g, act);
+    return launched();
+}
+
+int launch_s2b(const Call& c) {
+    const Geom& g = c.g;
+    const ConvPlan& p = c.p;
+    hipStream_t st = c.st;
+    const float* small = (const float*)c.v.small;
+    float* big = (float*)const_cast<void*>(c.v.big);
+    const float *P = c.v.P, *bias = c.v.bias;
+    const int ld_big = c.v.ld_big, ld_small = c.v.ld_small, act = c.v.act;
+    const long pix = (long)g.N * g.Hs * g.Ws, big_pix = (long)g.N * g.Hb * g.Wb;
+    const bool out_bf = c.io & PG_IO_BIG_BF16;
+    switch (p.path) {
+        case Path::Direct:
+            hipLaunchKernelGGL(k_small2big_direct, dim3((int)std::min<long>((big_pix * g.Cb + 255) / 256, 65536)), dim3(256), 0, st, small, ld_small, P, bias,
+                               big, ld_big, g, act);
+            return launched();
+        case Path::Ca1: {
+            const pg_epi_mul mul = mul_of(c);
+            TimedLaunch timed(st);
+            if (p.ca1_s1) {
+                // per-sample form: ~1536 workgroups in all, whole pixel rows of the workgroup (256 / (Cb / 4) pixels per trip)
+                const int npr = 256 / (g.Cb / 4), hwb = g.Hb * g.Wb;
+                const long per = std::max<long>(1, 1536 / g.N);
+                static const int minpix = pg_exp_env("PATCHGAN_CA1S1_MINPIX") ? atoi(pg_exp_env("PATCHGAN_CA1S1_MINPIX")) : 0;
+                const int ppb1 = std::max(minpix, (int)(((hwb + per - 1) / per + npr - 1) / npr * npr));
+                hipLaunchKernelGGL(k_s2b_ca1_s1, dim3((unsigned)((hwb + ppb1 - 1) / ppb1), g.N), dim3(256), (size_t)(g.Hs + 4) * (g.Ws + 4) * sizeof(float), st,
+                                   small, ld_small, P, bias, big, ld_big, g, act, out_bf ? 1 : 0, mul, ppb1);
+                return launched();
+            }
+            // pixels per workgroup: ~1500 workgroups, whole trips of 2 pixels per thread row (256 / (Cb / 4) pixel rows per workgroup)
+            const int trip = 2 * (256 / (g.Cb / 4));
+            static const int ca1_wgs = pg_exp_env("PATCHGAN_CA1_WGS") ? atoi(pg_exp_env("PATCHGAN_CA1_WGS")) : 1536;
+            const int ppb = (int)std::max<long>(trip, ((big_pix / ca1_wgs + trip - 1) / trip) * trip);
+            hipLaunchKernelGGL(k_s2b_ca1, dim3((unsigned)((big_pix + ppb - 1) / ppb)), dim3(256), 0, st, small, ld_small, P, bias, big, ld_big, g, act,
+                               out_bf ? 1 : 0, mul, ppb);
+            return launched();
+        }
+        case Path::Wino1: return launch_wino1(c, 1);
+        case Path::Wino2: return launch_wino2(c, 1);
+        case Path::TapnfBf:
+        case Path::Tapnf: {
+            const bool bf = p.path == Path::TapnfBf;
+            return launch_tapnf(bf, small, ld_small, P, bias, big, ld_big, g, act, tensor_bytes(pix, ld_small, g.Ca, bf), tensor_bytes(big_pix, ld_big, g.Cb),
+                                st);
+        }
+        case Path::Bf16xTapn: {
+            const int Nc = 16 * g.Cb;
+            float* D = (float*)((char*)c.v.ws + pg_bf16x_w_bytes(g.Ca, g.Cb));
+            int rc = pg_bf16x_pack(P, c.v.ws, g.Ca, g.Cb, 1, st);
+            if (rc != PG_OK) return rc;
+            {
+                TimedLaunch timed(st);
+                rc = pg_bf16x_conv(3, small, ld_small, tensor_bytes(pix, ld_small, g.Ca, true), c.v.ws, D, Nc, 0L, g.N, g.Hb, g.Wb, g.Hs, g.Ws, g.Ca, Nc, g.s,
+                                   &p.bx, nullptr, 0, 0, st);
+            }
+            if (rc != PG_OK) return rc;
+            return launch_col2im(D, bias, big, ld_big, g, act, st);
+        }
+        case Path::Bf16x: return launch_bf16x(c, 1);
+        case Path::TapnRowGemm: {
+            const int Nc = 16 * g.Cb;
+            float* Wp = (float*)c.v.ws;
+            float* D = Wp + (((size_t)Nc * g.Ca + 63) & ~(size_t)63);
+            const float* W = P;
+            if (g.Cb > 1) {
+                hipLaunchKernelGGL(k_pack_taps_b, dim3((Nc * g.Ca + 255) / 256), dim3(256), 0, st, P, Wp, g.Ca, g.Cb);
+                if (hipGetLastError() != hipSuccess) return PG_ELAUNCH;
+                W = Wp;
+            }
+            int rc = launch_row_gemm(c, small, ld_small, W, D, pix, g.Hs, g.Ws, g.Ca, Nc);
+            if (rc != PG_OK) return rc;
+            return launch_col2im(D, bias, big, ld_big, g, act, st);
+        }
+        default: break;
+    }
+    return launch_gemm(c, 1);
+}
+
+// the main kernel of the weight gradient (after the bias gradient's column sums); Views::P is dP
+int launch_wgrad(const Call& c) {
+    const Geom& g = c.g;
+    const ConvPlan& p = c.p;
+    hipStream_t st = c.st;
+    const float *small = (const float*)c.v.small, *big = (const float*)c.v.big;
+    float* dP = const_cast<float*>(c.v.P);
+    const int ld_big = c.v.ld_big, ld_small = c.v.ld_small;
+    const long Kp = (long)g.N * g.Hs * g.Ws, big_pix = (long)g.N * g.Hb * g.Wb, per = 16L * g.Ca * g.Cb;
+    float* rest = (float*)((char*)c.v.ws + p.reserved);
+    const bool in_bf = c.io != 0;
+    auto reduce = [&](const float* slabs, int n) { return launch_reduce(slabs, per, n, dP, g.Cb, 16L * g.Ca, g.Cb, nullptr, 0, st); };
+    switch (p.path) {
+        case Path::Direct: {
+            long smax = (long)((c.ws_bytes - p.reserved) / (sizeof(float) * (size_t)per));
+            int slices = (int)std::min<long>(std::min<long>(DIRECT_WGRAD_SLICES, smax), Kp);
+            if (slices < 1) slices = 1;
+            long pps = (Kp + slices - 1) / slices;
+            slices = (int)((Kp + pps - 1) / pps);
+            float* dst = slices == 1 ? dP : rest;
+            hipLaunchKernelGGL(k_wgrad_direct, dim3((int)((per + 255) / 256), slices), dim3(256), 0, st, small, ld_small, big, ld_big, dst, per, g, pps);
+            if (hipGetLastError() != hipSuccess) return PG_ELAUNCH;
+            return slices == 1 ? PG_OK : reduce(dst, slices);
+        }
+        case Path::WinoWgrad:
+        case Path::Wino2Wgrad: {
+            hipEvent_t e0 = t_ev0, e1 = t_ev1;
+            t_ev0 = nullptr;
+            t_ev1 = nullptr;
+            return (p.path == Path::WinoWgrad ? pg_wino_wgrad : pg_wino2_wgrad)(small, ld_small, big, ld_big, dP, g.N, g.Hb, g.Wb, g.Hs, g.Ws, g.Ca, g.Cb, rest,
+                                                                              st, e0, e1, c.v.x->v_pre, c.tune.s3w);
+        }
+        case Path::Bf16xWgrad: {
+            float* dst = p.split == 1 ? dP : rest;
+            int rc;
+            {
+                TimedLaunch timed(st);
+                rc = pg_bf16x_wgrad(small, ld_small, tensor_bytes(Kp, ld_small, g.Ca, true), big, ld_big, tensor_bytes(big_pix, ld_big, g.Cb > 8 ? g.Cb : 8, true),
+                                    dst, p.split == 1 ? 0L : p.bx.out_elems, g.N, g.Hb, g.Wb, g.Hs, g.Ws, g.Ca, g.Cb, g.s, &p.bx, st);
+            }
+            if (rc != PG_OK || p.split == 1) return rc;
+            return reduce(dst, p.split);
+        }
+        case Path::WgradTapnp: {
+            const int ntiles = (int)((Kp + 127) / 128), G = p.split;
+            const int small_b = (int)tensor_bytes(Kp, ld_small, g.Ca), big_b = (int)tensor_bytes(big_pix, ld_big, g.Cb);
+            const bool wide3 = (g.Cb == 3) && (ld_big % 4 == 0) && (ld_big >= 4) && aligned16(big);
+            {
+                TimedLaunch timed(st);
+                const dim3 grid(G, g.Cb <= 2 ? (g.Ca + 127) / 128 : (g.Ca + 63) / 64, 1);
+                auto go = [&](auto kernel) {
+                    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, small, ld_small, big, ld_big, rest, per, g, small_b, big_b, ntiles);
+                };
+                if (g.Cb == 1) go(k_wgrad_tapnp<1, false, 4>);
+                else if (g.Cb == 2) go(k_wgrad_tapnp<2, false, 4>);
+                else if (g.Cb == 4) go(k_wgrad_tapnp<4, true, 2>);
+                else if (wide3) go(k_wgrad_tapnp<3, true, 2>);
+                else go(k_wgrad_tapnp<3, false, 2>);
+            }
+            if (hipGetLastError() != hipSuccess) return PG_ELAUNCH;
+            return reduce(rest, G);
+        }
+        default: break;
+    }
+    // Path::Gemm (one GEMM per tap) / Path::WgradTapn (taps folded into N): into dP, or split-K slabs + reduce
+    const Plan& q = p.gemm;
+    float* dst = q.split == 1 ? dP : rest;
+    {
+        TimedLaunch timed(st);
+        if (p.path == Path::Gemm) {
+            dim3 grid(q.tiles_m * q.tiles_n, 16, q.split);
+            const int small_bytes = (int)tensor_bytes(Kp, ld_small, g.Ca, in_bf), big_bytes = (int)tensor_bytes(big_pix, ld_big, g.Cb, in_bf);
+            for_tile(q.t.id, [&](auto tt) {
+                using T = decltype(tt);
+                if (!p.fast)
+                    hipLaunchKernelGGL((k_wgrad<PG_TILE(T)>), grid, dim3(256), 0, st, small, ld_small, big, ld_big, dst, q.out_elems, g, q.cps, q.tiles_n, p.veck,
+                                       p.vecn);
+                else
+                    for_bool(p.pow2, [&](auto p2) {
+                        if (c.algo == PG_ALGO_BF16)
+                            for_bool(in_bf, [&](auto hin) {
+                                hipLaunchKernelGGL((k_wgrad_bf16<PG_TILE(T), decltype(p2)::value, decltype(hin)::value>), grid, dim3(256), 0, st, small, ld_small,
+                                                   big, ld_big, dst, q.out_elems, g, q.cps, q.tiles_n, small_bytes, big_bytes);
+                            });
+                        else
+                            hipLaunchKernelGGL((k_wgrad_fast<PG_TILE(T), decltype(p2)::value>), grid, dim3(256), 0, st, small, ld_small, big, ld_big, dst,
+                                               q.out_elems, g, q.cps, q.tiles_n, small_bytes, big_bytes);
+                    });
+            });
+        } else {
+            dim3 grid(q.tiles_m * q.tiles_n, 1, q.split);
+            const int vecy = (g.Cb == 4) && (ld_big % 4 == 0) && aligned16(big);
+            for_tile(q.t.id, [&](auto tt) {
+                using T = decltype(tt);
+                if (p.mode == 1)
+                    hipLaunchKernelGGL((k_wgrad_tapn<PG_TILE(T), 1>), grid, dim3(256), 0, st, small, ld_small, big, ld_big, dst, q.out_elems, g, q.cps, q.tiles_n,
+                                       p.veck, vecy);
+                else
+                    hipLaunchKernelGGL((k_wgrad_tapn<PG_TILE(T), 2>), grid, dim3(256), 0, st, big, ld_big, small, ld_small, dst, q.out_elems, g, q.cps, q.tiles_n,
+                                       p.vecn, 0);
+            });
+        }
+    }
+    if (hipGetLastError() != hipSuccess) return PG_ELAUNCH;
+    return q.split == 1 ? PG_OK : reduce(dst, q.split);
+}
+
+// plan the call and launch its path
+int run_conv(int op, const Views& v, const pg_conv_geom* gg, int algo_full, size_t ws_bytes, void* stream) {
+    if (!v.ws) ws_bytes = 0;
+    Call c{ConvPlan{}, v, to_geom(gg), algo_full & PG_ALGO_MASK, algo_full & PG_IO_MASK, tune_of(algo_full), ws_bytes, (hipStream_t)stream};
+    c.p = plan_conv(gg, op, algo_full, c.tune, ws_bytes, &c.v);
+    if (c.p.rc != PG_OK) return c.p.rc;
+    return op == 0 ? launch_b2s(c) : op == 1 ? launch_s2b(c) : launch_wgrad(c);
+}
+
+}  // namespace
+
+extern "C" {
+
+int pg_conv4x4_big2small_x(const float* big, int ld_big, const float* P, const float* bias, float* small, int ld_small,
+                           const pg_conv_geom* gg, int act, int algo, void* ws, size_t ws_bytes, void* stream, const pg_conv_extras* xp) {
+    const pg_conv_extras& x = xp ? *xp : NO_EXTRAS;
+    if ((x.u_cache && !aligned16(x.u_cache)) || (x.v_keep && !aligned16(x.v_keep)) || x.v_pre) return PG_EINVAL;
+    if (!geom_ok(gg) || !big || !P || !small || ld_big < gg->Cb || ld_small < gg->Ca) return PG_EINVAL;
+    if (act < PG_ACT_NONE || act > PG_ACT_SIGMOID) return PG_EINVAL;
+    // bf16 activation storage: PG_IO_BIG_BF16 = input, PG_IO_SMALL_BF16 = output
+    if ((algo & PG_IO_MASK) && (algo & PG_ALGO_MASK) != PG_ALGO_BF16) return PG_EINVAL;
+    return run_conv(0, Views{small, big, ld_small, ld_big, P, bias, act, ws, &x}, gg, algo, ws_bytes, stream);
+}
+
+int pg_conv4x4_big2small(const float* big, int ld_big, const float* P, const float* bias, float* small,
+                         int ld_small, const pg_conv_geom* gg, int act, int algo, void* ws, size_t ws_bytes,
+                         void* stream) {
+    return pg_conv4x4_big2small_x(big, ld_big, P, bias, small, ld_small, gg, act, algo, ws, ws_bytes, stream, nullptr);
+}
+
+int pg_conv4x4_small2big_x(const float* small, int ld_small, const float* P, const float* bias, float* big, int ld_big,
+                           const pg_conv_geom* gg, int act, int algo, void* ws, size_t ws_bytes, void* stream, const pg_conv_extras* xp) {
+    const pg_conv_extras& x = xp ? *xp : NO_EXTRAS;
+    if ((x.u_cache && !aligned16(x.u_cache)) || x.v_keep || x.v_pre) return PG_EINVAL;
+    if (x.mul_t && (x.mul_ld < gg->Cb || x.mul_act < PG_ACT_NONE || x.mul_act > PG_ACT_SIGMOID || x.part)) return PG_EINVAL;
+    if (!geom_ok(gg) || !big || !P || !small || ld_big < gg->Cb || ld_small < gg->Ca) return PG_EINVAL;
+    if (act < PG_ACT_NONE || act > PG_ACT_SIGMOID) return PG_EINVAL;
+    // PG_IO_SMALL_BF16 = input, PG_IO_BIG_BF16 = output
+    if ((algo & PG_IO_MASK) && (algo & PG_ALGO_MASK) != PG_ALGO_BF16) return PG_EINVAL;
+    return run_conv(1, Views{small, big, ld_small, ld_big, P, bias, act, ws, &x}, gg, algo, ws_bytes, stream);
+}
+
+int pg_conv4x4_small2big(const float* small, int ld_small, const float* P, const float* bias, float* big,
+                         int ld_big, const pg_conv_geom* gg, int act, int algo, void* ws, size_t ws_bytes,
+                         void* stream) {
+    return pg_conv4x4_small2big_x(small, ld_small, P, bias, big, ld_big, gg, act, algo, ws, ws_bytes, stream, nullptr);
 }
 
 static int wgrad_impl(const float* small, int ld_small, const float* big, int ld_big, float* dP, float* dbias,
@@ -4443,18 +4619,14 @@ static int wgrad_impl(const float* small, int ld_small, const float* big, int ld
     if (!geom_ok(gg) || !big || !dP || !small || ld_big < gg->Cb || ld_small < gg->Ca) return PG_EINVAL;
     if (v_pre && !aligned16(v_pre)) return PG_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    Geom g = to_geom(gg);
-    const Tune tune = tune_of(algo);
+    const Geom g = to_geom(gg);
     const int io = algo & PG_IO_MASK;                 // both activation operands bf16, or neither
-    algo &= PG_ALGO_MASK;
-    if (io && (algo != PG_ALGO_BF16 || io != PG_IO_MASK)) return PG_EINVAL;
+    if (io && ((algo & PG_ALGO_MASK) != PG_ALGO_BF16 || io != PG_IO_MASK)) return PG_EINVAL;
     if (io && dbias && !((g.Ca % 4 == 0) && (ld_small % 4 == 0) && aligned_io(small, true))) return PG_EINVAL;
     if (!ws) ws_bytes = 0;
-    const long Kp = (long)g.N * g.Hs * g.Ws;
-    size_t reserved = 0;
     if (dbias) {
-        reserved = ((size_t)COLSUM_CHUNKS * g.Ca * sizeof(float) + 255) & ~(size_t)255;
-        if (ws_bytes < reserved) return PG_EWORKSPACE;
+        if (ws_bytes < colsum_bytes(g.Ca)) return PG_EWORKSPACE;
+        const long Kp = (long)g.N * g.Hs * g.Ws;
         float* part = (float*)ws;
         int chunks = (int)std::min<long>(COLSUM_CHUNKS, Kp);
         long rpc = (Kp + chunks - 1) / chunks;
@@ -4472,133 +4644,9 @@ static int wgrad_impl(const float* small, int ld_small, const float* big, int ld
         int rc = launch_reduce(part, g.Ca, chunks, dbias, g.Ca, 1, g.Ca, nullptr, 0, st);
         if (rc != PG_OK) return rc;
     }
-    const long per = 16L * g.Ca * g.Cb;
-    if (algo == PG_ALGO_DIRECT) {
-        long smax = (long)((ws_bytes - reserved) / (sizeof(float) * (size_t)per));
-        int slices = (int)std::min<long>(std::min<long>(DIRECT_WGRAD_SLICES, smax), Kp);
-        if (slices < 1) slices = 1;
-        long pps = (Kp + slices - 1) / slices;
-        slices = (int)((Kp + pps - 1) / pps);
-        float* dst = slices == 1 ? dP : (float*)((char*)ws + reserved);
-        hipLaunchKernelGGL(k_wgrad_direct, dim3((int)((per + 255) / 256), slices), dim3(256), 0, st, small, ld_small, big,
-                           ld_big, dst, per, g, pps);
-        if (hipGetLastError() != hipSuccess) return PG_ELAUNCH;
-        if (slices == 1) return PG_OK;
-        return launch_reduce(dst, per, slices, dP, g.Cb, 16L * g.Ca, g.Cb, nullptr, 0, st);
-    }
-    if (algo == PG_ALGO_AUTO && wino_wgrad_ok(g, tune) && (ld_small % 4 == 0) && (ld_big % 4 == 0) && aligned16(small) &&
-        aligned16(big) && aligned16(ws) && ws_bytes >= reserved + pg_wino_wgrad_ws_bytes(g.N, g.Hs, g.Ws, g.Ca, g.Cb)) {
-        hipEvent_t e0 = t_ev0, e1 = t_ev1;
-        t_ev0 = nullptr;
-        t_ev1 = nullptr;
-        if (v_pre && !pg_wino_wgrad_v_bytes(g.N, g.Hs, g.Ws, g.Ca, g.Cb, tune.mo1)) return PG_EINVAL;
-        return pg_wino_wgrad(small, ld_small, big, ld_big, dP, g.N, g.Hb, g.Wb, g.Hs, g.Ws, g.Ca, g.Cb, (char*)ws + reserved, st,
-                             e0, e1, v_pre, tune.s3w);
-    }
-    if (algo == PG_ALGO_AUTO && wino2_wgrad_ok(g, tune) && (ld_small % 4 == 0) && (ld_big % 4 == 0) && aligned16(small) &&
-        aligned16(big) && aligned16(ws) && aligned16(dP) && ws_bytes >= reserved + pg_wino2_wgrad_ws_bytes(g.N, g.Hs, g.Ws, g.Ca, g.Cb)) {
-        hipEvent_t e0 = t_ev0, e1 = t_ev1;
-        t_ev0 = nullptr;
-        t_ev1 = nullptr;
-        return pg_wino2_wgrad(small, ld_small, big, ld_big, dP, g.N, g.Hb, g.Wb, g.Hs, g.Ws, g.Ca, g.Cb, (char*)ws + reserved, st,
-                              e0, e1, v_pre, tune.s3w);
-    }
-    if (v_pre) return PG_EINVAL;     // pg_conv_v_bytes said 0 for this call: there is no transformed operand to reuse
-    if (bf16x_wgrad_ok(g, algo | io, tune) && (g.Cb > 8 || ld_big == 8) && aligned_bf_view(small, ld_small, true) &&
-        aligned_bf_view(big, ld_big, true) && aligned16(dP) && (ws_bytes <= reserved || aligned16(ws))) {
-        const long small_bytes = tensor_bytes(Kp, ld_small, g.Ca, true);
-        const long big_bytes = tensor_bytes((long)g.N * g.Hb * g.Wb, ld_big, g.Cb > 8 ? g.Cb : 8, true);
-        if (small_bytes < FAST_LIMIT && big_bytes < FAST_LIMIT) {
-            pg_bf16x_plan wp = pg_bf16x_wgrad_plan(g.N, g.Hb, g.Wb, g.Hs, g.Ws, g.Ca, g.Cb, g.s);
-            pg_bf16x_clamp(&wp, ws_bytes > reserved ? ws_bytes - reserved : 0);
-            float* dst = wp.split == 1 ? dP : (float*)((char*)ws + reserved);
-            int rc;
-            {
-                TimedLaunch timed(st);
-                rc = pg_bf16x_wgrad(small, ld_small, small_bytes, big, ld_big, big_bytes, dst, wp.split == 1 ? 0L : wp.out_elems, g.N, g.Hb,
-                                    g.Wb, g.Hs, g.Ws, g.Ca, g.Cb, g.s, &wp, st);
-            }
-            if (rc != PG_OK || wp.split == 1) return rc;
-            return launch_reduce(dst, wp.out_elems, wp.split, dP, g.Cb, 16L * g.Ca, g.Cb, nullptr, 0, st);
-        }
-    }
-    Plan p = plan_wgrad(gg);
-    clamp_split(p, ws_bytes, reserved);
-    const bool in_bf = io != 0;
-    const int vecm = (g.Ca % 4 == 0) && (ld_small % 4 == 0) && aligned_io(small, in_bf);
-    const int vecn = (g.Cb % 4 == 0) && (ld_big % 4 == 0) && aligned_io(big, in_bf);
-    const int mode = wgrad_mode(gg);
-    if (io && mode != 0) return PG_EINVAL;
-    float* dst = p.split == 1 ? dP : (float*)((char*)ws + reserved);
-    TimedLaunch* timed = new (alloca(sizeof(TimedLaunch))) TimedLaunch(st);
-    if (mode == 0) {
-        dim3 grid(p.tiles_m * p.tiles_n, 16, p.split);
-        const long small_bytes = tensor_bytes(Kp, ld_small, g.Ca, in_bf);
-        const long big_bytes = tensor_bytes((long)g.N * g.Hb * g.Wb, ld_big, g.Cb, in_bf);
-        const bool pow2 = ((g.Hs & (g.Hs - 1)) == 0) && ((g.Ws & (g.Ws - 1)) == 0);
-        const bool fast = vecm && vecn && small_bytes < FAST_LIMIT && big_bytes < FAST_LIMIT && !force_generic() &&
-                          (pow2 || (g.Ws >= 16 && g.Hs >= 2));
-        if (io && !fast) {
-            timed->~TimedLaunch();
-            return PG_EINVAL;
-        }
-        if (fast && algo == PG_ALGO_BF16 && pow2 && in_bf) {
-            PG_DISPATCH_WGH(true, true, p.t.id, grid, st, small, ld_small, big, ld_big, dst, p.out_elems, g, p.cps, p.tiles_n,
-                            (int)small_bytes, (int)big_bytes);
-        } else if (fast && algo == PG_ALGO_BF16 && in_bf) {
-            PG_DISPATCH_WGH(false, true, p.t.id, grid, st, small, ld_small, big, ld_big, dst, p.out_elems, g, p.cps, p.tiles_n,
-                            (int)small_bytes, (int)big_bytes);
-        } else if (fast && algo == PG_ALGO_BF16 && pow2) {
-            PG_DISPATCH_WGH(true, false, p.t.id, grid, st, small, ld_small, big, ld_big, dst, p.out_elems, g, p.cps, p.tiles_n,
-                            (int)small_bytes, (int)big_bytes);
-        } else if (fast && algo == PG_ALGO_BF16) {
-            PG_DISPATCH_WGH(false, false, p.t.id, grid, st, small, ld_small, big, ld_big, dst, p.out_elems, g, p.cps, p.tiles_n,
-                            (int)small_bytes, (int)big_bytes);
-        } else if (fast && pow2) {
-            PG_DISPATCH_WGF(true, p.t.id, grid, st, small, ld_small, big, ld_big, dst, p.out_elems, g, p.cps, p.tiles_n,
-                            (int)small_bytes, (int)big_bytes);
-        } else if (fast) {
-            PG_DISPATCH_WGF(false, p.t.id, grid, st, small, ld_small, big, ld_big, dst, p.out_elems, g, p.cps, p.tiles_n,
-                            (int)small_bytes, (int)big_bytes);
-        } else {
-            PG_DISPATCH_TILE(k_wgrad, p.t.id, grid, st, small, ld_small, big, ld_big, dst, p.out_elems, g, p.cps,
-                             p.tiles_n, vecm, vecn);
-        }
-    } else if (mode == 1 && wgrad_tapnp_ok(g) && vecm && aligned16(ws) &&
-               (g.Cb != 4 || ((ld_big % 4 == 0) && aligned16(big))) && tensor_bytes(Kp, ld_small, g.Ca) < FAST_LIMIT &&
-               tensor_bytes((long)g.N * g.Hb * g.Wb, ld_big, g.Cb) < FAST_LIMIT &&
-               ws_bytes >= reserved + (size_t)wgrad_tapnp_slabs(g) * p.out_elems * sizeof(float)) {
-        // persistent form: one slab per workgroup column, reduced in workgroup order
-        const int ntiles = (int)((Kp + 127) / 128), G = wgrad_tapnp_slabs(g);
-        const int small_b = (int)tensor_bytes(Kp, ld_small, g.Ca), big_b = (int)tensor_bytes((long)g.N * g.Hb * g.Wb, ld_big, g.Cb);
-        const bool wide3 = (g.Cb == 3) && (ld_big % 4 == 0) && (ld_big >= 4) && aligned16(big);
-        float* slabs = (float*)((char*)ws + reserved);
-        if (g.Cb <= 2) {
-            dim3 grid(G, (g.Ca + 127) / 128, 1);
-            if (g.Cb == 1) hipLaunchKernelGGL((k_wgrad_tapnp<1, false, 4>), grid, dim3(256), 0, st, small, ld_small, big, ld_big, slabs, p.out_elems, g, small_b, big_b, ntiles);
-            else hipLaunchKernelGGL((k_wgrad_tapnp<2, false, 4>), grid, dim3(256), 0, st, small, ld_small, big, ld_big, slabs, p.out_elems, g, small_b, big_b, ntiles);
-        } else {
-            dim3 grid(G, (g.Ca + 63) / 64, 1);
-            if (g.Cb == 4) hipLaunchKernelGGL((k_wgrad_tapnp<4, true, 2>), grid, dim3(256), 0, st, small, ld_small, big, ld_big, slabs, p.out_elems, g, small_b, big_b, ntiles);
-            else if (wide3) hipLaunchKernelGGL((k_wgrad_tapnp<3, true, 2>), grid, dim3(256), 0, st, small, ld_small, big, ld_big, slabs, p.out_elems, g, small_b, big_b, ntiles);
-            else hipLaunchKernelGGL((k_wgrad_tapnp<3, false, 2>), grid, dim3(256), 0, st, small, ld_small, big, ld_big, slabs, p.out_elems, g, small_b, big_b, ntiles);
-        }
-        timed->~TimedLaunch();
-        if (hipGetLastError() != hipSuccess) return PG_ELAUNCH;
-        return launch_reduce(slabs, p.out_elems, G, dP, g.Cb, 16L * g.Ca, g.Cb, nullptr, 0, st);
-    } else if (mode == 1) {
-        dim3 grid(p.tiles_m * p.tiles_n, 1, p.split);
-        const int vecy = (g.Cb == 4) && (ld_big % 4 == 0) && aligned16(big);
-        PG_DISPATCH_TAPN(1, p.t.id, grid, st, small, ld_small, big, ld_big, dst, p.out_elems, g, p.cps, p.tiles_n, vecm,
-                         vecy);
-    } else {
-        dim3 grid(p.tiles_m * p.tiles_n, 1, p.split);
-        PG_DISPATCH_TAPN(2, p.t.id, grid, st, big, ld_big, small, ld_small, dst, p.out_elems, g, p.cps, p.tiles_n, vecn, 0);
-    }
-    timed->~TimedLaunch();
-    if (hipGetLastError() != hipSuccess) return PG_ELAUNCH;
-    if (p.split == 1) return PG_OK;
-    return launch_reduce(dst, p.out_elems, p.split, dP, g.Cb, 16L * g.Ca, g.Cb, nullptr, 0, st);
+    pg_conv_extras x = NO_EXTRAS;
+    x.v_pre = v_pre;
+    return run_conv(2, Views{small, big, ld_small, ld_big, dP, dbias, PG_ACT_NONE, ws, &x}, gg, algo, ws_bytes, stream);
 }
 
 int pg_conv4x4_wgrad(const float* small, int ld_small, const float* big, int ld_big, float* dP, float* dbias,
@@ -4630,14 +4678,10 @@ int pg_conv4x4_bwd_big_x(const float* small, int ld_small, const float* big, int
     const Geom g = to_geom(gg);
     const Tune tune = tune_of(algo);
     if (!ws) ws_bytes = 0;
-    const size_t vb = pg_wino2_v_bytes(g.N, g.Hs, g.Ws, g.Cb);
-    const bool share = (algo & PG_ALGO_MASK) == PG_ALGO_AUTO && pg_wino2_mo() == 3 && wino2_b2s_ok(g, tune) && wino2_wgrad_ok(g, tune) &&
-                       (ld_small % 4 == 0) && (ld_big % 4 == 0) && (ld_dsmall % 4 == 0) && aligned16(small) && aligned16(big) &&
-                       aligned16(P) && aligned16(dP) && aligned16(dsmall) && aligned16(ws) &&
-                       ws_bytes >= vb + std::max(pg_wino2_ws_bytes(g.N, g.Hs, g.Ws, g.Ca, g.Cb),
-                                                 pg_wino2_wgrad_ws_bytes(g.N, g.Hs, g.Ws, g.Ca, g.Cb));
+    const bool views_ok = (ld_small % 4 == 0) && (ld_big % 4 == 0) && (ld_dsmall % 4 == 0) && aligned16(small) && aligned16(big) &&
+                          aligned16(P) && aligned16(dP) && aligned16(dsmall) && aligned16(ws);
     hipEvent_t e0 = t_ev0, e1 = t_ev1, e2 = t_ev2, e3 = t_ev3;
-    if (!share) {       // the two halves as separate calls (each consumes one armed event pair)
+    if (!plan_share_v(g, algo, tune, ws_bytes, views_ok, nullptr)) {       // the two halves as separate calls (each consumes one armed event pair)
         t_ev2 = t_ev3 = nullptr;
         int rc = pg_conv4x4_wgrad(small, ld_small, big, ld_big, dP, nullptr, gg, algo, ws, ws_bytes, stream);
         if (rc != PG_OK) return rc;
@@ -4654,7 +4698,7 @@ int pg_conv4x4_bwd_big_x(const float* small, int ld_small, const float* big, int
     t_ev0 = t_ev1 = t_ev2 = t_ev3 = nullptr;
     // V(big) once; the weight-gradient GEMM and the data-gradient GEMM both read it (ws: V | DY S, then V | U M)
     float* V = (float*)ws;
-    void* rest = (char*)ws + vb;
+    void* rest = (char*)ws + pg_wino2_v_bytes(g.N, g.Hs, g.Ws, g.Cb);
     int rc = pg_wino2_v(big, ld_big, V, g.N, g.Hb, g.Wb, g.Hs, g.Ws, g.Cb, st);
     if (rc != PG_OK) return rc;
     rc = pg_wino2_wgrad(small, ld_small, big, ld_big, dP, g.N, g.Hb, g.Wb, g.Hs, g.Ws, g.Ca, g.Cb, rest, st, e0, e1, V, tune.s3w);
