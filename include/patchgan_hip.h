@@ -22,6 +22,14 @@
  *     never allocate, never synchronise; the caller owns all memory including
  *     the workspace.  Return 0 on success or a negative PG_E* code; nothing is
  *     launched when an error is returned.
+ *   - containment: a call writes the C channels of each pixel of its output
+ *     tensors and nothing else of the buffer they are slices of (not the other
+ *     ld - C channels of a pixel, nothing before the first or after the last
+ *     pixel), the documented element count of its flat outputs (dP: 16*Ca*Cb
+ *     floats, dbias: Ca floats, stats, coef, S, ...), at most ws_bytes bytes of
+ *     the workspace and at most the queried bytes of a hand-over buffer; it
+ *     reads its inputs only.  The two exceptions write WHOLE pixels and say so:
+ *     pg_pad8_bf16 and pg_din_fill zero their pad channels.
  *   - thread-compatible: no global mutable state (pg_conv_time_next keeps two thread-local event handles).
  */
 #ifndef PATCHGAN_HIP_H
@@ -114,7 +122,15 @@ size_t pg_conv_max_tensor_bytes(void);
 
 /* Bytes of workspace that lets op (0 = big2small, 1 = small2big, 2 = wgrad) use its preferred
  * split-K factor / Winograd path for geometry g under ANY algo / PG_TUNE_* combination.  A smaller (or NULL) workspace is
- * legal: the split shrinks, the Winograd paths fall back to the implicit GEMM. */
+ * legal: the split shrinks, the Winograd paths fall back to the implicit GEMM.  Two exceptions return PG_EWORKSPACE (nothing launched):
+ *   - pg_conv4x4_wgrad (and _wgrad_x) with dbias != NULL keeps the bias gradient's partial column sums at the head of the workspace:
+ *     below 1024 * Ca floats rounded up to 256 bytes it is refused; without dbias any size, NULL included, is PG_OK;
+ *   - bf16 tensors (PG_IO_*) run on bf16 kernels only, and the LDS-DMA kernels read packed bf16 weights from the workspace (unless
+ *     pg_conv_extras.u_cache holds them).  Where the register-staged bf16 kernels do not cover the call -- big2small from 8-channel
+ *     pixels, views or map sizes only the LDS-DMA kernels take -- a workspace without room for the pack leaves no kernel: pg_conv_kernel
+ *     then names a kernel without "bf16" for that size, and the call is refused.  (PG_EINVAL is for a call that has no bf16 kernel at
+ *     pg_conv_workspace_bytes() either.)
+ * A call writes nothing beyond the first ws_bytes bytes of `ws`, whatever path it takes. */
 size_t pg_conv_workspace_bytes(const pg_conv_geom* g, int op);   /* op 3 = pg_conv4x4_bwd_big */
 
 /* Reports which kernel the MFMA path of op would launch for g with a workspace of ws_bytes: tile_id
@@ -191,7 +207,10 @@ int pg_conv4x4_wgrad(const float* small, int ld_small, const float* big, int ld_
  *   u_valid  ... and, when non-zero, already hold the transform of the CURRENT weights: the weight transform is skipped
  *            (the discriminator's weights serve two forward and two data-gradient passes per step, trainer.py:66,98-99).
  * The size queries mirror the dispatch for 16-byte-aligned tensors and return 0 when the call would not take a path that has
- * such an operand; passing a hand-over to a call that does not take that path returns PG_EINVAL (nothing is launched). */
+ * such an operand; passing a hand-over to a call that does not take that path returns PG_EINVAL (nothing is launched: not the
+ * weight gradient's bias column sums either) -- under PG_ALGO_DIRECT, whose kernels have no such operand, always.  The queries take
+ * the workspace size of the CALL: with a smaller workspace a Winograd path falls back and its hand-overs go with it (the query
+ * returns 0, the call refuses them). */
 typedef struct pg_conv_extras {
     double* part;
     float* v_keep;
@@ -320,7 +339,9 @@ int pg_dropout_mask(float* mask, long nelem, float drop_p, uint64_t seed, void* 
  *   bstat[(s*C + c)*2 + {0,1}] = (batch mean, unbiased batch variance), fp64 (may be NULL): the input of the running update.
  * Statistics: fp64 partial sums per (sample, pixel chunk, channel), merged in a fixed order (bit-reproducible).  Every
  * (N / nseg) * HW must be > 1 (torch raises "Expected more than 1 value per channel when training" there).  Dropout as
- * pg_instnorm_act_fwd.  ws: pg_batchnorm_workspace_bytes. */
+ * pg_instnorm_act_fwd.  ws: pg_batchnorm_workspace_bytes -- REQUIRED: unlike the InstanceNorm entry points, pg_batchnorm_act_fwd,
+ * pg_batchnorm_stats (from y; with `part` it takes none) and pg_batchnorm_act_bwd do not fall back: a NULL or smaller workspace
+ * returns PG_EWORKSPACE (nothing launched), whatever kernel the views would select. */
 size_t pg_batchnorm_workspace_bytes(int N, int HW, int C, int nseg);
 int pg_batchnorm_act_fwd(const float* y, int ld_y, float* out, int ld_out, const float* weight, const float* bias, float* coef,
                          double* bstat, int N, int HW, int C, int nseg, int act, float eps, float drop_p, uint64_t seed, void* ws,

@@ -578,16 +578,22 @@ size_t pg_batchnorm_workspace_bytes(int N, int HW, int C, int nseg) {
     return std::max(a.part_bytes, b.part_bytes) + bcoef_bytes(nseg, C);
 }
 
+// One rule for the three entry points that take a workspace, whatever kernel the views select (the one-workgroup kernels of small
+// planes use none of it): the caller passes what the query says, or the call is refused before anything is launched.
+static bool ws_short(int N, int HW, int C, int nseg, const void* ws, size_t ws_bytes) {
+    return !ws || ws_bytes < pg_batchnorm_workspace_bytes(N, HW, C, nseg);
+}
+
 int pg_batchnorm_stats(const float* y, int ld_y, const double* part, int chunks, const float* weight, const float* bias, float* coef,
                        double* bstat, int N, int HW, int C, int nseg, float eps, void* ws, size_t ws_bytes, void* stream) {
     if (bad_geom(N, HW, C, nseg) || !weight || !bias || !coef || ld_y < C) return PG_EINVAL;
-    if (part ? chunks <= 0 : (!y || !ws)) return PG_EINVAL;
+    if (part ? chunks <= 0 : !y) return PG_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const int Ns = N / nseg;
     if (!part) {
         const bool vec = (C % 4 == 0) && (ld_y % 4 == 0) && al16(y);
         const BnPlan p = bn_plan(N, HW, C, vec ? 4 : 1);
-        if (ws_bytes < p.part_bytes) return PG_EWORKSPACE;
+        if (ws_short(N, HW, C, nseg, ws, ws_bytes)) return PG_EWORKSPACE;
         const dim3 grid(p.groups, p.nchunk, N);
         if (vec)
             hipLaunchKernelGGL((k_bn_partial<4, false, false>), grid, dim3(256), 0, st, y, ld_y, nullptr, 0, nullptr, 0, nullptr,
@@ -633,6 +639,7 @@ int pg_batchnorm_act_fwd(const float* y, int ld_y, float* out, int ld_out, const
                          size_t ws_bytes, void* stream) {
     if (bad_geom(N, HW, C, nseg) || !y || !out || !weight || !bias || !coef || ld_y < C || ld_out < C) return PG_EINVAL;
     if (drop_p < 0.f || drop_p >= 1.f || act < 0 || act > PG_ACT_SIGMOID) return PG_EINVAL;
+    if (ws_short(N, HW, C, nseg, ws, ws_bytes)) return PG_EWORKSPACE;
     const bool vec = (C % 4 == 0) && (ld_y % 4 == 0) && (ld_out % 4 == 0) && al16(y) && al16(out);
     if (bn_plan(N, HW, C, vec ? 4 : 1).nchunk > 1) {          // (the decision of pg_instnorm_act_fwd_t for the same views)
         const int rc = pg_batchnorm_stats(y, ld_y, nullptr, 0, weight, bias, coef, bstat, N, HW, C, nseg, eps, ws, ws_bytes, stream);
@@ -659,6 +666,7 @@ int pg_batchnorm_act_bwd(const float* g1, int ld_g1, const float* g2, int ld_g2,
     if (bad_geom(N, HW, C, nseg, train ? 2 : 1) || !g1 || !y || !coef || !dy || ld_g1 < C || ld_y < C || ld_dy < C || (g2 && ld_g2 < C))
         return PG_EINVAL;
     if ((!dweight) != (!dbias) || drop_p < 0.f || drop_p >= 1.f || act < 0 || act > PG_ACT_SIGMOID) return PG_EINVAL;
+    if (ws_short(N, HW, C, nseg, ws, ws_bytes)) return PG_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const int Ns = N / nseg;
     const int tr = train ? 1 : 0;
@@ -666,8 +674,6 @@ int pg_batchnorm_act_bwd(const float* g1, int ld_g1, const float* g2, int ld_g2,
                      (!g2 || ((ld_g2 % 4 == 0) && al16(g2)));
     const BnPlan p = bn_plan(N, HW, C, vec ? 4 : 1);
     if (p.nchunk > 1) {
-        if (!ws) return PG_EINVAL;
-        if (ws_bytes < p.part_bytes + bcoef_bytes(nseg, C)) return PG_EWORKSPACE;
         double* part = (double*)ws;
         float* bcoef = (float*)((char*)ws + p.part_bytes);
         const dim3 grid(p.groups, p.nchunk, N);

@@ -3696,7 +3696,7 @@ ConvPlan plan_big2small(const pg_conv_geom* gg, const PlanCtx& c) {
              p_bytes < FAST_P_LIMIT && !force_generic();
     if (c.algo == PG_ALGO_DIRECT) {
         p.path = Path::Direct;
-        if (v) return p;
+        if (v) return (c.part || c.has_u || c.has_v) ? fail(p) : p;     // (the direct kernels have no operand to hand over: the queries say 0)
     }
     if (plan_wino(p, c, 0)) return p;
     if (bf16x_ok(g, 0, c.algo | c.io, c.tune) && !c.has_v && plan_bf16x(p, c, 0)) return p;
@@ -3754,7 +3754,7 @@ ConvPlan plan_small2big(const pg_conv_geom* gg, const PlanCtx& c) {
              !force_generic();
     if (c.algo == PG_ALGO_DIRECT) {
         p.path = Path::Direct;
-        if (v) return c.mul ? fail(p) : p;
+        if (v) return (c.mul || c.part || c.has_u) ? fail(p) : p;
     }
     if (s2b_ca1_ok(g, c.algo | c.io) && !c.part && !c.has_u &&
         (q || (aligned16(v->P) && (!v->bias || aligned16(v->bias)) && aligned_bf_view(v->big, v->ld_big, out_bf) &&
@@ -3825,7 +3825,7 @@ ConvPlan plan_wgrad_conv(const pg_conv_geom* gg, const PlanCtx& c) {
     if (c.algo == PG_ALGO_DIRECT) {
         need(p, colsum + (size_t)DIRECT_WGRAD_SLICES * p.gemm.out_elems * sizeof(float));
         p.path = Path::Direct;
-        if (v) return p;
+        if (v) return c.has_v ? fail(p) : p;
     }
     // F(4x4,2x2) / F(4x4,3x3) of a stride-1 layer (w1), polyphase F(2x2,3x3) of a stride-2 layer
     const bool w1 = c.algo == PG_ALGO_AUTO && wino_wgrad_ok(g, c.tune), w2 = c.algo == PG_ALGO_AUTO && wino2_wgrad_ok(g, c.tune);
@@ -4566,16 +4566,39 @@ int launch_wgrad(const Call& c) {
     return q.split == 1 ? PG_OK : reduce(dst, q.split);
 }
 
+// The code of a refused call.  bf16 tensors run on the bf16 kernels only, and the LDS-DMA ones read packed bf16 weights from the
+// workspace: where the register-staged kernels do not cover the call (8-channel pixels, ...) a NULL or smaller workspace leaves no
+// kernel.  That is PG_EWORKSPACE -- the same call with pg_conv_workspace_bytes() is accepted -- and not PG_EINVAL.
+int refusal(int rc, int op, const Views& v, const pg_conv_geom* gg, int algo_full, size_t ws_bytes) {
+    if (rc != PG_EINVAL || !(algo_full & PG_IO_MASK)) return rc;
+    const size_t full = pg_conv_workspace_bytes(gg, op);
+    if (v.ws && ws_bytes >= full) return rc;
+    Views w = v;
+    if (!w.ws) w.ws = reinterpret_cast<void*>(uintptr_t(256));      // (planned, never launched: only its alignment is looked at)
+    return plan_conv(gg, op, algo_full, tune_of(algo_full), full, &w).rc == PG_OK ? PG_EWORKSPACE : rc;
+}
+
 // plan the call and launch its path
 int run_conv(int op, const Views& v, const pg_conv_geom* gg, int algo_full, size_t ws_bytes, void* stream) {
     if (!v.ws) ws_bytes = 0;
     Call c{ConvPlan{}, v, to_geom(gg), algo_full & PG_ALGO_MASK, algo_full & PG_IO_MASK, tune_of(algo_full), ws_bytes, (hipStream_t)stream};
     c.p = plan_conv(gg, op, algo_full, c.tune, ws_bytes, &c.v);
-    if (c.p.rc != PG_OK) return c.p.rc;
+    if (c.p.rc != PG_OK) return refusal(c.p.rc, op, v, gg, algo_full, ws_bytes);
     return op == 0 ? launch_b2s(c) : op == 1 ? launch_s2b(c) : launch_wgrad(c);
 }
 
 }  // namespace
+
+// A hand-over is taken only where its size query, asked with the workspace of THIS call, reports a size: the caller could not have
+// sized the buffer otherwise (pg_conv_v_bytes is 0 where the layer's weight gradient would not read the kept V, although the forward
+// path has one; the bf16 kernels promise their statistics epilogue only with the path's full workspace).  Else PG_EINVAL, nothing launched.
+static bool hand_overs_sized(const pg_conv_geom* gg, int op, int algo, const void* ws, size_t ws_bytes, const pg_conv_extras& x) {
+    const size_t wb = ws ? ws_bytes : 0;
+    if (x.part && (op > 1 || pg_conv_stats_chunks(gg, op, algo, wb) == 0)) return false;
+    if (x.u_cache && (op > 1 || pg_conv_u_bytes(gg, op, algo, wb) == 0)) return false;
+    if ((x.v_keep || x.v_pre) && pg_conv_v_bytes(gg, algo, wb) == 0) return false;
+    return true;
+}
 
 extern "C" {
 
@@ -4587,6 +4610,7 @@ int pg_conv4x4_big2small_x(const float* big, int ld_big, const float* P, const f
     if (act < PG_ACT_NONE || act > PG_ACT_SIGMOID) return PG_EINVAL;
     // bf16 activation storage: PG_IO_BIG_BF16 = input, PG_IO_SMALL_BF16 = output
     if ((algo & PG_IO_MASK) && (algo & PG_ALGO_MASK) != PG_ALGO_BF16) return PG_EINVAL;
+    if (!hand_overs_sized(gg, 0, algo, ws, ws_bytes, x)) return PG_EINVAL;
     return run_conv(0, Views{small, big, ld_small, ld_big, P, bias, act, ws, &x}, gg, algo, ws_bytes, stream);
 }
 
@@ -4605,6 +4629,7 @@ int pg_conv4x4_small2big_x(const float* small, int ld_small, const float* P, con
     if (act < PG_ACT_NONE || act > PG_ACT_SIGMOID) return PG_EINVAL;
     // PG_IO_SMALL_BF16 = input, PG_IO_BIG_BF16 = output
     if ((algo & PG_IO_MASK) && (algo & PG_ALGO_MASK) != PG_ALGO_BF16) return PG_EINVAL;
+    if (!hand_overs_sized(gg, 1, algo, ws, ws_bytes, x)) return PG_EINVAL;
     return run_conv(1, Views{small, big, ld_small, ld_big, P, bias, act, ws, &x}, gg, algo, ws_bytes, stream);
 }
 
@@ -4624,8 +4649,15 @@ static int wgrad_impl(const float* small, int ld_small, const float* big, int ld
     if (io && ((algo & PG_ALGO_MASK) != PG_ALGO_BF16 || io != PG_IO_MASK)) return PG_EINVAL;
     if (io && dbias && !((g.Ca % 4 == 0) && (ld_small % 4 == 0) && aligned_io(small, true))) return PG_EINVAL;
     if (!ws) ws_bytes = 0;
+    pg_conv_extras x = NO_EXTRAS;
+    x.v_pre = v_pre;
+    if (!hand_overs_sized(gg, 2, algo, ws, ws_bytes, x)) return PG_EINVAL;
     if (dbias) {
         if (ws_bytes < colsum_bytes(g.Ca)) return PG_EWORKSPACE;
+        // nothing is launched when an error is returned: the column sums start only for a call that the planner accepts
+        const Views vw{small, big, ld_small, ld_big, dP, dbias, PG_ACT_NONE, ws, &x};
+        const int prc = plan_conv(gg, 2, algo, tune_of(algo), ws_bytes, &vw).rc;
+        if (prc != PG_OK) return refusal(prc, 2, vw, gg, algo, ws_bytes);
         const long Kp = (long)g.N * g.Hs * g.Ws;
         float* part = (float*)ws;
         int chunks = (int)std::min<long>(COLSUM_CHUNKS, Kp);
@@ -4644,8 +4676,6 @@ static int wgrad_impl(const float* small, int ld_small, const float* big, int ld
         int rc = launch_reduce(part, g.Ca, chunks, dbias, g.Ca, 1, g.Ca, nullptr, 0, st);
         if (rc != PG_OK) return rc;
     }
-    pg_conv_extras x = NO_EXTRAS;
-    x.v_pre = v_pre;
     return run_conv(2, Views{small, big, ld_small, ld_big, dP, dbias, PG_ACT_NONE, ws, &x}, gg, algo, ws_bytes, stream);
 }
 
@@ -4674,6 +4704,7 @@ int pg_conv4x4_bwd_big_x(const float* small, int ld_small, const float* big, int
     const int u_valid = x ? x->u_valid : 0;
     if (Uext && !aligned16(Uext)) return PG_EINVAL;
     if (ld_small < gg->Ca || ld_big < gg->Cb || ld_dsmall < gg->Ca) return PG_EINVAL;
+    if (Uext && pg_conv_u_bytes(gg, 0, algo, ws ? ws_bytes : 0) == 0) return PG_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const Geom g = to_geom(gg);
     const Tune tune = tune_of(algo);

@@ -119,6 +119,38 @@ def _empty(N, H, W, C, spec):
     return _store(torch.zeros(N, C, H, W, dtype=torch.float64, device='cuda') * float('nan'), spec)
 
 
+class _Contained:
+    """Containment at the bench geometries, on the buffers _store made: every element of an output buffer outside its slice is still
+    what _store put there (NaN; zero in 8-channel bf16 pixels) -- the other channels of each pixel and the +64 tail -- and every input
+    buffer is bit for bit what it was."""
+
+    def __init__(self, key):
+        self.key, self.ins, self.outs = key, [], []
+
+    @staticmethod
+    def _bits(t):
+        return t.view(torch.int16 if t.dtype == torch.bfloat16 else torch.int32)
+
+    def inp(self, v):
+        self.ins.append((v, self._bits(v.t).clone()))
+        return v
+
+    def out(self, v, spec):
+        self.outs.append((v, bool(spec.pad8)))
+        return v
+
+    def check(self, what=''):
+        for v, zero in self.outs:
+            n = v.npix * v.ld
+            body = v.t[:n].view(-1, v.ld)
+            for name, r in (('tail', v.t[n:]), ('channels before the slice', body[:, :v.off]), ('channels after the slice', body[:, v.off + v.C:])):
+                if r.numel():
+                    ok = (r == 0).all() if zero else r.isnan().all()
+                    assert ok.item(), (self.key, what, 'output buffer written outside its slice: ' + name)
+        for v, snap in self.ins:
+            assert torch.equal(self._bits(v.t), snap), (self.key, what, 'input buffer modified')
+
+
 def _read(v):
     n = v.N * v.H * v.W * v.ld          # (views made by _store: off < ld)
     return v.t[:n].view(v.N, v.H, v.W, v.ld)[..., v.off:v.off + v.C].permute(0, 3, 1, 2).double()
@@ -165,14 +197,18 @@ def test_bench_layer_call_vs_float64(cs):
     Hs, Ws = T.Hs, T.Ws
     P = T.W.permute(2, 3, 0, 1).contiguous().reshape(-1).float()
     tol_f, tol_w = 2e-5, 3e-5
-    sync = torch.cuda.synchronize
+    guard = _Contained(cs.key)
+
+    def sync():
+        torch.cuda.synchronize()
+        guard.check()           # after each call: outputs written inside their slices only, inputs unchanged
 
     if cs.op == 'b2s':
-        src = _store(T.big, cs.big)
+        src = guard.inp(_store(T.big, cs.big))
         bias = T.bias_a.float() if cs.bias else None
         lin = T.ref('b2s') + (T.bias_a.view(1, -1, 1, 1) if cs.bias else 0)
         want = _act64(lin, cs.act)
-        out = _empty(N, Hs, Ws, Ca, cs.small)
+        out = guard.out(_empty(N, Hs, Ws, Ca, cs.small), cs.small)
         op.big2small(src, P, 0, bias, 0, out, L.ACT_CODES[cs.act])
         sync()
         ref_out = _read(out)
@@ -183,7 +219,7 @@ def test_bench_layer_call_vs_float64(cs):
             chunks = op.stats_chunks(0, src, out)
             if chunks:                      # K5: InstanceNorm partial sums from the conv epilogue
                 part = torch.full((N * chunks * Ca * 2,), float('nan'), dtype=torch.float64, device='cuda')
-                o2 = _empty(N, Hs, Ws, Ca, cs.small)
+                o2 = guard.out(_empty(N, Hs, Ws, Ca, cs.small), cs.small)
                 op.big2small(src, P, 0, None, 0, o2, part=part)
                 sync()
                 got2 = _read(o2)
@@ -198,17 +234,17 @@ def test_bench_layer_call_vs_float64(cs):
         if nb:                              # per-step weight cache: filled by one call, read by the next
             u = torch.zeros(nb, dtype=torch.uint8, device='cuda')
             for valid in (False, True):
-                o3 = _empty(N, Hs, Ws, Ca, cs.small)
+                o3 = guard.out(_empty(N, Hs, Ws, Ca, cs.small), cs.small)
                 op.big2small(src, P if not valid else torch.zeros_like(P), 0, bias, 0, o3, L.ACT_CODES[cs.act], u_cache=u, u_valid=valid)
                 sync()
                 assert torch.equal(_read(o3), plain), (cs.key, 'u_cache', valid)
 
     elif cs.op == 's2b':
-        src = _store(T.small, cs.small)
+        src = guard.inp(_store(T.small, cs.small))
         bias = T.bias_b.float() if cs.bias else None
         lin = T.ref('s2b') + (T.bias_b.view(1, -1, 1, 1) if cs.bias else 0)
         want = _act64(lin, cs.act)
-        out = _empty(N, Hb, Wb, Cb, cs.big)
+        out = guard.out(_empty(N, Hb, Wb, Cb, cs.big), cs.big)
         op.small2big(src, P, 0, bias, 0, out, L.ACT_CODES[cs.act])
         sync()
         plain = _read(out)
@@ -217,7 +253,7 @@ def test_bench_layer_call_vs_float64(cs):
             chunks = op.stats_chunks(1, src, out)
             if chunks:
                 part = torch.full((N * chunks * Cb * 2,), float('nan'), dtype=torch.float64, device='cuda')
-                o2 = _empty(N, Hb, Wb, Cb, cs.big)
+                o2 = guard.out(_empty(N, Hb, Wb, Cb, cs.big), cs.big)
                 op.small2big(src, P, 0, None, 0, o2, part=part)
                 sync()
                 got2 = _read(o2)
@@ -231,8 +267,8 @@ def test_bench_layer_call_vs_float64(cs):
             t64 = T.t_big if below == 'tanh' else _act64(T.t_big * 3 - 1, 'leakyrelu')
             if bfm:
                 t64 = t64.float().bfloat16().double()
-            tv = _store(t64, cs.big)
-            o4 = _empty(N, Hb, Wb, Cb, cs.big)
+            tv = guard.inp(_store(t64, cs.big))
+            o4 = guard.out(_empty(N, Hb, Wb, Cb, cs.big), cs.big)
             if op.mul_ok(src, o4, tv):
                 op.small2big(src, P, 0, None, 0, o4, mul=(tv, L.ACT_CODES[below]))
                 sync()
@@ -242,13 +278,13 @@ def test_bench_layer_call_vs_float64(cs):
         if nb:
             u = torch.zeros(nb, dtype=torch.uint8, device='cuda')
             for valid in (False, True):
-                o3 = _empty(N, Hb, Wb, Cb, cs.big)
+                o3 = guard.out(_empty(N, Hb, Wb, Cb, cs.big), cs.big)
                 op.small2big(src, P if not valid else torch.zeros_like(P), 0, bias, 0, o3, L.ACT_CODES[cs.act], u_cache=u, u_valid=valid)
                 sync()
                 assert torch.equal(_read(o3), plain), (cs.key, 'u_cache', valid)
 
     elif cs.op == 'wgrad':
-        vs, vb = _store(T.small, cs.small), _store(T.big, cs.big)
+        vs, vb = guard.inp(_store(T.small, cs.small)), guard.inp(_store(T.big, cs.big))
         want = T.ref('wgrad')
         dP = torch.full((16 * Ca * Cb,), float('nan'), device='cuda')
         db = torch.full((Ca + 4,), float('nan'), device='cuda') if cs.bias else None
@@ -256,10 +292,11 @@ def test_bench_layer_call_vs_float64(cs):
         sync()
         _check(_unpack(dP, Ca, Cb), want, False, tol_w, cs.key)
         if cs.bias:
+            assert db[Ca:].isnan().all().item(), (cs.key, 'dbias written beyond its Ca floats')
             _check(db[:Ca].double(), T.small.sum((0, 2, 3)), False, tol_w, cs.key + ' dbias')
         if not bfm and op.v_bytes() and E.ConvOp._aligned(vs, vb):       # the forward call's transformed input, handed over
             vk = torch.empty(op.v_bytes(), dtype=torch.uint8, device='cuda')
-            y = _empty(N, Hs, Ws, Ca, cs.small)
+            y = guard.out(_empty(N, Hs, Ws, Ca, cs.small), cs.small)
             op.big2small(vb, P, 0, None, 0, y, v_keep=vk)
             dP2 = torch.full((16 * Ca * Cb,), float('nan'), device='cuda')
             op.wgrad(vs, vb, dP2, 0, v_pre=vk)
@@ -267,9 +304,9 @@ def test_bench_layer_call_vs_float64(cs):
             assert torch.equal(dP2, dP), (cs.key, 'v_keep -> v_pre')
 
     else:   # bwd_big: ConvTranspose2d backward in one call: dW = wgrad(x = small, dy = big), dx = conv(dy, W)
-        vs, vb = _store(T.small, cs.small), _store(T.big, cs.big)
+        vs, vb = guard.inp(_store(T.small, cs.small)), guard.inp(_store(T.big, cs.big))
         dP = torch.full((16 * Ca * Cb,), float('nan'), device='cuda')
-        ds = _empty(N, Hs, Ws, Ca, BL.Operand(cs.small.bf))
+        ds = guard.out(_empty(N, Hs, Ws, Ca, BL.Operand(cs.small.bf)), BL.Operand(cs.small.bf))
         op.bwd_big(vs, vb, P, dP, 0, ds)
         sync()
         _check(_unpack(dP, Ca, Cb), T.ref('wgrad'), False, tol_w, cs.key + ' dW')
