@@ -1115,7 +1115,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 // products a_i b_j with i + j <= 4 are accumulated in fp32 by v_mfma_f32_32x32x16_bf16 (a product of two bf16 values is exact in fp32; the
 // dropped terms a2 b3 + a3 b2 + a3 b3 are <= 2^-25 |a b|, below the rounding of the fp32 accumulation itself).  Six MFMAs of 32 cycles per 16 k
 // instead of eight fp32 MFMAs of 64: 2.67x fewer matrix-pipe cycles for fp32-grade results (measured per kernel against float64: the same
-// 1e-6-level errors as the fp32-MFMA kernel, tests/test_bench_layers_gpu.py).  Operands stay fp32 in HBM: the split costs VALU work per
+// 1e-6-level errors as the fp32-MFMA kernel, tests/test_bench_layers_gpu.py; that each of the six products is really there is what
+// tests/test_exact_gpu.py checks, bit for bit, on operands that reach all three pieces).  Operands stay fp32 in HBM: the split costs VALU work per
 // staged value, not bytes.  Inf / NaN operands: a - RNE_bf16(a) is NaN for an infinite a, so an infinity in an operand gives NaN where
 // the fp32 kernel gives +-inf or NaN -- both poison the step.
 typedef __bf16 s3_bf16x8 __attribute__((ext_vector_type(8)));
