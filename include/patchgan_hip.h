@@ -363,6 +363,27 @@ int pg_batchnorm_eval_coef(const float* running_mean, const float* running_var, 
 int pg_batchnorm_act_bwd(const float* g1, int ld_g1, const float* g2, int ld_g2, const float* y, int ld_y, const float* coef,
                          float* dy, int ld_dy, float* dweight, float* dbias, int N, int HW, int C, int nseg, int train, int act,
                          float drop_p, uint64_t seed, void* ws, size_t ws_bytes, void* stream);
+/* ---- the split form (nn.SyncBatchNorm under data parallelism): "reduce -> coefficients -> apply" with room for the caller's
+ * collective between the reduce and the rest.  mom[(s*C + c)*2 + {0,1}] is a caller-owned fp64 buffer of LOCAL moments per (segment,
+ * channel), merged in a fixed order (bit-reproducible); the caller SUM-reduces it across ranks and passes `count`, the GLOBAL number of
+ * values per (segment, channel).  A LOCAL (N / nseg) * HW of 1 is legal here; count must be > 1.  ws: pg_batchnorm_workspace_bytes of
+ * the LOCAL geometry, REQUIRED as above (pg_batchnorm_moments_fwd with `part` takes none).
+ *   pg_batchnorm_moments_fwd:        mom = (sum y, sum y^2), from the conv's partial sums `part` (as pg_batchnorm_stats) or a pass over y
+ *   pg_batchnorm_coef_from_moments:  coef / bstat (may be NULL) as pg_batchnorm_stats writes them, from mom and count; then
+ *                                    pg_batchnorm_act_apply finishes the forward
+ *   pg_batchnorm_moments_bwd:        mom = (sum dz, sum dz*xhat), dz as pg_batchnorm_act_bwd forms it; dweight / dbias (both or neither)
+ *                                    = the LOCAL sums over the segments, written
+ *   pg_batchnorm_bwd_apply:          dy = scale * (dz - mom0/count - xhat * mom1/count) */
+int pg_batchnorm_moments_fwd(const float* y, int ld_y, const double* part, int chunks, double* mom, int N, int HW, int C, int nseg,
+                             void* ws, size_t ws_bytes, void* stream);
+int pg_batchnorm_coef_from_moments(const double* mom, double count, const float* weight, const float* bias, float eps, float* coef,
+                                   double* bstat, int C, int nseg, void* stream);
+int pg_batchnorm_moments_bwd(const float* g1, int ld_g1, const float* g2, int ld_g2, const float* y, int ld_y, const float* coef,
+                             double* mom, float* dweight, float* dbias, int N, int HW, int C, int nseg, int act, float drop_p,
+                             uint64_t seed, void* ws, size_t ws_bytes, void* stream);
+int pg_batchnorm_bwd_apply(const float* g1, int ld_g1, const float* g2, int ld_g2, const float* y, int ld_y, const float* coef,
+                           const double* mom, double count, float* dy, int ld_dy, int N, int HW, int C, int nseg, int act,
+                           float drop_p, uint64_t seed, void* ws, size_t ws_bytes, void* stream);
 /* Running statistics of up to PG_BN_MAX_LAYERS BatchNorm layers in ONE launch: per layer, `nslots` batch statistics
  * bstat[slot][C][2] folded in slot order (running = (1 - momentum) * running + momentum * batch, in double, stored as float after
  * each), num_batches_tracked += nslots on the device (a replayed hipGraph keeps counting). */

@@ -41,6 +41,7 @@ _p = ctypes.c_void_p
 _i = ctypes.c_int
 _l = ctypes.c_long
 _f = ctypes.c_float
+_d = ctypes.c_double
 _sz = ctypes.c_size_t
 _u64 = ctypes.c_uint64
 _G = ctypes.POINTER(ConvGeom)
@@ -113,6 +114,10 @@ SIGNATURES = {
     'pg_batchnorm_act_apply': (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _f, _u64, _p]),
     'pg_batchnorm_eval_coef': (_i, [_p, _p, _p, _p, _i, _f, _p, _p]),
     'pg_batchnorm_act_bwd': (_i, [_p, _i, _p, _i, _p, _i, _p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _f, _u64, _p, _sz, _p]),
+    'pg_batchnorm_moments_fwd': (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _p, _sz, _p]),
+    'pg_batchnorm_coef_from_moments': (_i, [_p, _d, _p, _p, _f, _p, _p, _i, _i, _p]),
+    'pg_batchnorm_moments_bwd': (_i, [_p, _i, _p, _i, _p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _u64, _p, _sz, _p]),
+    'pg_batchnorm_bwd_apply': (_i, [_p, _i, _p, _i, _p, _i, _p, _p, _d, _p, _i, _i, _i, _i, _i, _i, _f, _u64, _p, _sz, _p]),
     'pg_batchnorm_update_running': (_i, [_i, ctypes.POINTER(BnUpdateItem), _i, _f, _p]),
     'pg_loss_reduce_doubles': (_l, [_i, _i, _i]),
     'pg_loss_fused_max_nc': (_i, []),

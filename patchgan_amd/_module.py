@@ -91,7 +91,12 @@ class FlatParamModule(nn.Module):
         """The BNRun of one pass of this network in its current mode (self.training), or None without BatchNorm layers."""
         if not self.engine.has_bn:
             return None
-        return E.BNRun(self.training, self.bn_bufs, self.bn_scratch, slot, nseg)
+        dist = None
+        if self.engine.sync_bn and self.training:
+            # nn.SyncBatchNorm: the global batch's statistics while the data-parallel path is on; otherwise exactly BatchNorm2d
+            from .parallel import current
+            dist = current()
+        return E.BNRun(self.training, self.bn_bufs, self.bn_scratch, slot, nseg, dist)
 
     def bn_update(self, nslots):
         """Enqueue the running-statistics update of every BatchNorm layer from the batch statistics of slots [0, nslots) (no-op
@@ -129,7 +134,8 @@ class FlatParamModule(nn.Module):
         from . import _lib as L
         algo = {'fp32': L.ALGO_AUTO, 'bf16': L.ALGO_BF16}[precision]
         if precision == 'bf16' and self.engine.has_bn:
-            raise NotImplementedError("patchgan_amd: bf16 precision is not implemented for nn.BatchNorm2d networks (fp32 only)")
+            raise NotImplementedError("patchgan_amd: bf16 precision is not implemented for nn.BatchNorm2d / nn.SyncBatchNorm networks "
+                                      "(fp32 only)")
         self.engine.algo = algo | (self.engine.algo & ~L.ALGO_MASK)
         self.engine._ops = {}
         self.engine._sok = {}

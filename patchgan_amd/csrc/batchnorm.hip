@@ -390,6 +390,157 @@ __global__ __launch_bounds__(256) void k_bn_merge(const double* __restrict__ par
     }
 }
 
+// ---- split form (nn.SyncBatchNorm under data parallelism): a collective sits between the reduce and the rest, so the LOCAL fp64
+// moments of every (segment, channel) leave in a caller-owned buffer mom[(s*C + c)*2 + {0,1}], and the coefficients / the backward
+// apply are formed from the all-reduced moments and the GLOBAL count.  FWD: (sum x, sum x^2).  BWD: (sum dz, sum dz * xhat).
+// Planes the chunk plan does not split: one launch, the first pass of the one-workgroup kernels above (any count >= 1).
+template <int VEC, bool BWD>
+__global__ __launch_bounds__(256) void k_bn_mom_small(const float* __restrict__ y, int ld_y, const float* __restrict__ g1, int ld_g1,
+                                                      const float* __restrict__ g2, int ld_g2, const float* __restrict__ coef,
+                                                      double* __restrict__ mom, float* __restrict__ dw, float* __restrict__ db, int Ns,
+                                                      int HW, int C, int nseg, int G, int act, float drop_p, uint64_t seed) {
+    __shared__ double red[2 * VEC][256];
+    const int tid = threadIdx.x, cu = tid % G, pl = tid / G, PL = 256 / G;
+    const int c0 = (blockIdx.x * G + cu) * VEC;
+    const bool on = c0 < C;
+    const int M = Ns * HW;
+    const float keep_scale = 1.f / (1.f - drop_p);
+    double tw[VEC], tb[VEC];
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) tw[k] = tb[k] = 0.0;
+    for (int s = 0; s < nseg; ++s) {
+        const long p0 = (long)s * M;
+        float mf[VEC], rs[VEC], sc[VEC], sh[VEC];
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {
+            mf[k] = rs[k] = sc[k] = sh[k] = 0.f;
+            if (BWD) {
+                const float* q = coef + ((long)s * C + (on ? c0 + k : 0)) * 4;
+                mf[k] = q[0]; rs[k] = q[1]; sc[k] = q[2]; sh[k] = q[3];
+            }
+        }
+        double s1[VEC], s2[VEC];
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) s1[k] = s2[k] = 0.0;
+        if (on)
+            for (int p = pl; p < M; p += PL) {
+                const long gp = p0 + p;
+                const F<VEC> v = ld<VEC>(y + gp * ld_y + c0);
+                if (!BWD) {
+#pragma unroll
+                    for (int k = 0; k < VEC; ++k) {
+                        const double d = (double)v.v[k];
+                        s1[k] += d;
+                        s2[k] += d * d;
+                    }
+                } else {
+                    F<VEC> g = ld<VEC>(g1 + gp * ld_g1 + c0);
+                    if (g2) {
+                        const F<VEC> h = ld<VEC>(g2 + gp * ld_g2 + c0);
+#pragma unroll
+                        for (int k = 0; k < VEC; ++k) g.v[k] += h.v[k];
+                    }
+#pragma unroll
+                    for (int k = 0; k < VEC; ++k) {
+                        const float dz = bn_dz(g.v[k], v.v[k], sc[k], sh[k], act, drop_p, keep_scale, seed, (uint64_t)gp * C + c0 + k);
+                        s1[k] += (double)dz;
+                        s2[k] += (double)dz * (double)((v.v[k] - mf[k]) * rs[k]);
+                    }
+                }
+            }
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {
+            red[k][tid] = s1[k];
+            red[VEC + k][tid] = s2[k];
+        }
+        bn_lane_tree<2 * VEC>(red, tid, G);
+        if (on && pl == 0) {
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) {
+                double* o = mom + ((long)s * C + c0 + k) * 2;
+                o[0] = red[k][cu];
+                o[1] = red[VEC + k][cu];
+                tb[k] += red[k][cu];
+                tw[k] += red[VEC + k][cu];
+            }
+        }
+        __syncthreads();
+    }
+    if (BWD && on && pl == 0 && dw) {
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {
+            dw[c0 + k] = (float)tw[k];
+            db[c0 + k] = (float)tb[k];
+        }
+    }
+}
+
+// k_bn_merge's fixed-order sum of the partials of every (segment, channel), kept as moments.  BWD: dw / db (may be NULL) = the LOCAL
+// sums over the segments (a data-parallel caller SUM-reduces the weight gradients itself).
+template <bool BWD>
+__global__ __launch_bounds__(256) void k_bn_mom_merge(const double* __restrict__ part, int nchunk, int Ns, int nseg, int C,
+                                                      double* __restrict__ mom, float* __restrict__ dw, float* __restrict__ db) {
+    __shared__ double red[2][256];
+    const int tid = threadIdx.x, cc = tid % MERGE_CW, r = tid / MERGE_CW, R = 256 / MERGE_CW;
+    const int c = blockIdx.x * MERGE_CW + cc;
+    const bool on = c < C;
+    const int rows = Ns * nchunk;
+    double tw = 0.0, tb = 0.0;
+    for (int s = 0; s < nseg; ++s) {
+        double s1 = 0.0, s2 = 0.0;
+        if (on) {
+            const double2* p2 = reinterpret_cast<const double2*>(part) + (long)s * rows * C + c;
+            for (int row = r; row < rows; row += R) {
+                const double2 v = p2[(long)row * C];
+                s1 += v.x;
+                s2 += v.y;
+            }
+        }
+        red[0][tid] = s1;
+        red[1][tid] = s2;
+        bn_lane_tree<2>(red, tid, MERGE_CW);
+        if (on && r == 0) {
+            mom[((long)s * C + c) * 2 + 0] = red[0][cc];
+            mom[((long)s * C + c) * 2 + 1] = red[1][cc];
+            tb += red[0][cc];
+            tw += red[1][cc];
+        }
+        __syncthreads();
+    }
+    if (BWD && on && r == 0 && dw) {
+        dw[c] = (float)tw;
+        db[c] = (float)tb;
+    }
+}
+
+// coef / bstat of k_bn_merge<false> from (all-reduced) forward moments and the count M they were summed over
+__global__ void k_bn_coef_mom(const double* __restrict__ mom, double M, const float* __restrict__ w, const float* __restrict__ b,
+                              float eps, float* __restrict__ coef, double* __restrict__ bstat, int C, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int c = i % C;
+    const double mean = mom[(long)i * 2] / M;
+    double var = mom[(long)i * 2 + 1] / M - mean * mean;
+    var = var < 0.0 ? 0.0 : var;
+    const double rstd = 1.0 / sqrt(var + (double)eps);
+    const float sc = (float)((double)w[c] * rstd);
+    float* q = coef + (long)i * 4;
+    q[0] = (float)mean;
+    q[1] = (float)rstd;
+    q[2] = sc;
+    q[3] = (float)((double)b[c] - mean * (double)sc);
+    if (bstat) {
+        bstat[(long)i * 2 + 0] = mean;
+        bstat[(long)i * 2 + 1] = var * M / (M - 1.0);
+    }
+}
+
+// bcoef of k_bn_merge<true> (training mode) from (all-reduced) backward moments: (sum dz / M, sum dz*xhat / M)
+__global__ void k_bn_bcoef_mom(const double* __restrict__ mom, double M, float* __restrict__ bcoef, int n2) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n2) bcoef[i] = (float)(mom[i] / M);
+}
+
 // Apply pass, grid (blocks per sample, N) as InstanceNorm's k_in_apply: where the channel units divide 256 a thread keeps one channel
 // unit (its coefficients in registers) for the whole launch; otherwise the flat form within the sample.
 // FWD: out = dropout(act(x*scale + shift)).  BWD: dy = scale * (dz - bcoef0 - xhat * bcoef1).
@@ -703,6 +854,119 @@ int pg_batchnorm_act_bwd(const float* g1, int ld_g1, const float* g2, int ld_g2,
         hipLaunchKernelGGL(k_bn_bwd_small<1>, dim3((C + G - 1) / G), dim3(256), 0, st, g1, ld_g1, g2, ld_g2, y, ld_y, coef, dy, ld_dy,
                            dweight, dbias, Ns, HW, C, nseg, G, tr, act, drop_p, seed);
     }
+    return pg_launch_status();
+}
+
+// ---- split form: moments -> (the caller's all-reduce of mom) -> coefficients / backward apply.  One workspace rule for the three
+// entry points that take one: pg_batchnorm_workspace_bytes of the LOCAL geometry.
+int pg_batchnorm_moments_fwd(const float* y, int ld_y, const double* part, int chunks, double* mom, int N, int HW, int C, int nseg,
+                             void* ws, size_t ws_bytes, void* stream) {
+    if (bad_geom(N, HW, C, nseg, 1) || !mom || ld_y < C) return PG_EINVAL;
+    if (part ? chunks <= 0 : !y) return PG_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    const int Ns = N / nseg;
+    if (!part) {
+        if (ws_short(N, HW, C, nseg, ws, ws_bytes)) return PG_EWORKSPACE;
+        const bool vec = (C % 4 == 0) && (ld_y % 4 == 0) && al16(y);
+        const BnPlan p = bn_plan(N, HW, C, vec ? 4 : 1);
+        if (p.nchunk == 1) {
+            if (vec) {
+                const int units = C / 4, G = bn_small_group(units);
+                hipLaunchKernelGGL((k_bn_mom_small<4, false>), dim3((units + G - 1) / G), dim3(256), 0, st, y, ld_y, nullptr, 0, nullptr,
+                                   0, nullptr, mom, nullptr, nullptr, Ns, HW, C, nseg, G, 0, 0.f, 0ull);
+            } else {
+                const int G = bn_small_group(C);
+                hipLaunchKernelGGL((k_bn_mom_small<1, false>), dim3((C + G - 1) / G), dim3(256), 0, st, y, ld_y, nullptr, 0, nullptr, 0,
+                                   nullptr, mom, nullptr, nullptr, Ns, HW, C, nseg, G, 0, 0.f, 0ull);
+            }
+            return pg_launch_status();
+        }
+        const dim3 grid(p.groups, p.nchunk, N);
+        if (vec)
+            hipLaunchKernelGGL((k_bn_partial<4, false, false>), grid, dim3(256), 0, st, y, ld_y, nullptr, 0, nullptr, 0, nullptr,
+                               (double*)ws, Ns, HW, C, p.G, p.ppc, 0, 0.f, 0ull);
+        else
+            hipLaunchKernelGGL((k_bn_partial<1, false, false>), grid, dim3(256), 0, st, y, ld_y, nullptr, 0, nullptr, 0, nullptr,
+                               (double*)ws, Ns, HW, C, p.G, p.ppc, 0, 0.f, 0ull);
+        if (hipGetLastError() != hipSuccess) return PG_ELAUNCH;
+        part = (const double*)ws;
+        chunks = p.nchunk;
+    }
+    hipLaunchKernelGGL((k_bn_mom_merge<false>), dim3((C + MERGE_CW - 1) / MERGE_CW), dim3(256), 0, st, part, chunks, Ns, nseg, C, mom,
+                       (float*)nullptr, (float*)nullptr);
+    return pg_launch_status();
+}
+
+int pg_batchnorm_coef_from_moments(const double* mom, double count, const float* weight, const float* bias, float eps, float* coef,
+                                   double* bstat, int C, int nseg, void* stream) {
+    if (!mom || !weight || !bias || !coef || C <= 0 || nseg < 1 || nseg > 2 || !(count > 1.0)) return PG_EINVAL;
+    const int n = nseg * C;
+    hipLaunchKernelGGL(k_bn_coef_mom, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, mom, count, weight, bias, eps, coef,
+                       bstat, C, n);
+    return pg_launch_status();
+}
+
+int pg_batchnorm_moments_bwd(const float* g1, int ld_g1, const float* g2, int ld_g2, const float* y, int ld_y, const float* coef,
+                             double* mom, float* dweight, float* dbias, int N, int HW, int C, int nseg, int act, float drop_p,
+                             uint64_t seed, void* ws, size_t ws_bytes, void* stream) {
+    if (bad_geom(N, HW, C, nseg, 1) || !g1 || !y || !coef || !mom || ld_g1 < C || ld_y < C || (g2 && ld_g2 < C)) return PG_EINVAL;
+    if ((!dweight) != (!dbias) || drop_p < 0.f || drop_p >= 1.f || act < 0 || act > PG_ACT_SIGMOID) return PG_EINVAL;
+    if (ws_short(N, HW, C, nseg, ws, ws_bytes)) return PG_EWORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const int Ns = N / nseg;
+    const bool vec = (C % 4 == 0) && (ld_g1 % 4 == 0) && (ld_y % 4 == 0) && al16(g1) && al16(y) && (!g2 || ((ld_g2 % 4 == 0) && al16(g2)));
+    const BnPlan p = bn_plan(N, HW, C, vec ? 4 : 1);
+    if (p.nchunk == 1) {
+        if (vec) {
+            const int units = C / 4, G = bn_small_group(units);
+            hipLaunchKernelGGL((k_bn_mom_small<4, true>), dim3((units + G - 1) / G), dim3(256), 0, st, y, ld_y, g1, ld_g1, g2, ld_g2, coef,
+                               mom, dweight, dbias, Ns, HW, C, nseg, G, act, drop_p, seed);
+        } else {
+            const int G = bn_small_group(C);
+            hipLaunchKernelGGL((k_bn_mom_small<1, true>), dim3((C + G - 1) / G), dim3(256), 0, st, y, ld_y, g1, ld_g1, g2, ld_g2, coef, mom,
+                               dweight, dbias, Ns, HW, C, nseg, G, act, drop_p, seed);
+        }
+        return pg_launch_status();
+    }
+    double* part = (double*)ws;
+    const dim3 grid(p.groups, p.nchunk, N);
+#define BN_GO(V, ...)                                                                                            \
+    do {                                                                                                         \
+        if (g2) hipLaunchKernelGGL((k_bn_partial<V, true, true>), grid, dim3(256), 0, st, __VA_ARGS__);          \
+        else hipLaunchKernelGGL((k_bn_partial<V, true, false>), grid, dim3(256), 0, st, __VA_ARGS__);            \
+    } while (0)
+    if (vec) BN_GO(4, y, ld_y, g1, ld_g1, g2, ld_g2, coef, part, Ns, HW, C, p.G, p.ppc, act, drop_p, seed);
+    else BN_GO(1, y, ld_y, g1, ld_g1, g2, ld_g2, coef, part, Ns, HW, C, p.G, p.ppc, act, drop_p, seed);
+#undef BN_GO
+    if (hipGetLastError() != hipSuccess) return PG_ELAUNCH;
+    hipLaunchKernelGGL((k_bn_mom_merge<true>), dim3((C + MERGE_CW - 1) / MERGE_CW), dim3(256), 0, st, (const double*)part, p.nchunk, Ns,
+                       nseg, C, mom, dweight, dbias);
+    return pg_launch_status();
+}
+
+int pg_batchnorm_bwd_apply(const float* g1, int ld_g1, const float* g2, int ld_g2, const float* y, int ld_y, const float* coef,
+                           const double* mom, double count, float* dy, int ld_dy, int N, int HW, int C, int nseg, int act,
+                           float drop_p, uint64_t seed, void* ws, size_t ws_bytes, void* stream) {
+    if (bad_geom(N, HW, C, nseg, 1) || !g1 || !y || !coef || !mom || !dy || ld_g1 < C || ld_y < C || ld_dy < C || (g2 && ld_g2 < C))
+        return PG_EINVAL;
+    if (!(count > 1.0) || drop_p < 0.f || drop_p >= 1.f || act < 0 || act > PG_ACT_SIGMOID) return PG_EINVAL;
+    if (ws_short(N, HW, C, nseg, ws, ws_bytes)) return PG_EWORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const int Ns = N / nseg;
+    const bool vec = (C % 4 == 0) && (ld_g1 % 4 == 0) && (ld_y % 4 == 0) && (ld_dy % 4 == 0) && al16(g1) && al16(y) && al16(dy) &&
+                     (!g2 || ((ld_g2 % 4 == 0) && al16(g2)));
+    float* bcoef = (float*)ws;
+    const int n2 = nseg * C * 2;
+    hipLaunchKernelGGL(k_bn_bcoef_mom, dim3((n2 + 255) / 256), dim3(256), 0, st, mom, count, bcoef, n2);
+    if (hipGetLastError() != hipSuccess) return PG_ELAUNCH;
+#define BN_GO(V, GRID, ...)                                                                                      \
+    do {                                                                                                         \
+        if (g2) hipLaunchKernelGGL((k_bn_apply<V, true, true>), GRID, dim3(256), 0, st, __VA_ARGS__);            \
+        else hipLaunchKernelGGL((k_bn_apply<V, true, false>), GRID, dim3(256), 0, st, __VA_ARGS__);              \
+    } while (0)
+    if (vec) BN_GO(4, bn_apply_grid(N, HW, C / 4), y, ld_y, g1, ld_g1, g2, ld_g2, coef, bcoef, dy, ld_dy, Ns, HW, C, act, drop_p, seed);
+    else BN_GO(1, bn_apply_grid(N, HW, C), y, ld_y, g1, ld_g1, g2, ld_g2, coef, bcoef, dy, ld_dy, Ns, HW, C, act, drop_p, seed);
+#undef BN_GO
     return pg_launch_status();
 }
 

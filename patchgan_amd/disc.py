@@ -35,7 +35,7 @@ class _DiscFn(torch.autograd.Function):
 
 class Discriminator(FlatParamModule, Transferable):
     """Discriminator(input_nc, ndf=64, n_layers=3, norm=False, norm_layer=InstanceNorm2d) -- reference disc.py:8.  norm_layer:
-    nn.InstanceNorm2d or nn.BatchNorm2d (its defaults)."""
+    nn.InstanceNorm2d, nn.BatchNorm2d or -- for data parallelism: the global batch's statistics -- nn.SyncBatchNorm (their defaults)."""
 
     def __init__(self, input_nc, ndf=64, n_layers=3, norm=False, norm_layer=nn.InstanceNorm2d):
         super().__init__()

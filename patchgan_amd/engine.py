@@ -753,18 +753,49 @@ class BNRun:
     calls .eval() only in its validation loop).  train: batch statistics per SEGMENT (nseg runs of N / nseg consecutive samples: the
     discriminator's pass over din[2N] stands for two calls of the reference, trainer.py:97,99), segment s's (mean, unbiased var) into
     the scratch at slot + s, folded into the running statistics later by bn_update_running in slot order.  eval: the running
-    statistics of `bufs`, nothing is written."""
-    __slots__ = ('train', 'bufs', 'scratch', 'slot', 'nseg')
+    statistics of `bufs`, nothing is written.
+    dist: the parallel.Dist of a SyncBatchNorm network while the data-parallel path is on (else None) -- a training-mode pass then
+    normalises with the statistics of the GLOBAL batch (global segment s = every rank's segment s): each layer's local fp64 moments
+    are SUM-reduced across ranks between the reduce and the rest (_bn_allreduce), forward and backward."""
+    __slots__ = ('train', 'bufs', 'scratch', 'slot', 'nseg', 'dist')
 
-    def __init__(self, train, bufs, scratch, slot=0, nseg=1):
+    def __init__(self, train, bufs, scratch, slot=0, nseg=1, dist=None):
         self.train, self.bufs, self.scratch, self.slot, self.nseg = bool(train), bufs, scratch, slot, nseg if train else 1
+        self.dist = dist if (train and dist is not None and dist.on) else None
         assert slot + self.nseg <= BN_SLOTS
 
 
-def _bn_check(y, nseg):
-    if (y.N // nseg) * y.HW <= 1:
+def _bn_check(y, nseg, world=1):
+    if (y.N // nseg) * world * y.HW <= 1:
         raise ValueError(f"Expected more than 1 value per channel when training, got input size "
-                         f"torch.Size([{y.N // nseg}, {y.C}, {y.H}, {y.W}])")
+                         f"torch.Size([{y.N // nseg * world}, {y.C}, {y.H}, {y.W}])")
+
+
+def _bn_allreduce(dist, mom):
+    """SUM of one layer's moments across ranks: on the comm stream behind the kernel that wrote them, and the consuming stream waits
+    for it at once (the next kernel reads them) -- no host round trip.  Issued in layer order, the same on every rank."""
+    dist.all_reduce_side(mom)()
+
+
+def _bn_sync_fwd(lib, l, bn, flat, y, out, act, drop_p, seed, part, chunks, coef, st):
+    """The split route of batchnorm_act_fwd: local moments -> all-reduce -> coefficients from the global moments -> apply."""
+    w, b = L.ptr(flat, l.g_off), L.ptr(flat, l.be_off)
+    mom = torch.empty(bn.nseg * y.C * 2, dtype=torch.float64, device=y.t.device)
+    if part is not None:
+        L.check(lib.pg_batchnorm_moments_fwd(None, y.ld, part.data_ptr(), chunks, mom.data_ptr(), y.N, y.HW, y.C, bn.nseg, None, 0, st),
+                'pg_batchnorm_moments_fwd')
+    else:
+        ws = _workspace(int(lib.pg_batchnorm_workspace_bytes(y.N, y.HW, y.C, bn.nseg)), y.t.device)
+        L.check(lib.pg_batchnorm_moments_fwd(y.ptr(), y.ld, None, 0, mom.data_ptr(), y.N, y.HW, y.C, bn.nseg, ws.data_ptr(), ws.numel(),
+                                             st), 'pg_batchnorm_moments_fwd')
+    _bn_allreduce(bn.dist, mom)
+    count = float((y.N // bn.nseg) * bn.dist.world * y.HW)
+    bstat = L.ptr(bn.scratch, l.bs_off + bn.slot * y.C * 2)
+    L.check(lib.pg_batchnorm_coef_from_moments(mom.data_ptr(), count, w, b, BN_EPS, coef.data_ptr(), bstat, y.C, bn.nseg, st),
+            'pg_batchnorm_coef_from_moments')
+    L.check(lib.pg_batchnorm_act_apply(y.ptr(), y.ld, out.ptr(), out.ld, coef.data_ptr(), y.N, y.HW, y.C, bn.nseg, act, drop_p,
+                                       seed & _MASK64, st), 'pg_batchnorm_act_apply')
+    return coef
 
 
 def batchnorm_act_fwd(l, bn, flat, y, out, act, drop_p=0.0, seed=0, part=None, chunks=0):
@@ -780,6 +811,9 @@ def batchnorm_act_fwd(l, bn, flat, y, out, act, drop_p=0.0, seed=0, part=None, c
         L.check(lib.pg_batchnorm_act_apply(y.ptr(), y.ld, out.ptr(), out.ld, coef.data_ptr(), y.N, y.HW, y.C, 1, act, drop_p,
                                            seed & _MASK64, st), 'pg_batchnorm_act_apply')
         return coef
+    if bn.dist is not None:
+        _bn_check(y, bn.nseg, bn.dist.world)
+        return _bn_sync_fwd(lib, l, bn, flat, y, out, act, drop_p, seed, part, chunks, coef, st)
     _bn_check(y, bn.nseg)
     bstat = L.ptr(bn.scratch, l.bs_off + bn.slot * y.C * 2)
     if part is not None:
@@ -802,7 +836,7 @@ def conv_batchnorm_act(op, opcode, src, flat, l, y, out, bn, act, drop_p=0.0, se
     if u_cache is not None:
         kw.update(u_cache=u_cache, u_valid=u_valid)
     if bn.train:
-        _bn_check(y, bn.nseg)
+        _bn_check(y, bn.nseg, bn.dist.world if bn.dist is not None else 1)
     chunks = op.stats_chunks(opcode, src, y) if (FUSE_IN_STATS and bn.train) else 0
     if chunks:
         part = torch.empty(y.N * chunks * y.C * 2, dtype=torch.float64, device=y.t.device)
@@ -812,13 +846,28 @@ def conv_batchnorm_act(op, opcode, src, flat, l, y, out, bn, act, drop_p=0.0, se
     return batchnorm_act_fwd(l, bn, flat, y, out, act, drop_p, seed)
 
 
-def batchnorm_act_bwd(l, train, nseg, gflat, g1, g2, y, coef, dy, act, drop_p=0.0, seed=0):
-    """Backward of batchnorm_act_fwd (train / nseg: those of its pass).  gflat None: no weight / bias gradients (the generator step's
-    pass through D); else they are WRITTEN into gflat."""
+def batchnorm_act_bwd(l, train, nseg, gflat, g1, g2, y, coef, dy, act, drop_p=0.0, seed=0, dist=None):
+    """Backward of batchnorm_act_fwd (train / nseg / dist: those of its pass).  gflat None: no weight / bias gradients (the generator
+    step's pass through D); else they are WRITTEN into gflat.  dist (a training-mode pass that normalised with the global batch's
+    statistics): the split route -- local moments -> all-reduce -> apply with the global count; the weight / bias gradients stay the
+    LOCAL sums (the flat gradient is SUM-reduced across ranks afterwards like every other parameter's)."""
     lib = L.load()
     nseg = nseg if train else 1
     ws = _workspace(int(lib.pg_batchnorm_workspace_bytes(y.N, y.HW, y.C, nseg)), y.t.device)
     dw, db = (L.ptr(gflat, l.g_off), L.ptr(gflat, l.be_off)) if gflat is not None else (None, None)
+    if train and dist is not None:
+        st = _stream()
+        g2p, g2l = (g2.ptr(), g2.ld) if g2 is not None else (None, 0)
+        mom = torch.empty(nseg * y.C * 2, dtype=torch.float64, device=y.t.device)
+        L.check(lib.pg_batchnorm_moments_bwd(g1.ptr(), g1.ld, g2p, g2l, y.ptr(), y.ld, coef.data_ptr(), mom.data_ptr(), dw, db, y.N, y.HW,
+                                             y.C, nseg, act, drop_p, seed & _MASK64, ws.data_ptr(), ws.numel(), st),
+                'pg_batchnorm_moments_bwd')
+        _bn_allreduce(dist, mom)
+        count = float((y.N // nseg) * dist.world * y.HW)
+        L.check(lib.pg_batchnorm_bwd_apply(g1.ptr(), g1.ld, g2p, g2l, y.ptr(), y.ld, coef.data_ptr(), mom.data_ptr(), count, dy.ptr(),
+                                           dy.ld, y.N, y.HW, y.C, nseg, act, drop_p, seed & _MASK64, ws.data_ptr(), ws.numel(), st),
+                'pg_batchnorm_bwd_apply')
+        return
     L.check(lib.pg_batchnorm_act_bwd(g1.ptr(), g1.ld, g2.ptr() if g2 is not None else None, g2.ld if g2 is not None else 0,
                                      y.ptr(), y.ld, coef.data_ptr(), dy.ptr(), dy.ld, dw, db, y.N, y.HW, y.C, nseg, 1 if train else 0,
                                      act, drop_p, seed & _MASK64, ws.data_ptr(), ws.numel(), _stream()), 'pg_batchnorm_act_bwd')
@@ -1004,14 +1053,24 @@ def assign_offsets(layers):
 
 
 def norm_kind_of(norm_layer, who):
-    """'instance' | 'batch' for a constructor's norm_layer argument; anything else raises NotImplementedError.  BatchNorm2d is taken
-    with its defaults only (eps 1e-5, momentum 0.1, affine, tracked running statistics)."""
+    """'instance' | 'batch' | 'syncbatch' for a constructor's norm_layer argument; anything else raises NotImplementedError.
+    BatchNorm2d and SyncBatchNorm are taken with their defaults only (eps 1e-5, momentum 0.1, affine, tracked running statistics).
+    'syncbatch' is 'batch' in every respect (layout, buffers, scratch, kernels) plus "synchronise the batch statistics across ranks
+    while the data-parallel path is on" (layer_kind, BNRun.dist)."""
     if norm_layer is nn.InstanceNorm2d:
         return 'instance'
     if norm_layer is nn.BatchNorm2d:
         return 'batch'
-    raise NotImplementedError(f"{who} implements norm_layer=nn.InstanceNorm2d or nn.BatchNorm2d (with their defaults) only, "
+    if norm_layer is nn.SyncBatchNorm:
+        return 'syncbatch'
+    raise NotImplementedError(f"{who} implements norm_layer=nn.InstanceNorm2d or nn.BatchNorm2d (with their defaults) only -- and "
+                              f"nn.SyncBatchNorm, BatchNorm2d with the global batch's statistics under data parallelism --, "
                               f"got {norm_layer!r}")
+
+
+def layer_kind(norm_kind):
+    """The LayerSpec.norm_kind of a network built with norm_kind: a SyncBatchNorm network's layers ARE BatchNorm layers."""
+    return 'batch' if norm_kind == 'syncbatch' else norm_kind
 
 
 def param_keys(layers):
@@ -1178,6 +1237,8 @@ class GeneratorEngine(_WeightPrep):
     def __init__(self, input_nc, output_nc, nf, activation, final_act, use_dropout, algo=None, norm_kind='instance'):
         self.input_nc, self.output_nc, self.nf = input_nc, output_nc, nf
         self.activation, self.final_act, self.use_dropout = activation, final_act, use_dropout
+        self.sync_bn = norm_kind == 'syncbatch'
+        norm_kind = layer_kind(norm_kind)
         self.enc, self.dec = unet_layers(input_nc, output_nc, nf, activation, final_act, use_dropout, norm_kind)
         self.layers = self.enc + self.dec
         self.nparams = assign_offsets(self.layers)
@@ -1244,7 +1305,7 @@ class GeneratorEngine(_WeightPrep):
         F = [l.a for l in self.enc]
         c = GenContext()
         c.N, c.H, c.W, c.xin, c.gen_out, c.seed, c.train, c.sample0 = N, H, W, xin, gen_out, seed, train, sample0
-        c.bn_train, c.bn_nseg = (bn.train, bn.nseg) if bn is not None else (False, 1)
+        c.bn_train, c.bn_nseg, c.bn_dist = (bn.train, bn.nseg, bn.dist) if bn is not None else (False, 1, None)
         # cat_i (i = 1..6): input of decoder i = [dec_{i-1} out | enc_{6-i} out]
         # bf16 activation storage: every interior activation (conv outputs, normalised outputs, their gradients) is a bf16 tensor;
         # the image-facing tensors (x, enc0's conv output, the generator output and its gradient) stay fp32 and the InstanceNorm /
@@ -1329,7 +1390,8 @@ class GeneratorEngine(_WeightPrep):
         start all-reducing finished buckets under the rest of the backward pass."""
         def done(l):
             if on_ready is not None:
-                on_ready(l.p_off, l.p_off + 16 * l.a * l.b)
+                # (a BatchNorm layer's weight / bias gradients follow its conv block in the flat buffer and are written before it)
+                on_ready(l.p_off, l.be_off + (l.cout + 3) // 4 * 4 if l.bn else l.p_off + 16 * l.a * l.b)
         # defer_join: the caller joins the second stream itself (side_join()) before it reads the weight gradients -- the trainer puts
         # the discriminator's forward pass, which needs none of them, in between
         _side_begin(not self.act_bf or BF16_WGRAD_SIDE)       # (bf16: the two chains contend for the L1 path: 5.87 -> 5.94 ms at cfg4)
@@ -1370,7 +1432,7 @@ class GeneratorEngine(_WeightPrep):
             if l.bn:
                 drop = 0.2 if (c.train and l.dropout) else 0.0
                 batchnorm_act_bwd(l, c.bn_train, c.bn_nseg, gflat, g, None, c.yd[i], c.statsd[i], dy, act, drop,
-                                  _shift_seed(_mix_seed(c.seed, 2, i), c.sample0 * dy.HW * dy.C))
+                                  _shift_seed(_mix_seed(c.seed, 2, i), c.sample0 * dy.HW * dy.C), dist=c.bn_dist)
             elif l.norm:
                 drop = 0.2 if (c.train and l.dropout) else 0.0
                 instnorm_act_bwd(g, None, c.yd[i], c.statsd[i], dy, act, drop,
@@ -1404,7 +1466,7 @@ class GeneratorEngine(_WeightPrep):
             drop = 0.2 if (c.train and l.dropout) else 0.0
             if l.bn:
                 batchnorm_act_bwd(l, c.bn_train, c.bn_nseg, gflat, g_main, dskip[j] if j < 6 else None, c.y[j], c.stats[j], dy, act, drop,
-                                  _shift_seed(_mix_seed(c.seed, 1, j), c.sample0 * dy.HW * dy.C))
+                                  _shift_seed(_mix_seed(c.seed, 1, j), c.sample0 * dy.HW * dy.C), dist=c.bn_dist)
             else:
                 instnorm_act_bwd(g_main, dskip[j] if j < 6 else None, c.y[j], c.stats[j], dy, act, drop,
                                  _shift_seed(_mix_seed(c.seed, 1, j), c.sample0 * dy.HW * dy.C))
@@ -1456,6 +1518,8 @@ class DiscriminatorEngine(_WeightPrep):
 
     def __init__(self, input_nc, ndf, n_layers, norm, algo=None, norm_kind='instance'):
         self.input_nc, self.ndf, self.n_layers, self.norm = input_nc, ndf, n_layers, norm
+        self.sync_bn = bool(norm) and norm_kind == 'syncbatch'
+        norm_kind = layer_kind(norm_kind)
         self.layers = disc_layers(input_nc, ndf, n_layers, norm, norm_kind)
         self.nparams = assign_offsets(self.layers)
         self.has_bn = bool(norm) and norm_kind == 'batch'
@@ -1501,7 +1565,7 @@ class DiscriminatorEngine(_WeightPrep):
         dev = flat.device
         c = DiscContext()
         c.din, c.N, c.H, c.W = din, din.N, din.H, din.W
-        c.bn_train, c.bn_nseg = (bn.train, bn.nseg) if bn is not None else (False, 1)
+        c.bn_train, c.bn_nseg, c.bn_dist = (bn.train, bn.nseg, bn.dist) if bn is not None else (False, 1, None)
         c.t, c.stats, c.a, c.v, c.src = [], [], [], [], []
         # bf16 activation storage: the tensors between the first and the last layer are bf16; the input (x | mask), the first
         # layer's conv output (4-channel input: generic kernel) and the 1-channel head stay fp32
@@ -1569,7 +1633,7 @@ class DiscriminatorEngine(_WeightPrep):
                     dt = View.alloc(c.N, op.Hs, op.Ws, l.a, dev, bf=inner)
                     if l.bn:
                         batchnorm_act_bwd(l, c.bn_train, c.bn_nseg, gflat if need_wgrad else None, g, None, c.t[li], c.stats[li], dt,
-                                          L.ACT_NONE)
+                                          L.ACT_NONE, dist=c.bn_dist)
                     else:
                         instnorm_act_bwd(g, None, c.t[li], c.stats[li], dt, L.ACT_NONE)
                     g = dt

@@ -15,7 +15,13 @@ What is exchanged per step:
     can seed its local gradient (engine.loss_value_and_grad); issued on the comm stream too, under the
     discriminator's forward pass over the fake batch.
   * the step's loss scalars for logging.
-InstanceNorm statistics are per sample: nothing else crosses ranks.
+  * nn.SyncBatchNorm networks only: per BatchNorm layer and pass, forward and backward, ONE fp64 tensor of nseg * C * 2 local moments
+    ((sum x, sum x^2); (sum dz, sum dz * xhat)) is SUM-reduced between the layer's reduce and the rest (engine._bn_allreduce), so every
+    rank normalises with the statistics of the GLOBAL batch.  On the comm stream behind the kernel that wrote the moments, waited
+    for at once by the compute stream (the next kernel reads them): these collectives are on the critical path, a few KB each, and a
+    step issues them from one stream in the layer order of the host code -- the same on every rank.
+InstanceNorm statistics are per sample, and nn.BatchNorm2d networks are refused under a group (Trainer.batch): nothing else crosses
+ranks.
 """
 import os
 

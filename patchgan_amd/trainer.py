@@ -245,9 +245,11 @@ class Trainer:
         if dev.type != 'cuda':
             raise RuntimeError("patchgan_amd.Trainer needs the networks on a HIP device (generator.to('cuda')); "
                                "there is no CPU path")
-        if (G.engine.has_bn or D.engine.has_bn) and _dist().on:
-            # per-rank batch statistics would break "the sum over ranks is the large batch's step" (parallel.py); no SyncBatchNorm
-            raise NotImplementedError("patchgan_amd: data parallelism is not implemented for nn.BatchNorm2d networks")
+        if any(e.has_bn and not e.sync_bn for e in (G.engine, D.engine)) and _dist().on:
+            # per-rank batch statistics would break "the sum over ranks is the large batch's step" (parallel.py): only the opt-in
+            # nn.SyncBatchNorm layer type, which normalises with the global batch's statistics, passes
+            raise NotImplementedError("patchgan_amd: data parallelism is not implemented for nn.BatchNorm2d networks "
+                                      "(build them with norm_layer=nn.SyncBatchNorm: the same state_dict, global batch statistics)")
         # device-side input pipeline (opt-in, beyond the reference): decoded bytes x uint8 [N,H,W,Cin] + label map y uint8
         # [N,H,W]; `/255.` and the one-hot mask over self.label_values (io.py:42-56) run on the GPU after a 4x smaller H2D
         u8 = isinstance(x, torch.Tensor) and x.dtype == torch.uint8
@@ -567,6 +569,8 @@ class Trainer:
             ts = 'auto' if self.graph == 'auto' else False
         if E.PROFILER is not None or E._exp_env('PATCHGAN_TWO_STREAMS') == '0':
             return False          # (the launch profiler's event pairs keep everything on one stream)
+        if _dist().on and (self.generator.engine.sync_bn or self.discriminator.engine.sync_bn):
+            return False          # (SyncBatchNorm's per-layer collectives are issued from ONE compute stream, in one order on every rank)
         return ts
 
     def _kind_key(self, x, y, u8, dims, train):

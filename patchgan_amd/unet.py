@@ -45,7 +45,8 @@ class _UNetFn(torch.autograd.Function):
 
 class UNet(FlatParamModule, Transferable):
     """UNet(input_nc, output_nc, nf=64, norm_layer=InstanceNorm2d, use_dropout=False, activation='tanh',
-    final_act='softmax') -- reference unet.py:76-78.  norm_layer: nn.InstanceNorm2d or nn.BatchNorm2d (its defaults)."""
+    final_act='softmax') -- reference unet.py:76-78.  norm_layer: nn.InstanceNorm2d, nn.BatchNorm2d or -- for data
+    parallelism: the global batch's statistics -- nn.SyncBatchNorm (their defaults)."""
 
     def __init__(self, input_nc, output_nc, nf=64, norm_layer=nn.InstanceNorm2d, use_dropout=False,
                  activation='tanh', final_act='softmax'):
