@@ -465,6 +465,15 @@ int pg_adam_step(float* p, const float* g, float* m, float* v, long n, float lr,
  * (optimizer.step() of trainer.py:90,107 inside the replayed step). */
 int pg_adam_step_dev(float* p, const float* g, float* m, float* v, long n, float beta1, float beta2, float eps, const float* scalars,
                      void* stream);
+/* Both forms with an exponential moving average of the parameters kept in the same pass: after the Adam update of an element,
+ * ema += (p_new - ema) * (1 - ema_decay) in fp32, from the value just stored to p (5 reads + 4 writes per element; the update followed
+ * by a separate averaging pass takes 4 + 3 and 2 + 1).  p, m and v receive exactly what pg_adam_step / pg_adam_step_dev give them.
+ * `ema` holds n floats and must not alias p, g, m or v; the pointer requirements are those of pg_adam_step (non-NULL, 16-byte
+ * aligned).  ema_decay in [0, 1): PG_EINVAL for a NaN or a value outside, before any launch. */
+int pg_adam_ema_step(float* p, const float* g, float* m, float* v, float* ema, long n, float lr, float beta1, float beta2,
+                     float eps, float bc1, float sqrt_bc2, float ema_decay, void* stream);
+int pg_adam_ema_step_dev(float* p, const float* g, float* m, float* v, float* ema, long n, float beta1, float beta2, float eps,
+                         const float* scalars, float ema_decay, void* stream);
 
 /* ---- layout (the reference is NCHW end to end; trainer.py:55-66) ---------------------------------- */
 int pg_nchw_to_nhwc(const float* src, float* dst, int ld_dst, int N, int C, int H, int W, void* stream);

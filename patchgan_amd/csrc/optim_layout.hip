@@ -18,28 +18,48 @@ __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, 
 
 // DEV: the two step-dependent scalars (lr / bc1, sqrt(bc2)) come from device memory -- the form a captured hipGraph replays with a
 // new Adam step count (pg_adam_step_dev); otherwise they are kernel arguments.  Same arithmetic either way.
-template <bool DEV>
+// EMA: the exponential moving average of the parameters is updated in the same pass, e += (p_new - e) * (1 - decay), from the value
+// just computed for the store (pg_adam_ema_step*: 5 reads + 4 writes per element; Adam and a separate averaging pass take 4 + 3 and
+// 2 + 1).  adam_one is the same code in all four instantiations and the library is built without fp contraction: p, m, v do not
+// depend on EMA.
+template <bool EMA>
+__device__ __forceinline__ void ema_one(float& e, float p_new, float c) {
+    if constexpr (EMA) e = e + (p_new - e) * c;
+}
+
+template <bool DEV, bool EMA>
 __global__ void k_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                       long n, float lr_over_bc1, float beta1, float beta2, float eps, float sqrt_bc2, const float* __restrict__ scal) {
+                       long n, float lr_over_bc1, float beta1, float beta2, float eps, float sqrt_bc2, const float* __restrict__ scal,
+                       float* __restrict__ ema, float ema_decay) {
     if constexpr (DEV) {
         lr_over_bc1 = scal[0];
         sqrt_bc2 = scal[1];
     }
+    const float c = 1.f - ema_decay;
     const long n4 = n >> 2;
     const long stride = (long)gridDim.x * blockDim.x;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += stride) {
         float4 pp = reinterpret_cast<float4*>(p)[i], gg = reinterpret_cast<const float4*>(g)[i];
         float4 mm = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
+        float4 ee = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (EMA) ee = reinterpret_cast<float4*>(ema)[i];
         adam_one(pp.x, gg.x, mm.x, vv.x, lr_over_bc1, beta1, beta2, eps, sqrt_bc2);
         adam_one(pp.y, gg.y, mm.y, vv.y, lr_over_bc1, beta1, beta2, eps, sqrt_bc2);
         adam_one(pp.z, gg.z, mm.z, vv.z, lr_over_bc1, beta1, beta2, eps, sqrt_bc2);
         adam_one(pp.w, gg.w, mm.w, vv.w, lr_over_bc1, beta1, beta2, eps, sqrt_bc2);
+        ema_one<EMA>(ee.x, pp.x, c);
+        ema_one<EMA>(ee.y, pp.y, c);
+        ema_one<EMA>(ee.z, pp.z, c);
+        ema_one<EMA>(ee.w, pp.w, c);
         reinterpret_cast<float4*>(p)[i] = pp;
         reinterpret_cast<float4*>(m)[i] = mm;
         reinterpret_cast<float4*>(v)[i] = vv;
+        if constexpr (EMA) reinterpret_cast<float4*>(ema)[i] = ee;
     }
-    for (long i = (n4 << 2) + blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += stride)
+    for (long i = (n4 << 2) + blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += stride) {
         adam_one(p[i], g[i], m[i], v[i], lr_over_bc1, beta1, beta2, eps, sqrt_bc2);
+        if constexpr (EMA) ema_one<EMA>(ema[i], p[i], c);
+    }
 }
 
 // dst NHWC (pixel stride ld_dst) <- src NCHW; one thread per PIXEL: the C plane reads of a wave are C coalesced rows (one thread per
@@ -209,8 +229,8 @@ int pg_adam_step(float* p, const float* g, float* m, float* v, long n, float lr,
     if (!p || !g || !m || !v || n <= 0 || bc1 <= 0.f || sqrt_bc2 <= 0.f) return PG_EINVAL;
     const uintptr_t al = (uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v;
     if (al & 15) return PG_EINVAL;
-    hipLaunchKernelGGL(k_adam<false>, dim3(blocks_for(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr / bc1,
-                       beta1, beta2, eps, sqrt_bc2, (const float*)nullptr);
+    hipLaunchKernelGGL((k_adam<false, false>), dim3(blocks_for(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr / bc1,
+                       beta1, beta2, eps, sqrt_bc2, (const float*)nullptr, (float*)nullptr, 0.f);
     return pg_launch_status();
 }
 
@@ -219,8 +239,30 @@ int pg_adam_step_dev(float* p, const float* g, float* m, float* v, long n, float
     if (!p || !g || !m || !v || !scalars || n <= 0) return PG_EINVAL;
     const uintptr_t al = (uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v;
     if (al & 15) return PG_EINVAL;
-    hipLaunchKernelGGL(k_adam<true>, dim3(blocks_for(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, 0.f, beta1, beta2, eps,
-                       0.f, scalars);
+    hipLaunchKernelGGL((k_adam<true, false>), dim3(blocks_for(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, 0.f, beta1, beta2, eps,
+                       0.f, scalars, (float*)nullptr, 0.f);
+    return pg_launch_status();
+}
+
+int pg_adam_ema_step(float* p, const float* g, float* m, float* v, float* ema, long n, float lr, float beta1, float beta2, float eps,
+                     float bc1, float sqrt_bc2, float ema_decay, void* stream) {
+    if (!p || !g || !m || !v || !ema || n <= 0 || bc1 <= 0.f || sqrt_bc2 <= 0.f) return PG_EINVAL;
+    if (!(ema_decay >= 0.f && ema_decay < 1.f)) return PG_EINVAL;      // (a NaN fails both comparisons)
+    const uintptr_t al = (uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema;
+    if (al & 15) return PG_EINVAL;
+    hipLaunchKernelGGL((k_adam<false, true>), dim3(blocks_for(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr / bc1,
+                       beta1, beta2, eps, sqrt_bc2, (const float*)nullptr, ema, ema_decay);
+    return pg_launch_status();
+}
+
+int pg_adam_ema_step_dev(float* p, const float* g, float* m, float* v, float* ema, long n, float beta1, float beta2, float eps,
+                         const float* scalars, float ema_decay, void* stream) {
+    if (!p || !g || !m || !v || !ema || !scalars || n <= 0) return PG_EINVAL;
+    if (!(ema_decay >= 0.f && ema_decay < 1.f)) return PG_EINVAL;
+    const uintptr_t al = (uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema;
+    if (al & 15) return PG_EINVAL;
+    hipLaunchKernelGGL((k_adam<true, true>), dim3(blocks_for(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, 0.f, beta1, beta2,
+                       eps, 0.f, scalars, ema, ema_decay);
     return pg_launch_status();
 }
 

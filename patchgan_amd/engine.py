@@ -948,6 +948,30 @@ def adam_step_dev(p, g, m, v, scalars, beta1=0.9, beta2=0.999, eps=1e-8):
                                       scalars.data_ptr(), _stream()), 'pg_adam_step_dev')
 
 
+def check_ema_decay(decay):
+    """The decay of the generator's weight average as a float in [0, 1), or ValueError (what pg_adam_ema_step accepts)."""
+    if isinstance(decay, bool) or not isinstance(decay, (int, float, np.floating, np.integer)):
+        raise ValueError(f"ema_decay must be None or a float in [0, 1), not {decay!r}")
+    d = float(decay)
+    if not (0.0 <= d < 1.0) or not (float(np.float32(d)) < 1.0):        # (the kernel takes it as a float32)
+        raise ValueError(f"ema_decay must be None or a float in [0, 1), not {decay!r}")
+    return d
+
+
+def adam_ema_step(p, g, m, v, ema, step, lr, ema_decay, beta1=0.9, beta2=0.999, eps=1e-8):
+    """adam_step, and in the same pass ema += (p_new - ema) * (1 - ema_decay): the weights' exponential moving average."""
+    bc1 = 1.0 - beta1 ** step
+    bc2 = 1.0 - beta2 ** step
+    L.check(L.load().pg_adam_ema_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ema.data_ptr(), p.numel(), lr, beta1,
+                                      beta2, eps, bc1, math.sqrt(bc2), ema_decay, _stream()), 'pg_adam_ema_step')
+
+
+def adam_ema_step_dev(p, g, m, v, ema, scalars, ema_decay, beta1=0.9, beta2=0.999, eps=1e-8):
+    """adam_ema_step with lr / bc1 and sqrt(bc2) taken from the device tensor `scalars` (adam_step_dev); the decay stays a launch argument."""
+    L.check(L.load().pg_adam_ema_step_dev(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ema.data_ptr(), p.numel(), beta1,
+                                          beta2, eps, scalars.data_ptr(), ema_decay, _stream()), 'pg_adam_ema_step_dev')
+
+
 def tiles_gather(image, size, overlap):
     """reference infer.py:14-35 (n_crop): device image [C, H, W] -> View of the ny*nx overlapping size x size tiles in the
     NHWC batch layout the generator kernels read."""

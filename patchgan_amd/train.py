@@ -47,6 +47,14 @@ def parse_config(config):
     return dataset_params, train_paths, val_paths, split, gen_cfg, disc_cfg
 
 
+def apply_train_params(trainer, train_params):
+    """The trainer settings of the YAML's train_params: loss_type, seg_alpha and -- optional, absent = off -- ema_decay, the decay of
+    the generator's weight average (Trainer.ema_decay; checkpoints then include generator_ema_ep_*.pth)."""
+    trainer.loss_type = train_params['loss_type']
+    trainer.seg_alpha = train_params['seg_alpha']
+    trainer.ema_decay = train_params.get('ema_decay', None)
+
+
 def print_summary(name, module):
     n = sum(p.numel() for p in module.parameters())
     print(f"{name}: {n:,} parameters in {len(list(module.parameters()))} tensors")
@@ -142,6 +150,8 @@ def patchgan_train(argv=None):
     trainer.graph = 'auto'
     if dataset_kwargs.get('device_pipeline', False):
         trainer.label_values = [int(v) for v in np.sort(dataset_kwargs['labels'])]
+    train_params = config['train_params']
+    apply_train_params(trainer, train_params)      # (before a resume: with ema_decay set, load() restores the weight average too)
     if config.get('load_last_checkpoint', False):
         trainer.load_last_checkpoint()
     elif config.get('transfer_learn', {}).get('generator_checkpoint', None) is not None:
@@ -150,9 +160,6 @@ def patchgan_train(argv=None):
         generator.load_transfer_data(torch.load(gen_checkpoint, map_location=device))
         discriminator.load_transfer_data(torch.load(dsc_checkpoint, map_location=device))
 
-    train_params = config['train_params']
-    trainer.loss_type = train_params['loss_type']
-    trainer.seg_alpha = train_params['seg_alpha']
     return trainer.train(train_data, val_data, args.n_epochs,
                          dsc_learning_rate=train_params['disc_learning_rate'],
                          gen_learning_rate=train_params['gen_learning_rate'],

@@ -159,6 +159,14 @@ class Trainer:
     tversky_beta = 0.75
     tversky_gamma = 0.75
 
+    # Exponential moving average of the GENERATOR's weights (opt-in, beyond the reference): None = off -- no buffer, the same launches.
+    # A float in [0, 1): from the next setup_optimizers() on (train() calls it) a second flat buffer follows the weights inside G's
+    # Adam kernel, ema += (w_new - ema) * (1 - ema_decay) (pg_adam_ema_step), and `ema_generator` is a UNet in eval mode whose
+    # parameters are views of that buffer: what one checkpoints and predicts with.  Not optimizer state: a later setup_optimizers() /
+    # train() keeps it, reset_ema() restarts it from the live weights.  Every rank of a data-parallel job applies the same update to
+    # the same all-reduced gradient, so the averages agree without a collective.
+    ema_decay = None
+
     neptune_config = None
     label_values = None      # label list of the dataset, only for the uint8 (device-side) input path of batch()
     gc_freeze = False        # opt-in: gc.collect() + gc.freeze() after training steps 1 and 3 (_settle_gc; process-global)
@@ -226,6 +234,7 @@ class Trainer:
         self._kinds, self.step_times, self.launch_mode = {}, None, None      # per kind of step: warm-step count, the tournament, the decision; step_times = the last tournament's ms per step per candidate
         self._exec = None          # engine.Exec: this trainer's workspaces and second stream (created on the networks' device)
         self._oom_kinds, self.oom_fallbacks = set(), 0      # kinds of step pinned to one stream after an out-of-memory two-stream step
+        self._ema = self._ema_net = None      # the generator's weight average: flat fp32 buffer + the UNet that views it (ema_decay)
 
     # -------------------------------------------------------------------------------------- optimizers
     def setup_optimizers(self, gen_lr=1e-3, dsc_lr=1e-3):
@@ -236,6 +245,51 @@ class Trainer:
         self._adam = (torch.zeros_like(g), torch.zeros_like(g), torch.zeros_like(d), torch.zeros_like(d))
         self._t_g = self._t_d = 0
         self._graphs, self._kinds = {}, {}        # captured steps update the OLD moment buffers
+        self._ema_ensure()
+
+    # -------------------------------------------------------------------------------------- the generator's weight average
+    @property
+    def ema_generator(self):
+        """UNet (eval mode) on the averaged weights; None while ema_decay is None or before the state exists.  Its parameters are
+        views of the buffer G's Adam kernel updates in place, so state_dict() / forward() / predict_image() see the current average.
+        No access hook is needed: Adam(G) is enqueued on the main stream in every launch mode (one stream, two streams -- also when
+        it moves behind the fork of the deferred discriminator pass --, a replayed capture, data parallelism), so whatever reads the
+        average on the current stream is ordered behind the update.  A BatchNorm generator's running statistics are the live
+        generator's own tensors."""
+        return self._ema_net if self.ema_decay is not None else None
+
+    def _ema_now(self):
+        """The decay G's next Adam launch carries: None (plain pg_adam_step) or the validated float."""
+        if self.ema_decay is None:
+            return None
+        decay = E.check_ema_decay(self.ema_decay)
+        return decay if self._ema is not None else None      # (set after setup_optimizers(): it starts with the next one)
+
+    def _ema_ensure(self):
+        """Create the average (a copy of the live weights) if ema_decay asks for one and none exists; keep an existing one on the
+        generator's device, precision, tuning and BatchNorm buffers.  Draws nothing from torch's RNG."""
+        if self.ema_decay is None:
+            return
+        E.check_ema_decay(self.ema_decay)
+        G = self.generator
+        if self._ema is None:
+            self.flush()
+            self._ema = G.flat.detach().clone()
+            self._ema_net = G.twin(self._ema)
+        else:
+            if self._ema.device != G.flat.device:
+                self._ema = self._ema.to(G.flat.device)
+            self._ema_net.follow(G, self._ema)
+
+    def reset_ema(self):
+        """Restart the average from the live generator weights."""
+        if self.ema_decay is None:
+            raise RuntimeError("reset_ema(): Trainer.ema_decay is None (the weight average is off)")
+        fresh = self._ema is None
+        self._ema_ensure()            # (a new average starts as a copy already)
+        if not fresh:
+            self.flush()
+            self._ema.copy_(self.generator.flat)
 
     # -------------------------------------------------------------------------------------- one G+D step
     def batch(self, x, y, train=False):
@@ -274,6 +328,8 @@ class Trainer:
                                f"discriminator input {de.input_nc}")
         if train and self._adam is None:
             self.setup_optimizers(self.gen_lr, self.dsc_lr)
+        if train and self._ema is not None and self.ema_decay is not None:
+            self._ema_ensure()    # (a generator moved / re-tuned since: the average follows)
         self._step += 1
         ex = self._exec
         if ex is None or ex.device != dev:
@@ -543,7 +599,15 @@ class Trainer:
 
     def _adam_step(self, which):
         net, (m, v) = (self.generator, self._adam[0:2]) if which == 'g' else (self.discriminator, self._adam[2:4])
-        if self._adam_dev is not None:
+        decay = self._ema_now() if which == 'g' else None
+        if decay is not None:
+            # the generator's weight average rides in the same kernel (5 reads + 4 writes per element instead of 4 + 3 and a second pass)
+            if self._adam_dev is not None:
+                E.adam_ema_step_dev(net.flat, net.grad_flat, m, v, self._ema, self._adam_dev[0:2], decay)
+            else:
+                self._t_g += 1
+                E.adam_ema_step(net.flat, net.grad_flat, m, v, self._ema, self._t_g, self.gen_lr, decay)
+        elif self._adam_dev is not None:
             # a step being captured: lr / bc1 and sqrt(bc2) come from device memory (written before every replay, _batch_graph)
             E.adam_step_dev(net.flat, net.grad_flat, m, v, self._adam_dev[0:2] if which == 'g' else self._adam_dev[2:4])
         elif which == 'g':
@@ -578,7 +642,8 @@ class Trainer:
         return (bool(train), u8, dims, self.loss_type, float(self.seg_alpha), float(self.tversky_beta), float(self.tversky_gamma),
                 tuple(self.label_values) if self.label_values is not None else None, G.training, D.training,
                 G.engine.algo, bool(G.engine.act_bf), D.engine.algo, bool(D.engine.act_bf), G.flat.data_ptr(), D.flat.data_ptr(),
-                tuple(x.shape), tuple(y.shape), x.dtype, y.dtype, _dist().on)
+                tuple(x.shape), tuple(y.shape), x.dtype, y.dtype, _dist().on,
+                self._ema_now())          # (the decay is a launch argument of Adam(G): a captured step holds the value it was captured with)
 
     def _launch_mode(self, key, train):
         """'eager1' (launch by launch, one stream) | 'eager2' (launch by launch, two streams) | 'graph' (replay) for this step of kind
@@ -745,7 +810,8 @@ class Trainer:
 
     def _graph_ptrs(self):
         G, D = self.generator, self.discriminator
-        return tuple(t.data_ptr() if t is not None else 0 for t in (G.grad_flat, D.grad_flat) + tuple(self._adam))
+        ema = self._ema if self._ema_now() is not None else None
+        return tuple(t.data_ptr() if t is not None else 0 for t in (G.grad_flat, D.grad_flat) + tuple(self._adam) + (ema,))
 
     def _capture(self, key, x, y, u8, dims, two=False):
         class _StepGraph:
@@ -784,7 +850,8 @@ class Trainer:
         # one, so a replay never writes into memory the allocator has handed to someone else -- and it is captured again if the
         # buffers whose CONTENT matters outside the graph (gradients, moments) were replaced (_graph_ptrs).
         st.hold = (E.cur_exec(dev).buffers() + list(G.engine.__dict__.get('_upool', {}).values())
-                   + list(D.engine.__dict__.get('_upool', {}).values()) + [G.grad_flat, D.grad_flat] + list(self._adam))
+                   + list(D.engine.__dict__.get('_upool', {}).values()) + [G.grad_flat, D.grad_flat] + list(self._adam)
+                   + ([self._ema] if self._ema_now() is not None else []))
         st.ptrs = self._graph_ptrs()
         self._graphs[key] = st
         return st
@@ -911,6 +978,12 @@ class Trainer:
         print(f"Saving to {gen_savefile} and {disc_savefile}")
         torch.save(self.generator.state_dict_contiguous(), gen_savefile)
         torch.save(self.discriminator.state_dict_contiguous(), disc_savefile)
+        if self.ema_generator is not None:
+            # the averaged generator: the same keys and shapes as generator_ep_*.pth, so anything that loads one loads the other
+            # (patchgan_infer's checkpoint_paths.generator); the name stays clear of load_last_checkpoint's generator_ep*.pth glob
+            ema_savefile = f'{self.savefolder}/generator_ema_ep_{epoch:03d}.pth'
+            print(f"Saving to {ema_savefile}")
+            torch.save(self.ema_generator.state_dict_contiguous(), ema_savefile)
 
     def load_last_checkpoint(self):
         gen_ck = sorted(glob.glob(self.savefolder + "generator_ep*.pth"))
@@ -920,19 +993,37 @@ class Trainer:
         try:
             assert len(gen_epochs) > 0, "No checkpoints found!"
             start = max(gen_epochs.union(dsc_epochs))
-            self.load(f"{self.savefolder}/generator_ep_{start:03d}.pth", f"{self.savefolder}/discriminator_ep_{start:03d}.pth")
+            ema_save = f"{self.savefolder}/generator_ema_ep_{start:03d}.pth"
+            self.load(f"{self.savefolder}/generator_ep_{start:03d}.pth", f"{self.savefolder}/discriminator_ep_{start:03d}.pth",
+                      ema_save if os.path.exists(ema_save) else None)
             self.start = start + 1
         except Exception as e:
             print(e)
             print("Checkpoints not loaded")
 
-    def load(self, generator_save, discriminator_save):
+    def load(self, generator_save, discriminator_save, ema_save=None):
+        """With ema_decay set, the weight average comes from `ema_save` (a generator_ema_ep_*.pth); without such a file it
+        restarts from the generator weights just loaded."""
         self.flush()
         print(generator_save, discriminator_save)
         dev = self.generator.flat.device
         self.generator.load_state_dict(torch.load(generator_save, map_location=dev))
         self.discriminator.load_state_dict(torch.load(discriminator_save, map_location=dev))
         print(f"Loaded checkpoints from {os.path.basename(generator_save)} and {os.path.basename(discriminator_save)}")
+        if self.ema_decay is not None:
+            self.reset_ema()
+            if ema_save is None:
+                print("No averaged-generator checkpoint given: the weight average restarts from the loaded generator weights")
+            else:
+                # (parameters only: a BatchNorm generator's running statistics are the live generator's tensors, loaded above)
+                sd = torch.load(ema_save, map_location=dev)
+                own = self._ema_net.state_dict()
+                if set(sd) != set(own):
+                    raise RuntimeError(f"{ema_save}: not a state_dict of this generator")
+                with torch.no_grad():
+                    for k, _ in self._ema_net.named_parameters():
+                        own[k].copy_(sd[k])
+                print(f"Loaded the weight average from {os.path.basename(ema_save)}")
 
 
 class _Plateau:

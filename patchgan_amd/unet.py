@@ -58,6 +58,35 @@ class UNet(FlatParamModule, Transferable):
         self._calls = 0
         self._init_flat(self.engine.layers, self.engine.nparams)
 
+    def twin(self, flat):
+        """A second UNet with this one's constructor arguments, precision and tuning, in eval mode, whose parameters are views of
+        the given flat buffer (this network's packed layout and device) and whose BatchNorm running statistics ARE this network's
+        tensors.  Nothing is initialised, so nothing is drawn from torch's RNG (Trainer.ema_generator)."""
+        eng = self.engine
+        t = UNet.__new__(UNet)
+        nn.Module.__init__(t)
+        kind = 'syncbatch' if eng.sync_bn else ('batch' if eng.has_bn else 'instance')
+        t.engine = E.GeneratorEngine(eng.input_nc, eng.output_nc, eng.nf, eng.activation, eng.final_act, eng.use_dropout,
+                                     algo=eng.algo, norm_kind=kind)
+        t._param_keys = E.param_keys(t.engine.layers)
+        t._seed_base, t._calls = self._seed_base, 0
+        t._layers = t.engine.layers
+        t.eval()
+        t.follow(self, flat)
+        return t
+
+    def follow(self, other, flat):
+        """Keep a twin() in step with `other`: its device (flat buffer), BatchNorm buffers, precision and tuning."""
+        if any(getattr(self, k, None) is not v for k, v in (('flat', flat), ('bn_bufs', other.bn_bufs), ('bn_counters', other.bn_counters))):
+            self._bind(flat, other.bn_bufs, other.bn_counters)
+        eng, src = self.engine, other.engine
+        if (eng.algo, eng.act_bf) != (src.algo, src.act_bf):
+            eng.algo, eng.act_bf = src.algo, src.act_bf
+            eng._ops, eng._sok = {}, {}
+            eng.clear_weight_caches()
+        if hasattr(other, 'precision'):
+            self.precision = other.precision
+
     def _next_seed(self):
         self._calls += 1
         return E._mix_seed(self._seed_base, self._calls)
