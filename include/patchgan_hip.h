@@ -224,7 +224,24 @@ typedef struct pg_conv_extras {
     const void* mul_t;
     int mul_ld;
     int mul_act;
+    /* big2small with v_keep, as ONE PART of a larger batch: the kept transform is V[point][tile][k] with the tiles of the whole batch
+     * running inside every point's plane, so a call over samples [n0, n0 + N) of a batch of Nt writes (and its GEMM reads) rows
+     * [v_tile0, v_tile0 + tiles(N)) of every plane of the buffer sized for Nt (pg_conv_v_bytes of the Nt geometry):
+     *   v_stride  floats between two planes = tiles(Nt) * k (k = 4 * Cb on the polyphase path, Cb on the stride-1 path); 0 = the
+     *             dense layout of this call's own N (and then v_tile0 must be 0)
+     *   v_tile0   first tile row = n0 * tiles(1)
+     * Rows outside the range are not touched.  Per-tile arithmetic does not depend on either field.  Honoured by the polyphase
+     * path and by the row-fused F(3x3,4x4) path (the only ones that keep V); PG_EINVAL where the range leaves the plane, the strided
+     * buffer is beyond the kernels' 32-bit offsets, or v_keep is NULL.  Whether the parts of a batch compute what the whole-batch call
+     * computes, bit for bit, is answered by pg_conv_batch_halves_same(). */
+    long long v_stride;
+    long long v_tile0;
 } pg_conv_extras;
+/* 1 if pg_conv4x4_big2small on geometry g (N samples) and on the same geometry with 2 * N samples do the same arithmetic per sample:
+ * the same path and kernel symbol, no split over K in either, and a kept V (pg_conv_v_bytes) in both or in neither -- decided by the
+ * planner the entry points launch from, for 16-byte-aligned contiguous tensors.  ws_bytes_n / ws_bytes_2n: the workspace sizes the two
+ * calls would be made with.  Then two half calls (v_stride / v_tile0 above) fill what the whole call fills.  0 otherwise. */
+int pg_conv_batch_halves_same(const pg_conv_geom* g, int algo, size_t ws_bytes_n, size_t ws_bytes_2n);
 int pg_conv_mul_ok(const pg_conv_geom* g, int algo, size_t ws_bytes);   /* small2big: the kernel of this call can apply mul_t */
 int pg_conv_stats_chunks(const pg_conv_geom* g, int op, int algo, size_t ws_bytes);   /* op 0 big2small, 1 small2big */
 size_t pg_conv_u_bytes(const pg_conv_geom* g, int op, int algo, size_t ws_bytes);      /* op 0 big2small, 1 small2big */

@@ -50,7 +50,8 @@ _G = ctypes.POINTER(ConvGeom)
 class ConvExtras(ctypes.Structure):
     """struct pg_conv_extras: optional hand-overs between calls on the same layer"""
     _fields_ = [('part', ctypes.c_void_p), ('v_keep', ctypes.c_void_p), ('v_pre', ctypes.c_void_p), ('u_cache', ctypes.c_void_p),
-                ('u_valid', ctypes.c_int), ('mul_t', ctypes.c_void_p), ('mul_ld', ctypes.c_int), ('mul_act', ctypes.c_int)]
+                ('u_valid', ctypes.c_int), ('mul_t', ctypes.c_void_p), ('mul_ld', ctypes.c_int), ('mul_act', ctypes.c_int),
+                ('v_stride', ctypes.c_longlong), ('v_tile0', ctypes.c_longlong)]
 
 
 _X = ctypes.POINTER(ConvExtras)
@@ -90,6 +91,7 @@ SIGNATURES = {
     'pg_conv_stats_chunks': (_i, [_G, _i, _i, _sz]),
     'pg_conv_u_bytes': (_sz, [_G, _i, _i, _sz]),
     'pg_conv_v_bytes': (_sz, [_G, _i, _sz]),
+    'pg_conv_batch_halves_same': (_i, [_G, _i, _sz, _sz]),
     'pg_conv4x4_big2small_x': (_i, [_p, _i, _p, _p, _p, _i, _G, _i, _i, _p, _sz, _p, _X]),
     'pg_conv4x4_small2big_x': (_i, [_p, _i, _p, _p, _p, _i, _G, _i, _i, _p, _sz, _p, _X]),
     'pg_conv4x4_wgrad_x': (_i, [_p, _i, _p, _i, _p, _p, _G, _i, _p, _sz, _p, _X]),

@@ -17,6 +17,7 @@
 #include <stdio.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <string.h>
 #include <type_traits>
 #include <vector>
 #include "patchgan_hip.h"
@@ -3536,7 +3537,7 @@ struct Views {
     void* ws;
     const pg_conv_extras* x;   // never null
 };
-static const pg_conv_extras NO_EXTRAS = {nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, 0};
+static const pg_conv_extras NO_EXTRAS = {nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, 0, 0, 0};
 // hand-overs a query asks about (a launch reads them from Views::x)
 enum { OFFER_PART = 1, OFFER_U = 2, OFFER_V = 4, OFFER_MUL = 8 };
 
@@ -4108,6 +4109,29 @@ size_t pg_conv_v_bytes(const pg_conv_geom* g, int algo, size_t ws_bytes) {
     return 0;
 }
 
+// the parts of a batch compute what the whole-batch call computes: same path and kernel, no split over K, V kept in both or in neither
+int pg_conv_batch_halves_same(const pg_conv_geom* g, int algo, size_t ws_bytes_n, size_t ws_bytes_2n) {
+    if (!geom_ok(g) || g->N > (1 << 29)) return 0;
+    pg_conv_geom g2 = *g;
+    g2.N *= 2;
+    ConvPlan a, b;
+    if (!geom_ok(&g2) || !query_plan(g, 0, algo, ws_bytes_n, 0, &a) || !query_plan(&g2, 0, algo, ws_bytes_2n, 0, &b)) return 0;
+    if (a.rc != PG_OK || b.rc != PG_OK || a.path != b.path || a.split != 1 || b.split != 1) return 0;
+    const Tune tune = tune_of(algo);
+    if (a.path == Path::Wino1) {
+        // the fully fused F(3x3,4x4) GEMM splits its K range by the grid it gets from the batch; the row-fused form never does
+        const bool rows = a.mo == 3 && b.mo == 3 && pg_wino_row_on() && !tune.dma;
+        if (!rows && (pg_wino_gemm_slices(g->N, g->Hs, g->Ws, g->Cb, g->Ca, tune.mo1) != 1 ||
+                      pg_wino_gemm_slices(g2.N, g->Hs, g->Ws, g->Cb, g->Ca, tune.mo1) != 1))
+            return 0;
+    }
+    char na[128], nb[128];
+    name_of(a, to_geom(g), 0, algo, tune, na, sizeof na);
+    name_of(b, to_geom(&g2), 0, algo, tune, nb, sizeof nb);
+    if (strcmp(na, nb) != 0) return 0;
+    return (pg_conv_v_bytes(g, algo, ws_bytes_n) != 0) == (pg_conv_v_bytes(&g2, algo, ws_bytes_2n) != 0) ? 1 : 0;
+}
+
 int pg_conv_prep_batch(int n, const pg_conv_prep_item* items, void* stream) {
     if (n < 0 || (n > 0 && !items)) return PG_EINVAL;
     hipStream_t st = (hipStream_t)stream;
@@ -4197,14 +4221,17 @@ int launch_wino1(const Call& c, int op) {
     const int Hi = op == 0 ? g.Hb : g.Hs, Wi = op == 0 ? g.Wb : g.Ws, Ci = op == 0 ? g.Cb : g.Ca;
     const int Ho = op == 0 ? g.Hs : g.Hb, Wo = op == 0 ? g.Ws : g.Wb, Co = op == 0 ? g.Ca : g.Cb;
     const pg_epi_mul mul = op == 0 ? pg_epi_mul{nullptr, 0, 0} : mul_of(c);
-    int rc = op == 0 ? pg_wino_prepare(in, ld_in, c.v.P, 0, g.N, Hi, Wi, Ci, Ho, Wo, Co, 1, c.v.ws, c.st, mo1, x.u_cache, x.u_valid, x.v_keep)
+    // (a kept V that is part of a larger batch's: only the row-fused form reads it -- refused before anything is launched)
+    if ((x.v_stride || x.v_tile0) && (op != 0 || !pg_wino_gemm_rows(g.N, Ho, Wo, Ci, Co, mo1, c.tune.dma, out, ld_out, c.v.bias, mul))) return PG_EINVAL;
+    int rc = op == 0 ? pg_wino_prepare(in, ld_in, c.v.P, 0, g.N, Hi, Wi, Ci, Ho, Wo, Co, 1, c.v.ws, c.st, mo1, x.u_cache, x.u_valid, x.v_keep,
+                                       (long)x.v_stride, (long)x.v_tile0)
                      : pg_wino_prepare(in, ld_in, c.v.P, 1, g.N, Hi, Wi, Ci, Ho, Wo, Co, 2, c.v.ws, c.st, mo1, x.u_cache, x.u_valid);
     if (rc != PG_OK) return rc;
     const int nsl = pg_wino_gemm_rows(g.N, Ho, Wo, Ci, Co, mo1, c.tune.dma, out, ld_out, c.v.bias, mul) ? 1 : pg_wino_gemm_slices(g.N, Ho, Wo, Ci, Co, mo1);
     {
         TimedLaunch timed(c.st);
         rc = pg_wino_gemm(c.v.bias, out, ld_out, g.N, Ci, Ho, Wo, Co, c.v.act, c.v.ws, c.st, mo1, c.tune.dma, x.u_cache, mul, op == 0 ? x.v_keep : nullptr,
-                          c.tune.s3r);
+                          c.tune.s3r, (long)x.v_stride, (long)x.v_tile0);
     }
     if (rc != PG_OK || nsl == 1) return rc;
     const long pix = (long)g.N * Ho * Wo;
@@ -4220,7 +4247,8 @@ int launch_wino2(const Call& c, int op) {
     t_ev1 = nullptr;
     if (op == 0)
         return pg_wino2_b2s((const float*)c.v.big, c.v.ld_big, c.v.P, c.v.bias, (float*)const_cast<void*>(c.v.small), c.v.ld_small, g.N, g.Hb, g.Wb, g.Hs,
-                            g.Ws, g.Ca, g.Cb, c.v.act, c.v.ws, c.st, e0, e1, nullptr, x.part, x.v_keep, x.u_cache, x.u_valid, c.tune.s3);
+                            g.Ws, g.Ca, g.Cb, c.v.act, c.v.ws, c.st, e0, e1, nullptr, x.part, x.v_keep, x.u_cache, x.u_valid, c.tune.s3, (long)x.v_stride,
+                            (long)x.v_tile0);
     return pg_wino2_s2b((const float*)c.v.small, c.v.ld_small, c.v.P, c.v.bias, (float*)const_cast<void*>(c.v.big), c.v.ld_big, g.N, g.Hb, g.Wb, g.Hs, g.Ws,
                         g.Ca, g.Cb, c.v.act, c.v.ws, c.st, e0, e1, x.part, x.u_cache, x.u_valid, mul_of(c), c.tune.s3);
 }
@@ -4611,6 +4639,18 @@ int pg_conv4x4_big2small_x(const float* big, int ld_big, const float* P, const f
     // bf16 activation storage: PG_IO_BIG_BF16 = input, PG_IO_SMALL_BF16 = output
     if ((algo & PG_IO_MASK) && (algo & PG_ALGO_MASK) != PG_ALGO_BF16) return PG_EINVAL;
     if (!hand_overs_sized(gg, 0, algo, ws, ws_bytes, x)) return PG_EINVAL;
+    if (x.v_stride || x.v_tile0) {
+        // the kept V as rows [v_tile0, v_tile0 + tiles) of a larger batch's planes: the range stays inside a plane, the strided buffer
+        // inside the kernels' 32-bit offsets
+        ConvPlan f;
+        if (!x.v_keep || x.v_stride < 0 || x.v_tile0 < 0 || !query_plan(gg, 0, algo, ws ? ws_bytes : 0, OFFER_V, &f)) return PG_EINVAL;
+        if (f.path != Path::Wino1 && f.path != Path::Wino2) return PG_EINVAL;
+        const bool w1 = f.path == Path::Wino1;
+        const long X = w1 ? 36 : 16, K = w1 ? gg->Cb : 4L * gg->Cb;
+        const long T = w1 ? (long)gg->N * ((gg->Hs + 2) / 3) * ((gg->Ws + 2) / 3) : pg_wino2_tiles_b2s(gg->N, gg->Hs, gg->Ws);
+        const long zs = x.v_stride ? (long)x.v_stride : T * K;
+        if ((zs & 3) || (x.v_tile0 + T) * K > zs || (double)X * zs * 4 >= 1.5e9) return PG_EINVAL;
+    }
     return run_conv(0, Views{small, big, ld_small, ld_big, P, bias, act, ws, &x}, gg, algo, ws_bytes, stream);
 }
 
@@ -4623,7 +4663,7 @@ int pg_conv4x4_big2small(const float* big, int ld_big, const float* P, const flo
 int pg_conv4x4_small2big_x(const float* small, int ld_small, const float* P, const float* bias, float* big, int ld_big,
                            const pg_conv_geom* gg, int act, int algo, void* ws, size_t ws_bytes, void* stream, const pg_conv_extras* xp) {
     const pg_conv_extras& x = xp ? *xp : NO_EXTRAS;
-    if ((x.u_cache && !aligned16(x.u_cache)) || x.v_keep || x.v_pre) return PG_EINVAL;
+    if ((x.u_cache && !aligned16(x.u_cache)) || x.v_keep || x.v_pre || x.v_stride || x.v_tile0) return PG_EINVAL;
     if (x.mul_t && (x.mul_ld < gg->Cb || x.mul_act < PG_ACT_NONE || x.mul_act > PG_ACT_SIGMOID || x.part)) return PG_EINVAL;
     if (!geom_ok(gg) || !big || !P || !small || ld_big < gg->Cb || ld_small < gg->Ca) return PG_EINVAL;
     if (act < PG_ACT_NONE || act > PG_ACT_SIGMOID) return PG_EINVAL;
@@ -4686,7 +4726,7 @@ int pg_conv4x4_wgrad(const float* small, int ld_small, const float* big, int ld_
 
 int pg_conv4x4_wgrad_x(const float* small, int ld_small, const float* big, int ld_big, float* dP, float* dbias,
                        const pg_conv_geom* gg, int algo, void* ws, size_t ws_bytes, void* stream, const pg_conv_extras* x) {
-    if (x && (x->part || x->v_keep || x->u_cache)) return PG_EINVAL;
+    if (x && (x->part || x->v_keep || x->u_cache || x->v_stride || x->v_tile0)) return PG_EINVAL;
     return wgrad_impl(small, ld_small, big, ld_big, dP, dbias, gg, algo, ws, ws_bytes, stream, x ? x->v_pre : nullptr);
 }
 
@@ -4699,7 +4739,7 @@ int pg_conv4x4_bwd_big_x(const float* small, int ld_small, const float* big, int
                          float* dsmall, int ld_dsmall, const pg_conv_geom* gg, int algo, void* ws, size_t ws_bytes, void* stream,
                          const pg_conv_extras* x) {
     if (!geom_ok(gg) || !small || !big || !P || !dP || !dsmall) return PG_EINVAL;
-    if (x && (x->part || x->v_keep || x->v_pre || x->mul_t)) return PG_EINVAL;      // only the data gradient's u_cache / u_valid
+    if (x && (x->part || x->v_keep || x->v_pre || x->mul_t || x->v_stride || x->v_tile0)) return PG_EINVAL;      // only the data gradient's u_cache / u_valid
     float* const Uext = x ? x->u_cache : nullptr;
     const int u_valid = x ? x->u_valid : 0;
     if (Uext && !aligned16(Uext)) return PG_EINVAL;

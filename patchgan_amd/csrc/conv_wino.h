@@ -17,7 +17,8 @@ bool pg_wino_small_tile(int N, int Hout, int Wout, int Cin, int Cout, int mo_for
 size_t pg_wino_ws_bytes(int N, int Hout, int Wout, int Cin, int Cout, int mo_forced);
 // weight transform + input transform into ws
 int pg_wino_prepare(const float* in, int ld_in, const float* P, int flip, int N, int Hin, int Win, int Cin, int Hout,
-                    int Wout, int Cout, int pad, void* ws, hipStream_t st, int mo_forced, float* Uext, int u_valid, float* Vext = nullptr);
+                    int Wout, int Cout, int pad, void* ws, hipStream_t st, int mo_forced, float* Uext, int u_valid, float* Vext = nullptr,
+                    long v_stride = 0, long v_tile0 = 0);
 // Uext (optional, all paths with a weight transform): caller-owned cache of the transformed weights; u_valid != 0: it already
 // holds the transform of the current weights and the transform kernel is skipped
 size_t pg_wino_u_bytes(int N, int Hout, int Wout, int Cin, int Cout, int mo_forced);
@@ -44,10 +45,12 @@ int pg_wino_dma_mode();   // process default (PATCHGAN_WINO_DMA): 0 register-sta
 // the batched GEMM with fused output transform, bias and activation
 int pg_wino_gemm(const float* bias, float* out, int ld_out, int N, int Cin, int Hout, int Wout, int Cout, int act,
                  void* ws, hipStream_t st, int mo_forced, int dma_mode, const float* Uext, pg_epi_mul mul = pg_epi_mul{nullptr, 0, 0},
-                 const float* Vext = nullptr, int s3 = 0);
+                 const float* Vext = nullptr, int s3 = 0, long v_stride = 0, long v_tile0 = 0);
 // s3: the row-fused F(3x3,4x4) GEMM in split-bf16 form (k_wino_gemm_row_s3 instead of k_wino_gemm_row; Cin % 32 == 0)
 // Vext (both): the transformed input lives in a caller-owned buffer (pg_wino_wgrad_v_bytes) instead of the workspace -- the forward
 // call keeps it for the layer's weight gradient (Vpre of pg_wino_wgrad), F(3x3,4x4) forward + F(4x4,3x3) weight gradient only
+// v_stride / v_tile0 (both, and pg_wino2_b2s): Vext / Vkeep is the V of a LARGER batch -- its planes are v_stride floats apart (0: this
+// call's own T * Cin resp. T * 4 * Cb) and this call owns rows [v_tile0, v_tile0 + T) of each (pg_conv_extras.v_stride / v_tile0)
 
 // weight gradient of the same layers, F(4x4, 2x2) or F(4x4, 3x3) (X = 25 / 36 points): V (X*tiles*Cb) | DY (X*tiles*Ca) | S (slices*X*Ca*Cb) in ws
 bool pg_wino_wgrad_geom_ok(int N, int Hs, int Ws, int Ca, int Cb);
@@ -74,7 +77,7 @@ size_t pg_wino2_ws_bytes(int N, int Hs, int Ws, int Ca, int Cb);
 // Vpre (optional, F(3x3,2x2) only): the transformed input already computed by pg_wino2_v; ws then holds U | M only
 int pg_wino2_b2s(const float* big, int ld_big, const float* P, const float* bias, float* small, int ld_small, int N, int Hb,
                  int Wb, int Hs, int Ws, int Ca, int Cb, int act, void* ws, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1,
-                 const float* Vpre, double* part, float* Vkeep, float* Uext, int u_valid, int s3);
+                 const float* Vpre, double* part, float* Vkeep, float* Uext, int u_valid, int s3, long v_stride = 0, long v_tile0 = 0);
 // s3 (both directions): != 0 runs the batched GEMM in split-bf16 form (k_wino_bgemm_s3: fp32 operands split into three bf16 pieces while they
 // are staged, six bf16 MFMAs per 16 k, fp32 accumulate), 0 on v_mfma_f32_32x32x2_f32 (k_wino_bgemm)
 // part (optional, both directions): the output transform also writes per-sample partial sums / sums of squares of the output,

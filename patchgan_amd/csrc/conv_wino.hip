@@ -117,7 +117,8 @@ __global__ __launch_bounds__(256) void k_wino_u(const float* __restrict__ P, flo
 // (tile, 4 channels).
 template <int MO>
 __global__ __launch_bounds__(256) void k_wino_v(const float* __restrict__ in, int ld_in, float* __restrict__ V, int N,
-                                                int Hin, int Win, int Ci, int TH, int TW, int pad) {
+                                                int Hin, int Win, int Ci, int TH, int TW, int pad, long zstride, long tile0) {
+    // zstride: floats between two points' planes of V (T * Ci when V holds this call's tiles only), tile0: this call's first row in a plane
     constexpr int NP = MO + 3;
     const int cq = Ci >> 2;
     const long T = (long)N * TH * TW;
@@ -156,7 +157,7 @@ __global__ __launch_bounds__(256) void k_wino_v(const float* __restrict__ in, in
             f32x4 s = z;
 #pragma unroll
             for (int j = 0; j < NP; ++j) s += t[a][j] * s1_bt<MO>(b, j);
-            *reinterpret_cast<f32x4*>(V + ((long)(a * NP + b) * T + tile) * Ci + c0) = s;
+            *reinterpret_cast<f32x4*>(V + (long)(a * NP + b) * zstride + (tile0 + tile) * Ci + c0) = s;
         }
 }
 
@@ -338,7 +339,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 template <int WPE, int MR = 1>      // MR: 32-row MFMA tiles per wave (64 * MR tiles per workgroup)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void k_wino_gemm_row(
     const float* __restrict__ V, const float* __restrict__ U, float* __restrict__ Tout, int T, int Ci, int Co, int v_bytes, int u_bytes,
-    int tiles_n) {
+    int tiles_n, int v_xi) {      // v_xi: elements between two points' planes of V (T * Ci when dense)
     constexpr int NP = 6, KCL = 64, LDL = KCL + 4, QR = KCL / 4, RP = 256 / QR, BM = 64 * MR, BN = 64, AI = BM / RP, BI = BN / RP;
     __shared__ __attribute__((aligned(16))) float smem[(BM + BN) * LDL];
     float* As = smem;
@@ -372,7 +373,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
         const int co = n0 + r0 + RP * i;
         b_off[i] = (co < Co) ? co * Ci + kq * 4 : 0x10000000;
     }
-    const int v_xi = T * Ci, u_xi = Co * Ci;
+    const int u_xi = Co * Ci;
     f32x4 ra[AI], rb[BI];
     int ld_j = 0, ld_ch = 0;
     auto issue_loads = [&](bool on) {
@@ -953,7 +954,8 @@ __device__ __forceinline__ void wino2_v_tile(const float* __restrict__ src, int 
 
 template <int MO>
 __global__ __launch_bounds__(256) void k_wino2_v(const float* __restrict__ big, int ld, float* __restrict__ V, int N, int Hb,
-                                                 int Wb, int Cb, int TH, int TW) {
+                                                 int Wb, int Cb, int TH, int TW, long zstride, long tile0) {
+    // zstride: floats between two points' planes of V (T * 4 * Cb when V holds this call's tiles only), tile0: this call's first row in a plane
     const int cq = Cb >> 2;
     const long T = (long)N * TH * TW;
     const long idx = blockIdx.x * (long)blockDim.x + threadIdx.x;
@@ -967,8 +969,8 @@ __global__ __launch_bounds__(256) void k_wino2_v(const float* __restrict__ big, 
     const int ti = rem / TW, tj = rem - ti * TW;
     const long K = 4L * Cb;
     // X_ph[MO*ti + i][MO*tj + j] = big[2*(MO*ti + i) + r - 1][2*(MO*tj + j) + s - 1]
-    wino2_v_tile<MO>(big, ld, n, Hb, Wb, 2 * MO * ti + (ph >> 1) - 1, 2 * MO * tj + (ph & 1) - 1, 2, c0, V, T * K,
-                     tile * K + ph * Cb + c0);
+    wino2_v_tile<MO>(big, ld, n, Hb, Wb, 2 * MO * ti + (ph >> 1) - 1, 2 * MO * tj + (ph & 1) - 1, 2, c0, V, zstride,
+                     (tile0 + tile) * K + ph * Cb + c0);
 }
 
 #ifdef PG_TRACE_R
@@ -979,7 +981,7 @@ __device__ unsigned long long* pg_trace_buf_w = nullptr;
 template <int MR, int NR, int WM, int WN>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_wino_bgemm(const float* __restrict__ A, const float* __restrict__ B,
                                                     float* __restrict__ C, int Mrows, int Ncols, int K, int a_bytes,
-                                                    int b_bytes, int tiles_m, int tiles_n) {
+                                                    int b_bytes, int tiles_m, int tiles_n, int a_zs) {
     constexpr int BM = WM * MR * 32, BN = WN * NR * 32, AI = BM / 32, BI = BN / 32;
     __shared__ __attribute__((aligned(16))) float smem[(BM + BN) * LDK];
     float* As = smem;
@@ -1003,7 +1005,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     for (int i = 0; i < AI; ++i) {
         const int m = m0 + r0 + 32 * i;
         a_ok[i] = m < Mrows;
-        a_off[i] = (z * Mrows + min(m, Mrows - 1)) * K + kq * 4;
+        a_off[i] = z * a_zs + min(m, Mrows - 1) * K + kq * 4;      // a_zs: elements between two batches of A (Mrows * K when dense)
     }
 #pragma unroll
     for (int i = 0; i < BI; ++i) {
@@ -1149,7 +1151,7 @@ constexpr int S3_KC = 16, S3_LDR = 3 * S3_KC + 8;
 template <int MR, int NR, int WM, int WN, int WPE, int VAR = 1, bool PIPE = false>      // VAR: order of the six products (1 = largest first, the shipped one; others: PATCHGAN_S3_VAR, experiment)
 __global__ __launch_bounds__(WM * WN * 64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void k_wino_bgemm_s3(const float* __restrict__ A, const float* __restrict__ B,
                                                     float* __restrict__ C, int Mrows, int Ncols, int K, int a_bytes,
-                                                    int b_bytes, int tiles_m, int tiles_n) {
+                                                    int b_bytes, int tiles_m, int tiles_n, int a_zs) {
     // (WM x WN waves; four staging lanes per 16-wide row piece, RP rows per pass.  <2,2,4,2>: a 256 x 128 tile on EIGHT waves -- the B rows
     //  staged once for twice the MFMAs, 86 KB of LDS, one workgroup per CU)
     constexpr int BM = WM * MR * 32, BN = WN * NR * 32, RP = WM * WN * 16, AI = BM / RP, BI = BN / RP, BUF = (BM + BN) * S3_LDR;
@@ -1172,7 +1174,7 @@ __global__ __launch_bounds__(WM * WN * 64) __attribute__((amdgpu_waves_per_eu(WP
     for (int i = 0; i < AI; ++i) {
         const int m = m0 + r0 + RP * i;
         a_ok[i] = m < Mrows;
-        a_off[i] = (z * Mrows + min(m, Mrows - 1)) * K + kq * 4;
+        a_off[i] = z * a_zs + min(m, Mrows - 1) * K + kq * 4;      // a_zs: elements between two batches of A (Mrows * K when dense)
     }
 #pragma unroll
     for (int i = 0; i < BI; ++i) {
@@ -1468,7 +1470,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 template <int WPE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void k_wino_gemm_row_s3(
     const float* __restrict__ V, const float* __restrict__ U, float* __restrict__ Tout, int T, int Ci, int Co, int v_bytes, int u_bytes,
-    int tiles_n) {
+    int tiles_n, int v_xi) {      // v_xi: elements between two points' planes of V (T * Ci when dense)
     constexpr int NP = 6, BM = 128, BN = 64, MR = 2, BUF = (BM + BN) * S3_LDR;
     __shared__ __attribute__((aligned(16))) __bf16 smem[2 * BUF];
     const __amdgpu_buffer_rsrc_t rV = __builtin_amdgcn_make_buffer_rsrc((void*)V, 0, v_bytes, 0x00020000);
@@ -1496,7 +1498,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
         const int co = n0 + r0;
         b_off = (co < Co) ? co * Ci + kq * 4 : 0x10000000;
     }
-    const int v_xi = T * Ci, u_xi = Co * Ci;
+    const int u_xi = Co * Ci;
     int ld_j = 0, ld_ch = 0;
     auto issue_loads = [&](f32x4 (&ra)[2], f32x4& rb) {         // the next (j, chunk) in order; beyond the last one: masked
         const bool on = ld_j < NP;
@@ -1609,7 +1611,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 template <int MR, int NR, int WM, int WN, int WPE = 2>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void k_wino_bgemm_mz(const float* __restrict__ A, const float* __restrict__ B,
                                                        float* __restrict__ C, int Mrows, int Ncols, int K, int zb, int a_bytes,
-                                                       int b_bytes, int tiles_m, int tiles_n) {
+                                                       int b_bytes, int tiles_m, int tiles_n, int a_zs) {
     constexpr int BM = WM * MR * 32, BN = WN * NR * 32, AI = BM / 32, BI = BN / 32;
     __shared__ __attribute__((aligned(16))) float smem[(BM + BN) * LDK];
     float* As = smem;
@@ -1631,7 +1633,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
     for (int i = 0; i < AI; ++i) {
         const int m = m0 + r0 + 32 * i;
         a_ok[i] = m < Mrows;
-        a_off[i] = (z0 * Mrows + min(m, Mrows - 1)) * K + kq * 4;
+        a_off[i] = z0 * a_zs + min(m, Mrows - 1) * K + kq * 4;
     }
 #pragma unroll
     for (int i = 0; i < BI; ++i) {
@@ -1639,7 +1641,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
         b_ok[i] = n < Ncols;
         b_off[i] = (z0 * Ncols + min(n, Ncols - 1)) * K + kq * 4;
     }
-    const int a_zs = Mrows * K, b_zs = Ncols * K;       // elements per batch
+    const int b_zs = Ncols * K;       // elements per batch of B (A: a_zs, Mrows * K when dense)
     f32x4 ra[AI], rb[BI];
     int ld_z = 0, ld_c = 0;                             // (batch, chunk) of the NEXT load
     auto issue_loads = [&](bool on) {
@@ -2159,9 +2161,12 @@ float* pg_wino_gemm_slabs(void* ws, int N, int Hout, int Wout, int Cin, int Cout
 }
 
 int pg_wino_prepare(const float* in, int ld_in, const float* P, int flip, int N, int Hin, int Win, int Cin, int Hout,
-                    int Wout, int Cout, int pad, void* ws, hipStream_t st, int forced, float* Uext, int u_valid, float* Vext) {
+                    int Wout, int Cout, int pad, void* ws, hipStream_t st, int forced, float* Uext, int u_valid, float* Vext, long v_stride,
+                    long v_tile0) {
     const int mo = pg_wino_mo(N, Hout, Wout, Cin, Cout, forced), TH = (Hout + mo - 1) / mo, TW = (Wout + mo - 1) / mo;
     const long T = (long)N * TH * TW, X = wino1_nxi(N, Hout, Wout, Cin, Cout, forced);
+    if ((v_stride || v_tile0) && !Vext) return PG_EINVAL;
+    const long zs = v_stride ? v_stride : T * Cin;      // Vext as rows [v_tile0, v_tile0 + T) of a larger batch's planes
     float* U = Uext ? Uext : (float*)ws;       // Uext: caller-owned cache of the transformed weights (u_valid: already filled)
     float* V = Vext ? Vext : (float*)((char*)ws + align256((size_t)X * Cout * Cin * 4));      // Vext: caller-owned (kept for the weight gradient)
     const dim3 gu((unsigned)(((long)Cout * Cin + 255) / 256)), gv((unsigned)((T * (Cin / 4) + 255) / 256));
@@ -2173,9 +2178,9 @@ int pg_wino_prepare(const float* in, int ld_in, const float* P, int flip, int N,
         if (hipGetLastError() != hipSuccess) return PG_ELAUNCH;
     }
     if (mo == 3)
-        hipLaunchKernelGGL(k_wino_v<3>, gv, dim3(256), 0, st, in, ld_in, V, N, Hin, Win, Cin, TH, TW, pad);
+        hipLaunchKernelGGL(k_wino_v<3>, gv, dim3(256), 0, st, in, ld_in, V, N, Hin, Win, Cin, TH, TW, pad, zs, v_tile0);
     else
-        hipLaunchKernelGGL(k_wino_v<2>, gv, dim3(256), 0, st, in, ld_in, V, N, Hin, Win, Cin, TH, TW, pad);
+        hipLaunchKernelGGL(k_wino_v<2>, gv, dim3(256), 0, st, in, ld_in, V, N, Hin, Win, Cin, TH, TW, pad, zs, v_tile0);
     return hipGetLastError() == hipSuccess ? PG_OK : PG_ELAUNCH;
 }
 
@@ -2192,23 +2197,28 @@ int pg_wino_dma_mode() {
 }
 
 int pg_wino_gemm(const float* bias, float* out, int ld_out, int N, int Cin, int Hout, int Wout, int Cout, int act,
-                 void* ws, hipStream_t st, int forced, int dma_mode, const float* Uext, pg_epi_mul mul, const float* Vext, int s3) {
+                 void* ws, hipStream_t st, int forced, int dma_mode, const float* Uext, pg_epi_mul mul, const float* Vext, int s3,
+                 long v_stride, long v_tile0) {
     const int mo = pg_wino_mo(N, Hout, Wout, Cin, Cout, forced), TH = (Hout + mo - 1) / mo, TW = (Wout + mo - 1) / mo;
     const long T = (long)N * TH * TW, X = wino1_nxi(N, Hout, Wout, Cin, Cout, forced);
     const float* U = Uext ? Uext : (const float*)ws;
-    const float* V = Vext ? Vext : (const float*)((const char*)ws + align256((size_t)X * Cout * Cin * 4));
+    const bool rows = pg_wino_gemm_rows(N, Hout, Wout, Cin, Cout, forced, dma_mode, out, ld_out, bias, mul);
+    // Vext as rows [v_tile0, v_tile0 + T) of a larger batch's planes: the row-fused form only (the one that runs where V is kept)
+    if ((v_stride || v_tile0) && (!Vext || !rows)) return PG_EINVAL;
+    const long zs = v_stride ? v_stride : T * Cin;
+    const float* V = Vext ? Vext + v_tile0 * Cin : (const float*)((const char*)ws + align256((size_t)X * Cout * Cin * 4));
     const bool small_tile = pg_wino_small_tile(N, Hout, Wout, Cin, Cout, forced);
-    const int v_bytes = (int)(X * T * Cin * 4), u_bytes = (int)(X * Cout * Cin * 4);
+    const int v_bytes = (int)(((X - 1) * zs + T * Cin) * 4), u_bytes = (int)(X * Cout * Cin * 4);
     const int tn = (Cout + 63) / 64;
-    if (pg_wino_gemm_rows(N, Hout, Wout, Cin, Cout, forced, dma_mode, out, ld_out, bias, mul)) {
+    if (rows) {
         float* Tt = pg_wino_gemm_slabs(ws, N, Hout, Wout, Cin, Cout, forced);
         // (MR = 2 -- 128 tiles per workgroup, 64 x 32 per wave, 2 waves per SIMD -- measured 0.14 ms per step slower)
         if (s3 && Cin % 32 == 0)
             hipLaunchKernelGGL((k_wino_gemm_row_s3<2>), dim3((unsigned)(((T + 127) / 128) * tn * 6)), dim3(256), 0, st, V, U, Tt, (int)T, Cin,
-                               Cout, v_bytes, u_bytes, tn);
+                               Cout, v_bytes, u_bytes, tn, (int)zs);
         else
             hipLaunchKernelGGL((k_wino_gemm_row<4, 1>), dim3((unsigned)(((T + 63) / 64) * tn * 6)), dim3(256), 0, st, V, U, Tt, (int)T, Cin, Cout,
-                               v_bytes, u_bytes, tn);
+                               v_bytes, u_bytes, tn, (int)zs);
         if (hipGetLastError() != hipSuccess) return PG_ELAUNCH;
         const dim3 go((unsigned)((T * (Cout / 4) + 255) / 256));
         if (mul.t)
@@ -2359,11 +2369,11 @@ int pg_wino_wgrad(const float* small, int ld_small, const float* big, int ld_big
     float* S = (float*)((char*)DY + align256((size_t)X * T * Ca * 4));
     const dim3 gv((unsigned)((T * (Cb / 4) + 255) / 256)), gd((unsigned)((T * (Ca / 4) + 255) / 256));
     if (R == 3) {
-        if (!Vpre) hipLaunchKernelGGL(k_wino_v<3>, gv, dim3(256), 0, st, big, ld_big, (float*)ws, N, Hb, Wb, Cb, TH, TW, 1);
+        if (!Vpre) hipLaunchKernelGGL(k_wino_v<3>, gv, dim3(256), 0, st, big, ld_big, (float*)ws, N, Hb, Wb, Cb, TH, TW, 1, T * Cb, 0L);
         if (hipGetLastError() != hipSuccess) return PG_ELAUNCH;
         hipLaunchKernelGGL(k_wino_dy<3>, gd, dim3(256), 0, st, small, ld_small, DY, N, Hs, Ws, Ca, TH, TW);
     } else {
-        hipLaunchKernelGGL(k_wino_v<2>, gv, dim3(256), 0, st, big, ld_big, (float*)ws, N, Hb, Wb, Cb, TH, TW, 1);
+        hipLaunchKernelGGL(k_wino_v<2>, gv, dim3(256), 0, st, big, ld_big, (float*)ws, N, Hb, Wb, Cb, TH, TW, 1, T * Cb, 0L);
         if (hipGetLastError() != hipSuccess) return PG_ELAUNCH;
         hipLaunchKernelGGL(k_wino_dy<2>, gd, dim3(256), 0, st, small, ld_small, DY, N, Hs, Ws, Ca, TH, TW);
     }
@@ -2405,7 +2415,7 @@ int pg_wino_wgrad(const float* small, int ld_small, const float* big, int ld_big
 // kernel (126 registers, four waves per SIMD, four workgroups per CU covering each other's prologues) 8.90.
 // the split-bf16 batched GEMM: 128-row tiles at two waves per SIMD (194 registers), 64-row tiles at three (118)
 static void bgemm_s3_launch(int big_rows, dim3 grid, hipStream_t st, const float* A, const float* B, float* C, int Mrows, int Ncols, int K,
-                            int a_bytes, int b_bytes, int tm, int tn) {
+                            int a_bytes, int b_bytes, int tm, int tn, int a_zs) {
     static const int var = [] {      // PATCHGAN_S3_VAR (experiment): order of the six products, see k_wino_bgemm_s3
         const char* e = pg_exp_env("PATCHGAN_S3_VAR");
         return e ? atoi(e) : 1;
@@ -2421,17 +2431,17 @@ static void bgemm_s3_launch(int big_rows, dim3 grid, hipStream_t st, const float
     if (var == 1 && big && big_rows && Mrows >= big) {
         const int X = (int)grid.x / (tm * tn), tm2 = (Mrows + 255) / 256;
         hipLaunchKernelGGL((k_wino_bgemm_s3<2, 2, 4, 2, 2, 1, false>), dim3(tm2 * tn * X), dim3(512), 0, st, A, B, C, Mrows, Ncols, K, a_bytes, b_bytes,
-                           tm2, tn);
+                           tm2, tn, a_zs);
         return;
     }
     if (var == 1 && pipe) {
         if (big_rows)
-            hipLaunchKernelGGL((k_wino_bgemm_s3<2, 2, 2, 2, 2, 1, true>), grid, dim3(256), 0, st, A, B, C, Mrows, Ncols, K, a_bytes, b_bytes, tm, tn);
+            hipLaunchKernelGGL((k_wino_bgemm_s3<2, 2, 2, 2, 2, 1, true>), grid, dim3(256), 0, st, A, B, C, Mrows, Ncols, K, a_bytes, b_bytes, tm, tn, a_zs);
         else
-            hipLaunchKernelGGL((k_wino_bgemm_s3<1, 2, 2, 2, 3, 1, true>), grid, dim3(256), 0, st, A, B, C, Mrows, Ncols, K, a_bytes, b_bytes, tm, tn);
+            hipLaunchKernelGGL((k_wino_bgemm_s3<1, 2, 2, 2, 3, 1, true>), grid, dim3(256), 0, st, A, B, C, Mrows, Ncols, K, a_bytes, b_bytes, tm, tn, a_zs);
         return;
     }
-#define S3_GO(MR, WPE, VAR) hipLaunchKernelGGL((k_wino_bgemm_s3<MR, 2, 2, 2, WPE, VAR>), grid, dim3(256), 0, st, A, B, C, Mrows, Ncols, K, a_bytes, b_bytes, tm, tn)
+#define S3_GO(MR, WPE, VAR) hipLaunchKernelGGL((k_wino_bgemm_s3<MR, 2, 2, 2, WPE, VAR>), grid, dim3(256), 0, st, A, B, C, Mrows, Ncols, K, a_bytes, b_bytes, tm, tn, a_zs)
     if (var == 0) { if (big_rows) S3_GO(2, 2, 0); else S3_GO(1, 3, 0); }
     else if (var == 2) { if (big_rows) S3_GO(2, 2, 2); else S3_GO(1, 3, 2); }
     else if (var == 3) { if (big_rows) S3_GO(2, 2, 3); else S3_GO(1, 3, 3); }
@@ -2484,10 +2494,15 @@ size_t pg_wino2_ws_bytes(int N, int Hs, int Ws, int Ca, int Cb) {
 template <int MO>
 static int wino2_b2s_run(const float* big, int ld_big, const float* P, const float* bias, float* small, int ld_small, int N,
                          int Hb, int Wb, int Hs, int Ws, int Ca, int Cb, int act, void* ws, hipStream_t st, hipEvent_t ev0,
-                         hipEvent_t ev1, const float* Vpre, double* part, float* Vkeep, float* Uext, int u_valid, int s3) {
+                         hipEvent_t ev1, const float* Vpre, double* part, float* Vkeep, float* Uext, int u_valid, int s3, long v_stride,
+                         long v_tile0) {
     constexpr int X = (MO + 1) * (MO + 1);
     const int TH = (Hs + MO - 1) / MO, TW = (Ws + MO - 1) / MO, K = 4 * Cb;
     const long T = (long)N * TH * TW;
+    // Vkeep as rows [v_tile0, v_tile0 + T) of every plane of a larger batch's V (planes v_stride floats apart): the transform writes
+    // them in place and the GEMM reads them through a pointer advanced to the first row and the same plane stride
+    if ((v_stride || v_tile0) && (!Vkeep || Vpre)) return PG_EINVAL;
+    const long zs = v_stride ? v_stride : T * K;
     // ws: U | V | M, or U | M when the caller supplies the transformed input (Vpre: shared with the weight gradient).
     // Vkeep: write V there (caller-owned, kept for the layer's weight gradient); Uext: caller-owned cache of U
     float* Uws = (float*)ws;
@@ -2495,33 +2510,33 @@ static int wino2_b2s_run(const float* big, int ld_big, const float* P, const flo
     float* Vws = (float*)((char*)Uws + align256((size_t)X * Ca * K * 4));
     float* M = Vpre ? Vws : (float*)((char*)Vws + align256((size_t)X * T * K * 4));
     float* Vown = Vkeep ? Vkeep : Vws;
-    const float* V = Vpre ? Vpre : Vown;
+    const float* V = Vpre ? Vpre : Vown + v_tile0 * K;
     if (!(Uext && u_valid)) {
         hipLaunchKernelGGL(k_wino2_u<MO>, dim3((unsigned)(((long)Ca * Cb + 255) / 256)), dim3(256), 0, st, P, U, Ca, Cb);
         if (hipGetLastError() != hipSuccess) return PG_ELAUNCH;
     }
     if (!Vpre) {
         hipLaunchKernelGGL(k_wino2_v<MO>, dim3((unsigned)((T * Cb + 255) / 256)), dim3(256), 0, st, big, ld_big, Vown, N, Hb, Wb, Cb,
-                           TH, TW);
+                           TH, TW, zs, v_tile0);
         if (hipGetLastError() != hipSuccess) return PG_ELAUNCH;
     }
     if (ev0) (void)hipEventRecord(ev0, st);
-    const int a_bytes = (int)((long)X * T * K * 4), b_bytes = (int)((long)X * Ca * K * 4);
+    const int a_bytes = (int)(((long)(X - 1) * zs + T * K) * 4), b_bytes = (int)((long)X * Ca * K * 4), a_zs = (int)zs;
     {
         const int big_rows = T >= 1024;
         const int tm = (int)(big_rows ? (T + 127) / 128 : (T + 63) / 64), tn = (Ca + 127) / 128;
         const int zb = s3 ? 1 : bgemm_zb((long)tm * tn, X);
         const dim3 grid((unsigned)(tm * tn * (X / zb)));
         if (s3)
-            bgemm_s3_launch(big_rows, grid, st, V, U, M, (int)T, Ca, K, a_bytes, b_bytes, tm, tn);
+            bgemm_s3_launch(big_rows, grid, st, V, U, M, (int)T, Ca, K, a_bytes, b_bytes, tm, tn, a_zs);
         else if (big_rows && zb > 1)
-            hipLaunchKernelGGL((k_wino_bgemm_mz<2, 2, 2, 2>), grid, dim3(256), 0, st, V, U, M, (int)T, Ca, K, zb, a_bytes, b_bytes, tm, tn);
+            hipLaunchKernelGGL((k_wino_bgemm_mz<2, 2, 2, 2>), grid, dim3(256), 0, st, V, U, M, (int)T, Ca, K, zb, a_bytes, b_bytes, tm, tn, a_zs);
         else if (big_rows)
-            hipLaunchKernelGGL((k_wino_bgemm<2, 2, 2, 2>), grid, dim3(256), 0, st, V, U, M, (int)T, Ca, K, a_bytes, b_bytes, tm, tn);
+            hipLaunchKernelGGL((k_wino_bgemm<2, 2, 2, 2>), grid, dim3(256), 0, st, V, U, M, (int)T, Ca, K, a_bytes, b_bytes, tm, tn, a_zs);
         else if (zb > 1)
-            hipLaunchKernelGGL((k_wino_bgemm_mz<1, 2, 2, 2>), grid, dim3(256), 0, st, V, U, M, (int)T, Ca, K, zb, a_bytes, b_bytes, tm, tn);
+            hipLaunchKernelGGL((k_wino_bgemm_mz<1, 2, 2, 2>), grid, dim3(256), 0, st, V, U, M, (int)T, Ca, K, zb, a_bytes, b_bytes, tm, tn, a_zs);
         else
-            hipLaunchKernelGGL((k_wino_bgemm<1, 2, 2, 2>), grid, dim3(256), 0, st, V, U, M, (int)T, Ca, K, a_bytes, b_bytes, tm, tn);
+            hipLaunchKernelGGL((k_wino_bgemm<1, 2, 2, 2>), grid, dim3(256), 0, st, V, U, M, (int)T, Ca, K, a_bytes, b_bytes, tm, tn, a_zs);
     }
     if (ev1) (void)hipEventRecord(ev1, st);
     if (hipGetLastError() != hipSuccess) return PG_ELAUNCH;
@@ -2536,12 +2551,13 @@ static int wino2_b2s_run(const float* big, int ld_big, const float* P, const flo
 
 int pg_wino2_b2s(const float* big, int ld_big, const float* P, const float* bias, float* small, int ld_small, int N, int Hb,
                  int Wb, int Hs, int Ws, int Ca, int Cb, int act, void* ws, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1,
-                 const float* Vpre, double* part, float* Vkeep, float* Uext, int u_valid, int s3) {
+                 const float* Vpre, double* part, float* Vkeep, float* Uext, int u_valid, int s3, long v_stride, long v_tile0) {
     if (pg_wino2_mo() == 4)
-        return wino2_b2s_run<4>(big, ld_big, P, bias, small, ld_small, N, Hb, Wb, Hs, Ws, Ca, Cb, act, ws, st, ev0, ev1, nullptr, part,
-                                nullptr, Uext, u_valid, s3);
+        return (v_stride || v_tile0) ? PG_EINVAL
+                                     : wino2_b2s_run<4>(big, ld_big, P, bias, small, ld_small, N, Hb, Wb, Hs, Ws, Ca, Cb, act, ws, st, ev0, ev1,
+                                                        nullptr, part, nullptr, Uext, u_valid, s3, 0, 0);
     return wino2_b2s_run<3>(big, ld_big, P, bias, small, ld_small, N, Hb, Wb, Hs, Ws, Ca, Cb, act, ws, st, ev0, ev1, Vpre, part, Vkeep,
-                            Uext, u_valid, s3);
+                            Uext, u_valid, s3, v_stride, v_tile0);
 }
 int pg_wino_prep_batch(int n, const pg_wino_prep* items, hipStream_t st) {
     if (n <= 0) return PG_OK;
@@ -2608,7 +2624,7 @@ size_t pg_wino2_v_bytes(int N, int Hs, int Ws, int Cb) {
 int pg_wino2_v(const float* big, int ld_big, float* V, int N, int Hb, int Wb, int Hs, int Ws, int Cb, hipStream_t st) {
     const int TH = (Hs + 2) / 3, TW = (Ws + 2) / 3;
     const long T = (long)N * TH * TW;
-    hipLaunchKernelGGL(k_wino2_v<3>, dim3((unsigned)((T * Cb + 255) / 256)), dim3(256), 0, st, big, ld_big, V, N, Hb, Wb, Cb, TH, TW);
+    hipLaunchKernelGGL(k_wino2_v<3>, dim3((unsigned)((T * Cb + 255) / 256)), dim3(256), 0, st, big, ld_big, V, N, Hb, Wb, Cb, TH, TW, T * 4 * Cb, 0L);
     return hipGetLastError() == hipSuccess ? PG_OK : PG_ELAUNCH;
 }
 
@@ -2651,15 +2667,15 @@ static int wino2_s2b_run(const float* small, int ld_small, const float* P, const
         const int zb = s3 ? 1 : bgemm_zb((long)tm * tn, X);
         const dim3 grid((unsigned)(tm * tn * (X / zb)));
         if (s3)
-            bgemm_s3_launch(big_rows, grid, st, V, U, M, (int)T, NC, Ca, a_bytes, b_bytes, tm, tn);
+            bgemm_s3_launch(big_rows, grid, st, V, U, M, (int)T, NC, Ca, a_bytes, b_bytes, tm, tn, (int)T * Ca);
         else if (big_rows && zb > 1)
-            hipLaunchKernelGGL((k_wino_bgemm_mz<2, 2, 2, 2>), grid, dim3(256), 0, st, V, U, M, (int)T, NC, Ca, zb, a_bytes, b_bytes, tm, tn);
+            hipLaunchKernelGGL((k_wino_bgemm_mz<2, 2, 2, 2>), grid, dim3(256), 0, st, V, U, M, (int)T, NC, Ca, zb, a_bytes, b_bytes, tm, tn, (int)T * Ca);
         else if (big_rows)
-            hipLaunchKernelGGL((k_wino_bgemm<2, 2, 2, 2>), grid, dim3(256), 0, st, V, U, M, (int)T, NC, Ca, a_bytes, b_bytes, tm, tn);
+            hipLaunchKernelGGL((k_wino_bgemm<2, 2, 2, 2>), grid, dim3(256), 0, st, V, U, M, (int)T, NC, Ca, a_bytes, b_bytes, tm, tn, (int)T * Ca);
         else if (zb > 1)
-            hipLaunchKernelGGL((k_wino_bgemm_mz<1, 2, 2, 2>), grid, dim3(256), 0, st, V, U, M, (int)T, NC, Ca, zb, a_bytes, b_bytes, tm, tn);
+            hipLaunchKernelGGL((k_wino_bgemm_mz<1, 2, 2, 2>), grid, dim3(256), 0, st, V, U, M, (int)T, NC, Ca, zb, a_bytes, b_bytes, tm, tn, (int)T * Ca);
         else
-            hipLaunchKernelGGL((k_wino_bgemm<1, 2, 2, 2>), grid, dim3(256), 0, st, V, U, M, (int)T, NC, Ca, a_bytes, b_bytes, tm, tn);
+            hipLaunchKernelGGL((k_wino_bgemm<1, 2, 2, 2>), grid, dim3(256), 0, st, V, U, M, (int)T, NC, Ca, a_bytes, b_bytes, tm, tn, (int)T * Ca);
     }
     if (ev1) (void)hipEventRecord(ev1, st);
     if (hipGetLastError() != hipSuccess) return PG_ELAUNCH;
@@ -2731,7 +2747,7 @@ int pg_wino2_wgrad(const float* small, int ld_small, const float* big, int ld_bi
     const float* V = Vpre ? Vpre : Vown;
     if (!Vpre) {
         hipLaunchKernelGGL(k_wino2_v<3>, dim3((unsigned)((T * Cb + 255) / 256)), dim3(256), 0, st, big, ld_big, Vown, N, Hb, Wb, Cb, TH,
-                           TW);
+                           TW, T * K, 0L);
         if (hipGetLastError() != hipSuccess) return PG_ELAUNCH;
     }
     hipLaunchKernelGGL(k_wino2_dy, dim3((unsigned)((T * (Ca / 4) + 255) / 256)), dim3(256), 0, st, small, ld_small, DY, N, Hs, Ws,

@@ -506,13 +506,29 @@ class ConvOp:
         same layer (v_pre); 0 when the two calls do not both take the polyphase Winograd path."""
         return self._query(('v',), lambda: L.load().pg_conv_v_bytes(ctypes.byref(self.g), self.algo, self.ws_arg))
 
+    def halves_same(self, whole):
+        """big2small of this op (N samples) and of `whole` (the same layer on 2 N samples) do the same arithmetic per sample
+        (pg_conv_batch_halves_same: same kernel, no split over K, V kept in both or in neither): two calls of this op on the halves
+        of a 2 N batch fill what one call of `whole` fills, bit for bit."""
+        assert whole.g.key()[1:] == self.g.key()[1:] and whole.N == 2 * self.N and whole.algo == self.algo
+        return bool(self._query(('halves', whole.ws_arg), lambda: L.load().pg_conv_batch_halves_same(
+            ctypes.byref(self.g), self.algo, self.ws_arg, whole.ws_arg)))
+
+    def v_part(self, whole, n0):
+        """(v_stride, v_tile0) with which big2small of this op, run on samples [n0, n0 + N) of the batch of `whole`, keeps its
+        transformed input in the buffer of whole.v_bytes() bytes: V[point][tile][k], the tiles of the whole batch inside every
+        point's plane."""
+        points, k = (16, 4 * self.Cb) if self.stride == 2 else (36, self.Cb)
+        stride = whole.v_bytes() // (4 * points)
+        return stride, n0 * (stride // k) // whole.N
+
     @staticmethod
-    def _extras(part=None, v_keep=None, v_pre=None, u_cache=None, u_valid=False, mul=None):
+    def _extras(part=None, v_keep=None, v_pre=None, u_cache=None, u_valid=False, mul=None, v_part=(0, 0)):
         if part is None and v_keep is None and v_pre is None and u_cache is None and mul is None:
             return None
         p = lambda t: t.data_ptr() if t is not None else None
         mt, ml, ma = (mul[0].ptr(), mul[0].ld, mul[1]) if mul is not None else (None, 0, 0)
-        return L.ConvExtras(p(part), p(v_keep), p(v_pre), p(u_cache), 1 if u_valid else 0, mt, ml, ma)
+        return L.ConvExtras(p(part), p(v_keep), p(v_pre), p(u_cache), 1 if u_valid else 0, mt, ml, ma, v_part[0], v_part[1])
 
     def mul_ok(self, small, big, t):
         """small2big(small -> big) can fold `big *= f'(t)` into its epilogue (pg_conv_extras.mul_t): the kernel of this call supports
@@ -526,14 +542,16 @@ class ConvOp:
         return bool(self._query(('mul', io), lambda: L.load().pg_conv_mul_ok(ctypes.byref(self.g), self.algo | io,
                                                                               self.ws_arg)))
 
-    def big2small(self, big, P, p_off, bias, b_off, small, act=L.ACT_NONE, part=None, v_keep=None, u_cache=None, u_valid=False):
-        """part / v_keep / u_cache: the optional hand-overs of pg_conv_extras (sizes: stats_chunks(0), v_bytes(), u_bytes(0))."""
+    def big2small(self, big, P, p_off, bias, b_off, small, act=L.ACT_NONE, part=None, v_keep=None, u_cache=None, u_valid=False,
+                  v_part=(0, 0)):
+        """part / v_keep / u_cache: the optional hand-overs of pg_conv_extras (sizes: stats_chunks(0), v_bytes(), u_bytes(0)).
+        v_part: v_keep is the buffer of this layer on a larger batch and this call fills its own rows of it (see v_part())."""
         assert (big.N, big.H, big.W, big.C) == (self.N, self.Hb, self.Wb, self.Cb), 'big view mismatch'
         assert (small.N, small.H, small.W, small.C) == (self.N, self.Hs, self.Ws, self.Ca), 'small view mismatch'
         wp, wn = self._ws(P.device)
         args = (big.ptr(), big.ld, L.ptr(P, p_off), L.ptr(bias, b_off) if bias is not None else None, small.ptr(), small.ld,
                 ctypes.byref(self.g), act, self.algo | self._io(big, small), wp, wn, _stream())
-        x = self._extras(part=part, v_keep=v_keep, u_cache=u_cache, u_valid=u_valid)
+        x = self._extras(part=part, v_keep=v_keep, u_cache=u_cache, u_valid=u_valid, v_part=v_part if v_keep is not None else (0, 0))
 
         def go():
             if x is None:
@@ -1534,7 +1552,18 @@ def disc_layers(input_nc, ndf, n_layers, norm, norm_kind='instance'):
 
 
 class DiscContext:
-    pass
+    def samples(self, n0, n):
+        """The context of samples [n0, n0 + n) of this pass, for a backward pass WITHOUT weight gradients (the generator step's data
+        gradient through D reads the fake half of the step's one 2N context): views of the same tensors, no kept V."""
+        assert not self.bf and not any(s is not None for s in self.stats), 'sample views: fp32 contexts without a norm layer'
+        c = DiscContext()
+        c.N, c.H, c.W = n, self.H, self.W
+        c.bn_train, c.bn_nseg, c.bn_dist, c.bf, c.seam8 = self.bn_train, self.bn_nseg, self.bn_dist, self.bf, self.seam8
+        c.din = self.din.samples(n0, n)
+        c.t, c.a, c.src = ([v.samples(n0, n) for v in vs] for vs in (self.t, self.a, self.src))
+        c.stats, c.v = list(self.stats), [None] * len(self.v)
+        c.out = c.a[-1]
+        return c
 
 
 class DiscriminatorEngine(_WeightPrep):
@@ -1577,6 +1606,57 @@ class DiscriminatorEngine(_WeightPrep):
     def out_shape(self, N, H, W):
         op = self.ops(N, H, W)[-1]
         return (N, 1, op.Hs, op.Ws)
+
+    def halves_ok(self, N, H, W):
+        """One pass over 2 N samples may be run as two passes over N samples each that fill one context (forward_part): a network
+        without norm layers on fp32 tensors, every layer's N-sample call doing per sample what its 2 N-sample call does
+        (ConvOp.halves_same), and every layer's second half starting on a 16-byte boundary (the views of the two halves then take
+        the same kernels as the whole tensor's).  InstanceNorm / BatchNorm discriminators and bf16 networks answer False: their
+        callers keep the separate passes."""
+        key = ('halves', N, H, W)
+        if key not in self._ops:
+            ok = not self.norm and not self.act_bf and (self.algo & L.ALGO_MASK) in (L.ALGO_AUTO, L.ALGO_MFMA, L.ALGO_DIRECT)
+            if ok:
+                half, whole = self.ops(N, H, W), self.ops(2 * N, H, W)
+                ok = all(h.halves_same(w) and (N * h.Hs * h.Ws * h.Ca * 4) % 16 == 0 for h, w in zip(half, whole))
+            self._ops[key] = ok
+        return self._ops[key]
+
+    def context(self, flat, din, keep_v=False):
+        """An empty context of a pass over din [Nt,H,W,input_nc] (needs halves_ok(Nt / 2, H, W)): every layer's output tensor and
+        kept transform allocated for Nt samples, nothing launched.  forward_part() fills it half by half; once both halves are in
+        it is what forward(flat, din, keep_v=keep_v) returns."""
+        ops = self.ops(din.N, din.H, din.W)
+        dev = flat.device
+        c = DiscContext()
+        c.din, c.N, c.H, c.W = din, din.N, din.H, din.W
+        c.bn_train, c.bn_nseg, c.bn_dist, c.bf, c.seam8 = False, 1, None, False, False
+        c.t, c.stats, c.a, c.v, c.src = [], [], [], [], []
+        src = din
+        for l, op in zip(self.layers, ops):
+            c.src.append(src)
+            t = View.alloc(din.N, op.Hs, op.Ws, l.a, dev)
+            vb = op.v_bytes() if (keep_v and KEEP_V and ConvOp._aligned(src, t) and ConvOp.fits(src, t)) else 0
+            c.v.append(torch.empty(vb, dtype=torch.uint8, device=dev) if vb else None)
+            c.t.append(t)
+            c.stats.append(None)
+            c.a.append(t)
+            src = t
+        c.out = src
+        return c
+
+    def forward_part(self, flat, c, n0, n, ucache=None):
+        """Samples [n0, n0 + n) of the pass whose context c is (context()): the n-sample plan of every layer, reading and writing
+        the sample ranges of c's tensors; a kept transform goes into its rows of the whole batch's buffer (ConvOp.v_part)."""
+        whole = self.ops(c.N, c.H, c.W)
+        dev = flat.device
+        for li, (l, op) in enumerate(zip(self.layers, self.ops(n, c.H, c.W))):
+            src, t = c.src[li].samples(n0, n), c.t[li].samples(n0, n)
+            bias = flat if l.bias_key is not None else None
+            u, uv = _ucache(ucache, li, 0, op, dev, src, t, l.p_off)
+            vk = c.v[li]
+            op.big2small(src, flat, l.p_off, bias, l.b_off, t, L.ACT_CODES[l.act], v_keep=vk, u_cache=u, u_valid=uv,
+                         v_part=op.v_part(whole[li], n0) if vk is not None else (0, 0))
 
     def forward(self, flat, din, ucache=None, keep_v=False, bn=None):
         """din: View [N,H,W,input_nc].  Returns a context; ctx.out is the sigmoid patch map View [N,h,w,1].

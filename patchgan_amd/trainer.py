@@ -8,6 +8,8 @@ Per-step schedule (reference trainer.py:50-115):
    dgrad through D (its weight grads are skipped: the reference zeroes them at trainer.py:93-94) ->
    G bwd -> Adam(G) -> D fwd over din[2N] (real and detached fake in one batch) -> BCE halves -> D bwd -> Adam(D) ->
    one device->host copy of the loss scalars.
+   Where the planner allows it (SHARE_D_FAKE, DiscriminatorEngine.halves_ok) the two D forwards are two N-sample half passes that fill
+   ONE 2N context: D fwd(fake) is its fake half, the later pass only adds the real half -- D(x | G(x)) is computed once.
    Under data parallelism: G's gradient buckets are all-reduced asynchronously from inside G bwd and Adam(G) moves behind
    the D backward; D's gradient is all-reduced asynchronously and Adam(D) moves behind the next step's G forward (flush()).
    On two streams (a device-bound kind of step; engine.Exec) the same launches are spread over two in-order chains: the weight
@@ -43,6 +45,10 @@ ADAM_G_BESIDE = E._exp_env('PATCHGAN_ADAM_G_BESIDE') != '0'      # ... and G's A
 #  RCCL group: the compute stream shared a hardware queue with a stream waiting for the deferred pass; patchgan_amd/__init__.py asks
 #  for 8 queues: 8.51)
 DEFER_D_BWD_DP = E._exp_env('PATCHGAN_DEFER_D_BWD_DP') != '0'
+# D(x | G(x)) once per step: the generator step's pass over the fake batch and the fake half of the discriminator step's 2N pass read the
+# same bytes with the same weights -- run as two half passes that fill ONE 2N context (engine.DiscriminatorEngine.forward_part) where the
+# planner says the halves compute what the whole computes (halves_ok); off = the reference's three passes (A/B switch, tests)
+SHARE_D_FAKE = E._exp_env('PATCHGAN_SHARE_D_FAKE') != '0'
 DEFER_D_BWD = E._exp_env('PATCHGAN_DEFER_D_BWD') != '0'      # two-stream step: the discriminator's backward pass + Adam(D) under the NEXT step's generator forward (A/B switch)
 
 
@@ -447,12 +453,23 @@ class Trainer:
         # weights, both final here -- it is enqueued on the second stream now and runs under the rest of the generator step (same
         # kernels, same 2N plan: bit-identical); joined where the discriminator step reads its output
         dc2 = None
+        # shared pass: the step's ONE context over din[2N]; its fake half is filled on this stream where the generator step needs it, its
+        # real half (x | y and D's weights only) wherever the 2N pass would run.  Its tensors are allocated here, on this stream, before
+        # the fork: both streams write into them, and they are released only after the streams have joined.
+        # (both halves of din on one 16-byte phase: the first layer then takes the same kernel for either as for the whole buffer)
+        shared = (de.context(D.flat, din, keep_v=train)
+                  if (SHARE_D_FAKE and de.halves_ok(N, H, W) and (fake.ptr() - real.ptr()) % 16 == 0) else None)
+        real_done = False
         # (evaluation passes and data-parallel steps too; under data parallelism D's deferred update of the previous step has been
         #  applied by flush() above, and on_side() orders the second stream behind it)
         if ex.enabled and E.PROFILER is None and EARLY_D_FWD:      # (bf16 networks too: 5.93 -> 5.84 ms at cfg4)
             n_prepared = len(ucache)
             with E.on_side():
-                dc2 = de.forward(D.flat, din, ucache=ucache, keep_v=train, bn=D.bn_run(1, 2))
+                if shared is not None:
+                    de.forward_part(D.flat, shared, 0, N, ucache=ucache)
+                    real_done = True
+                else:
+                    dc2 = de.forward(D.flat, din, ucache=ucache, keep_v=train, bn=D.bn_run(1, 2))
                 self._mark('side: dc2 fwd done')
             if len(ucache) != n_prepared:
                 # (a transformed-weight entry the batched preparation did not cover was made by a kernel on the second stream -- the
@@ -460,7 +477,11 @@ class Trainer:
                 E.side_join()
         # (BatchNorm discriminator: this pass's batch statistics go to slot 0, the 2N pass's halves to slots 1 and 2 -- the order of the
         #  reference's three calls, trainer.py:66,97,99, whichever pass runs first here)
-        dc = de.forward(D.flat, fake, ucache=ucache, bn=D.bn_run(0, 1))                       # trainer.py:66
+        if shared is not None:
+            de.forward_part(D.flat, shared, N, N, ucache=ucache)                              # trainer.py:66 (and the fake half of :98-99)
+            dc = shared.samples(N, N)
+        else:
+            dc = de.forward(D.flat, fake, ucache=ucache, bn=D.bn_run(0, 1))                   # trainer.py:66
         gseg = E.View.alloc(N, H, W, Cout, dev) if train else None
         E.loss_finish(seg_pending, _LOSS_MODES[self.loss_type], float(self.seg_alpha), gseg, losses, 0, Bglobal,
                       self.tversky_gamma)                                                     # trainer.py:71-82
@@ -497,7 +518,11 @@ class Trainer:
         del dc
 
         # ---- discriminator step: real and (pre-update, detached) fake in one 2N batch        trainer.py:96-99
-        if dc2 is None:
+        if shared is not None:
+            if not real_done:
+                de.forward_part(D.flat, shared, 0, N, ucache=ucache)                          # trainer.py:96-97
+            dc2 = shared
+        elif dc2 is None:
             dc2 = de.forward(D.flat, din, ucache=ucache, keep_v=train, bn=D.bn_run(1, 2))
         if ex.pending or ex.keep:
             E.side_join()
