@@ -471,6 +471,23 @@ int pg_loss_value_grad(const double* Spart, int nsplit, double* S_out, const dou
                        int Bglobal, float alpha, float beta, float gamma, const float* p, int ld_p, const float* y, int ld_y,
                        float tconst, float* g, int ld_g, float* loss_out, void* stream);
 
+/* ---- segmentation metrics (beyond the reference, which reports loss scalars only; the call sites are patchgan_amd's
+ * Trainer.batch(train=False) beside the segmentation loss's pg_loss_reduce_parts, and Trainer.evaluate) -------------
+ * The integer counts IoU / Dice / precision / recall / pixel accuracy are made of.  p (prediction) and y (target) are fp32 NHWC channel
+ * slices as pg_loss_reduce takes them.  K = 2 for C == 1, else K = C; `counts` holds K*K + 1 64-bit words on the device and the call
+ * ADDS to them (one buffer collects a whole validation pass; the caller zeroes it):
+ *   counts[t*K + q]  pixels of true class t predicted as class q
+ *   counts[K*K]      ignored pixels
+ *   C == 1: q = (p >= threshold), t = (y >= 0.5f); nothing is ignored.
+ *   C  > 1: q / t = FIRST index of the maximum of p[0..C) / y[0..C) (strict `>` scan from channel 0: numpy.argmax, pg_tiles_blend --
+ *           q is the class patchgan_infer writes); `threshold` is not read.  A pixel whose largest y is <= 0 has no listed label (a
+ *           one-hot mask over a label subset): it is ignored -- counts[K*K] += 1 and nothing else.
+ * Inputs are finite (NaN: unspecified).  Integer atomics only: the sums do not depend on arrival order.
+ * PG_EINVAL before any launch: NULL p, y or counts; N, HW or C <= 0; C > pg_seg_confusion_max_c(); ld_p < C; ld_y < C. */
+int pg_seg_confusion_max_c(void);    /* 32 */
+int pg_seg_confusion(const float* p, int ld_p, const float* y, int ld_y, int N, int HW, int C, float threshold,
+                     unsigned long long* counts, void* stream);
+
 /* ---- optimizer (torch.optim.Adam defaults, trainer.py:169-172) -----------------------------------
  * m += (g-m)*(1-b1); v = v*b2 + (1-b2)*g*g; p -= (lr/bc1) * m / (sqrt(v)/sqrt_bc2 + eps)
  * over n contiguous floats; bc1 = 1-b1^t and sqrt_bc2 = sqrt(1-b2^t) are computed by the caller. */

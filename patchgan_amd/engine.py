@@ -990,6 +990,18 @@ def adam_ema_step_dev(p, g, m, v, ema, scalars, ema_decay, beta1=0.9, beta2=0.99
                                           beta2, eps, scalars.data_ptr(), ema_decay, _stream()), 'pg_adam_ema_step_dev')
 
 
+def seg_confusion(p, y, threshold, counts):
+    """Add the confusion counts of prediction View p against target View y (fp32, the same shape) to `counts`: an int64 device tensor
+    of K*K + 1 words, K = 2 for one channel (p >= threshold against y >= 0.5) and the channel count otherwise (first maximum against
+    first maximum; a pixel without a positive target channel counts as ignored in the last word).  pg_seg_confusion, on the current
+    stream; nothing is read back (metrics.SegCounts.read does that, once per pass)."""
+    assert (p.N, p.H, p.W, p.C) == (y.N, y.H, y.W, y.C) and not p.bf and not y.bf, 'seg_confusion takes fp32 views of one shape'
+    K = 2 if p.C == 1 else p.C
+    assert counts.dtype == torch.int64 and counts.numel() == K * K + 1 and counts.is_contiguous() and counts.device == p.t.device
+    L.check(L.load().pg_seg_confusion(p.ptr(), p.ld, y.ptr(), y.ld, p.N, p.HW, p.C, float(threshold), counts.data_ptr(), _stream()),
+            'pg_seg_confusion')
+
+
 def tiles_gather(image, size, overlap):
     """reference infer.py:14-35 (n_crop): device image [C, H, W] -> View of the ny*nx overlapping size x size tiles in the
     NHWC batch layout the generator kernels read."""

@@ -34,6 +34,7 @@ import tqdm
 
 from . import _lib as L
 from . import engine as E
+from .metrics import BestTracker, SegCounts, report
 from .parallel import current as _dist, GradReducer
 
 device = 'cuda' if torch.cuda.is_available() else 'cpu'
@@ -173,6 +174,16 @@ class Trainer:
     # the same all-reduced gradient, so the averages agree without a collective.
     ema_decay = None
 
+    # Segmentation metrics of evaluation passes (opt-in, beyond the reference): None = off -- no launch, no buffer, no key, file or
+    # printed line.  True: every batch(train=False) adds ONE launch beside its segmentation loss (engine.seg_confusion: the confusion
+    # counts of G(x) against y, integers, accumulated in `seg_counts` on the device; reset_metrics() / read_metrics()), train() records
+    # IoU / Dice / precision / recall / pixel accuracy of every validation pass in `val_history` -- with ema_decay also of the
+    # averaged generator (evaluate()) -- and save_best = 'miou' | 'mdice' keeps the best epoch's weights as best_generator.pth /
+    # best_discriminator.pth (/ best_generator_ema.pth) with best_metrics.json.  Training steps never launch it.
+    metrics = None
+    metric_threshold = 0.5   # one-channel masks: prediction >= this is foreground (several channels: the first maximum, no threshold)
+    save_best = None
+
     neptune_config = None
     label_values = None      # label list of the dataset, only for the uint8 (device-side) input path of batch()
     gc_freeze = False        # opt-in: gc.collect() + gc.freeze() after training steps 1 and 3 (_settle_gc; process-global)
@@ -241,6 +252,9 @@ class Trainer:
         self._exec = None          # engine.Exec: this trainer's workspaces and second stream (created on the networks' device)
         self._oom_kinds, self.oom_fallbacks = set(), 0      # kinds of step pinned to one stream after an out-of-memory two-stream step
         self._ema = self._ema_net = None      # the generator's weight average: flat fp32 buffer + the UNet that views it (ema_decay)
+        self.seg_counts = None     # metrics.SegCounts of the evaluation steps since reset_metrics() (created by the first one; `metrics`)
+        self.val_history = []      # train() with metrics: one dict per epoch (losses + scores of the validation pass)
+        self._best = None          # metrics.BestTracker (save_best)
 
     # -------------------------------------------------------------------------------------- optimizers
     def setup_optimizers(self, gen_lr=1e-3, dsc_lr=1e-3):
@@ -297,9 +311,76 @@ class Trainer:
             self.flush()
             self._ema.copy_(self.generator.flat)
 
+    # -------------------------------------------------------------------------------------- segmentation metrics
+    def _seg_counts(self):
+        """The counts evaluation steps add to, created on first use (on the generator's device, for its output channels)."""
+        G = self.generator
+        sc = self.seg_counts
+        if sc is None or sc.C != G.engine.output_nc or sc.t.device != G.flat.device:
+            sc = self.seg_counts = SegCounts(G.engine.output_nc, G.flat.device)
+        return sc
+
+    def reset_metrics(self):
+        """Zero the counts of the evaluation steps (Trainer.metrics); the validation pass of train() starts with it."""
+        self._seg_counts().zero_()
+
+    def read_metrics(self):
+        """Scores of the evaluation steps since reset_metrics(): metrics.scores() of their confusion matrix plus `confusion` (np.int64
+        [K, K], [true class][predicted class]) and `ignored`.  Waits for the device; under data parallelism the ranks' counts are
+        summed, which is a collective: every rank calls it."""
+        return report(*self._seg_counts().read(_dist()))
+
+    def evaluate(self, data, generator=None):
+        """A generator-only pass over `data` (an iterable of (x, y) batches as batch() takes them): no discriminator, no update.
+        `generator`: any UNet of the live generator's geometry on its device -- None = the live one, `trainer.ema_generator` the
+        intended other.  It runs in eval mode (restored afterwards).  Per batch: one generator forward writing into the view an
+        evaluation batch() uses (so its head layer runs the same kernel: the pass is bit-comparable to batch(train=False)), the
+        segmentation loss by batch()'s own calls, and the confusion counts -- into counts of this call's own, not `seg_counts`.
+        Nothing is read back per batch: the loss values are summed on the device.  Returns {'seg_loss': mean over the batches,
+        **scores, 'confusion', 'ignored'}; under data parallelism every rank passes its shard and gets the global result (collective)."""
+        net = self.generator if generator is None else generator
+        G = self.generator
+        ge, dev = net.engine, G.flat.device
+        if (ge.input_nc, ge.output_nc) != (G.engine.input_nc, G.engine.output_nc) or net.flat.device != dev:
+            raise RuntimeError("evaluate(): the generator must have the live generator's channels and device")
+        self.flush()
+        dist = _dist()
+        counts = SegCounts(ge.output_nc, dev)
+        total = torch.zeros(1, dtype=torch.float64, device=dev)
+        allred = dist.all_reduce_side if dist.on else None
+        ex = self._exec
+        if ex is None or ex.device != dev:
+            ex = self._exec = E.Exec(dev)
+        was_training, nbatches = net.training, 0
+        net.eval()
+        try:
+            with ex:
+                for x, y in data:
+                    x, y, u8, N, H, W, Cin, Cout = self._inputs(x, y)
+                    din, real, fake = self._din(x, y, u8, N, H, W, Cin, Cout)
+                    xin, yv, gen = fake.channels(0, Cin), real.channels(Cin, Cout), fake.channels(Cin, Cout)
+                    loss = torch.empty(1, dtype=torch.float32, device=dev)
+                    ge.forward(net.flat, xin, gen, False, 0, sample0=dist.rank * N, bn=net.bn_run())
+                    pending = E.loss_begin(gen, yv, 0.0, self.tversky_beta, allred)
+                    E.seg_confusion(gen, yv, self.metric_threshold, counts.t)
+                    E.loss_finish(pending, _LOSS_MODES[self.loss_type], float(self.seg_alpha), None, loss, 0, N * dist.world,
+                                  self.tversky_gamma)
+                    total += loss
+                    nbatches += 1
+        finally:
+            net.train(was_training)
+        if dist.on and self.loss_type != 'tversky':
+            # (focal-Tversky's value is global on every rank already; the others are per-rank partial means: batch() sums them too)
+            if dist.backend != 'nccl':
+                total = total.cpu()
+            dist.dist.all_reduce(total, op=dist.dist.ReduceOp.SUM)
+        out = report(*counts.read(dist))
+        seg = float(total.cpu()[0]) / nbatches if nbatches else float('nan')
+        return dict({'seg_loss': seg}, **out)
+
     # -------------------------------------------------------------------------------------- one G+D step
-    def batch(self, x, y, train=False):
-        t_host0 = time.perf_counter()
+    def _inputs(self, x, y):
+        """One batch as batch() / evaluate() take it, on the generator's device: (x, y, u8, N, H, W, Cin, Cout)."""
         G, D = self.generator, self.discriminator
         dev = G.flat.device
         if dev.type != 'cuda':
@@ -332,6 +413,13 @@ class Trainer:
         if Cin != ge.input_nc or Cout != ge.output_nc or Cin + Cout != de.input_nc:
             raise RuntimeError(f"channel mismatch: x {Cin}, y {Cout} vs generator ({ge.input_nc}->{ge.output_nc}), "
                                f"discriminator input {de.input_nc}")
+        return x, y, u8, N, H, W, Cin, Cout
+
+    def batch(self, x, y, train=False):
+        t_host0 = time.perf_counter()
+        G, D = self.generator, self.discriminator
+        x, y, u8, N, H, W, Cin, Cout = self._inputs(x, y)
+        dev = G.flat.device
         if train and self._adam is None:
             self.setup_optimizers(self.gen_lr, self.dsc_lr)
         if train and self._ema is not None and self.ema_decay is not None:
@@ -390,6 +478,28 @@ class Trainer:
             ev.record()
             self.marks.append((name, ev, time.perf_counter()))
 
+    def _din(self, x, y, u8, N, H, W, Cin, Cout):
+        """The discriminator input buffer of one step, filled from the device-resident inputs: (din, real, fake) with samples [0,N)
+        real = x|y and [N,2N) fake = x|G(x) (trainer.py:65,96,98), the generator's output channels still to be written."""
+        dev = self.generator.flat.device
+        de = self.discriminator.engine
+        Cd = Cin + Cout
+        # (bf16 networks read it through pg_pad8_bf16: 8-float pixels there, so that pass and the fill below move whole 16-byte pieces)
+        ld_din = 8 if (4 < Cd < 8 and (de.algo & L.ALGO_MASK) == L.ALGO_BF16) else Cd
+        din = E.View(torch.empty(2 * N * H * W * ld_din, dtype=torch.float32, device=dev), 0, ld_din, 2 * N, H, W, Cd)
+        real, fake = din.samples(0, N), din.samples(N, N)
+        if u8:
+            real.channels(0, Cin).from_u8(x)
+            fake.channels(0, Cin).from_u8(x)
+            real.channels(Cin, Cout).from_labels(y, self.label_values)
+        elif Cd <= 8:
+            E.din_fill(x, y, real, fake)       # both halves' x | y (and the fake half's zeroed mask channels) in one launch
+        else:
+            real.channels(0, Cin).from_nchw(x)
+            fake.channels(0, Cin).from_nchw(x)
+            real.channels(Cin, Cout).from_nchw(y)
+        return din, real, fake
+
     def _enqueue_step(self, x, y, u8, N, H, W, Cin, Cout, train):
         """Every launch of one step on the current stream, from the device-resident inputs to the four loss scalars (returned as a
         device tensor).  Nothing in here reads the device; the only step-dependent HOST values are the dropout seed (self._step) and
@@ -408,25 +518,10 @@ class Trainer:
                               'the data-parallel step keeps five streams busy and loses ~0.6 ms per step at cfg2 with the default 4 hardware '
                               'queues -- import patchgan_amd first or export GPU_MAX_HW_QUEUES=8')
         Bglobal = N * dist.world
-        Cd = Cin + Cout
         ex = E.cur_exec(dev)
         self._mark('start')
 
-        # discriminator input buffer: samples [0,N) real = x|y, [N,2N) fake = x|G(x)   (trainer.py:65,96,98)
-        # (bf16 networks read it through pg_pad8_bf16: 8-float pixels there, so that pass and the fill below move whole 16-byte pieces)
-        ld_din = 8 if (4 < Cd < 8 and (de.algo & L.ALGO_MASK) == L.ALGO_BF16) else Cd
-        din = E.View(torch.empty(2 * N * H * W * ld_din, dtype=torch.float32, device=dev), 0, ld_din, 2 * N, H, W, Cd)
-        real, fake = din.samples(0, N), din.samples(N, N)
-        if u8:
-            real.channels(0, Cin).from_u8(x)
-            fake.channels(0, Cin).from_u8(x)
-            real.channels(Cin, Cout).from_labels(y, self.label_values)
-        elif Cd <= 8:
-            E.din_fill(x, y, real, fake)       # both halves' x | y (and the fake half's zeroed mask channels) in one launch
-        else:
-            real.channels(0, Cin).from_nchw(x)
-            fake.channels(0, Cin).from_nchw(x)
-            real.channels(Cin, Cout).from_nchw(y)
+        din, real, fake = self._din(x, y, u8, N, H, W, Cin, Cout)
         xin, yv, gen = fake.channels(0, Cin), real.channels(Cin, Cout), fake.channels(Cin, Cout)
 
         losses = torch.empty(4, dtype=torch.float32, device=dev)   # seg, gdisc, real*0.5, fake*0.5 (each written by its loss kernel)
@@ -446,6 +541,10 @@ class Trainer:
         # seg loss, phase 1 (per-sample reductions); under data parallelism its two batch-global terms are summed across
         # ranks on the comm stream while the discriminator's forward pass over the fake batch runs
         seg_pending = E.loss_begin(gen, yv, 0.0, self.tversky_beta, allred)
+        if self.metrics and not train:
+            # evaluation step: the confusion counts of G(x) against y, one more pass over the bytes the loss reduction just read (on this
+            # stream in every launch mode; never in a training step, so a captured step does not hold it)
+            E.seg_confusion(gen, yv, self.metric_threshold, self._seg_counts().t)
         # D's weights do not change until the Adam step at the end of this call: its Winograd-transformed weights are computed
         # once per (layer, direction) and shared by the passes below through this per-step cache
         ucache = de.ucache_begin(D.flat, N, H, W, tag=bool(train))
@@ -668,7 +767,9 @@ class Trainer:
                 tuple(self.label_values) if self.label_values is not None else None, G.training, D.training,
                 G.engine.algo, bool(G.engine.act_bf), D.engine.algo, bool(D.engine.act_bf), G.flat.data_ptr(), D.flat.data_ptr(),
                 tuple(x.shape), tuple(y.shape), x.dtype, y.dtype, _dist().on,
-                self._ema_now())          # (the decay is a launch argument of Adam(G): a captured step holds the value it was captured with)
+                self._ema_now(),          # (the decay is a launch argument of Adam(G): a captured step holds the value it was captured with)
+                # (an evaluation step with the metrics launch is another kind of step than one without: never timed against each other)
+                (float(self.metric_threshold) if self.metrics else None) if not train else None)
 
     def _launch_mode(self, key, train):
         """'eager1' (launch by launch, one stream) | 'eager2' (launch by launch, two streams) | 'graph' (replay) for this step of kind
@@ -898,7 +999,14 @@ class Trainer:
               lr_decay=None, decay_freq=5, reduce_on_plateau=False):
         """Reference trainer.py:117-279: Adam(lr, betas=(0.9, 0.999)) for G and D, optional exponential LR decay every
         `decay_freq` epochs (resumed as lr*decay^((start-1)/decay_freq)), per-epoch train + validation loops, checkpoint
-        every `save_freq` epochs.  Returns (G_loss_ep, D_loss_ep): per-epoch means of the training losses."""
+        every `save_freq` epochs.  Returns (G_loss_ep, D_loss_ep): per-epoch means of the training losses.
+        With `metrics` the validation pass also yields IoU / Dice (val_history, one printed line per epoch) and `save_best` keeps the
+        best epoch's weights (_validated)."""
+        if self.save_best is not None:
+            if not self.metrics:
+                raise ValueError(f"Trainer.save_best = {self.save_best!r} needs Trainer.metrics = True (the score comes from the validation counts)")
+            if self._best is None or self._best.metric != self.save_best:
+                self._best = BestTracker(self.save_best)      # (a resumed run keeps what load_last_checkpoint() read back)
         if (lr_decay is not None) and not reduce_on_plateau:
             gen_lr = gen_learning_rate * (lr_decay) ** ((self.start - 1) / (decay_freq))
             dsc_lr = dsc_learning_rate * (lr_decay) ** ((self.start - 1) / (decay_freq))
@@ -941,11 +1049,15 @@ class Trainer:
                 history[key].append(train_mean[key])
             # the reference keeps ONE running-mean dict across both loops: a validation pass without batches reports the
             # training means (trainer.py:204-262)
+            if self.metrics:
+                self.reset_metrics()
             val_mean = dict(train_mean, **self._run_epoch(val_data, False, epoch, 'Validation: '))
             if self.neptune_config is not None:
                 for phase, mean in (('train', train_mean), ('eval', val_mean)):
                     self.neptune_config[f'{phase}/gen_loss'].append(mean['gen'])
                     self.neptune_config[f'{phase}/disc_loss'].append(mean['disc'])
+            if self.metrics:
+                self._validated(epoch, val_mean, val_data)
 
             if plateau is not None:
                 self.gen_lr = plateau[0].step(val_mean['gen'])
@@ -958,6 +1070,43 @@ class Trainer:
                 self.save(epoch)
         self.flush()
         return history['gen'], history['disc']
+
+    def _validated(self, epoch, val_mean, val_data):
+        """After an epoch's validation pass with `metrics`: read its counts (a collective under data parallelism, as is the averaged
+        generator's own pass), record and print the scores, and keep the best weights so far (save_best)."""
+        live = self.read_metrics()
+        entry = dict({'epoch': epoch}, **{k: val_mean[k] for k in StepLosses.KEYS if k in val_mean})
+        entry.update(live)
+        ema = None
+        if self.ema_generator is not None:
+            ema = entry['ema'] = self.evaluate(val_data, self.ema_generator)
+        self.val_history.append(entry)
+        rank0 = _dist().rank == 0
+        if rank0:
+            def line(s):
+                return f"mIoU {s['miou']:.4f}  mDice {s['mdice']:.4f}  pixel acc {s['pixel_acc']:.4f}"
+            print(f"Validation metrics -- {line(live)}" + (f"  |  averaged generator: {line(ema)}" if ema is not None else ""))
+        if self.neptune_config is not None:
+            self.neptune_config['eval/miou'].append(live['miou'])
+            self.neptune_config['eval/mdice'].append(live['mdice'])
+        if self.save_best is None:
+            return
+        # (the scores come from all-reduced integers: every rank takes the same decision; rank 0 writes)
+        better = self._best.update('generator', epoch, live)
+        better_ema = ema is not None and self._best.update('generator_ema', epoch, ema)
+        if not (better or better_ema):
+            return
+        self.flush()
+        if not rank0:
+            return
+        if better:
+            print(f"Best {self.save_best} so far ({live[self.save_best]:.4f}): saving to {self.savefolder}best_generator.pth and best_discriminator.pth")
+            torch.save(self.generator.state_dict_contiguous(), f'{self.savefolder}/best_generator.pth')
+            torch.save(self.discriminator.state_dict_contiguous(), f'{self.savefolder}/best_discriminator.pth')
+        if better_ema:
+            print(f"Best {self.save_best} of the averaged generator so far ({ema[self.save_best]:.4f}): saving to {self.savefolder}best_generator_ema.pth")
+            torch.save(self.ema_generator.state_dict_contiguous(), f'{self.savefolder}/best_generator_ema.pth')
+        self._best.save(self.savefolder)
 
     def _run_epoch(self, data, train, epoch, desc, **bar_kwargs):
         """One pass over `data` through batch(train=...): networks switched to train() / eval(), the data source
@@ -1022,6 +1171,9 @@ class Trainer:
             self.load(f"{self.savefolder}/generator_ep_{start:03d}.pth", f"{self.savefolder}/discriminator_ep_{start:03d}.pth",
                       ema_save if os.path.exists(ema_save) else None)
             self.start = start + 1
+            best = BestTracker.load(self.savefolder)      # (save_best: the resumed run competes with the best model already on disk)
+            if best is not None:
+                self._best = best
         except Exception as e:
             print(e)
             print("Checkpoints not loaded")
