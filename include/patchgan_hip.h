@@ -547,6 +547,29 @@ int pg_tiles_gather(const float* image, int C, int H, int W, int size, int eff, 
 int pg_tiles_blend(const float* tiles, int ld, int C, int size, int eff, int H, int W, double threshold, double* mask,
                    long long* argmax, void* stream);
 
+/* ---- test-time augmentation and windowed blend around the same tiles ------------------------------
+ * K = 1, 2, 4 or 8 variants of every tile travel through the generator as further samples: with T = ny*nx tiles the batch holds
+ * K*T samples and variant k of tile t is sample k*T + t (K = 1: the layout of pg_tiles_gather).  Variant k is the [C,size,size]
+ * tile after, in this order,  k & 4: transpose(-1,-2);  k & 2: flip(-2);  k & 1: flip(-1)  -- K = 2 the horizontal flip, K = 4 both
+ * flips, K = 8 the dihedral group.  The largest K: */
+int pg_tiles_tta_max(void);   /* 8 */
+/* image [C,H,W] -> tiles [K*ny*nx, size, size, ld] NHWC.  PG_EINVAL before any launch: NULL image or tiles, C <= 0, ld < C,
+ * K not in {1,2,4,8}, H or W smaller than size. */
+int pg_tiles_gather_tta(const float* image, int C, int H, int W, int size, int eff, int K, float* tiles, int ld, void* stream);
+/* predicted tiles [K*ny*nx, size, size, ld] -> weighted average in the image frame.  `window`: `size` doubles on the device, every
+ * one finite and > 0 (the caller's duty); tile t at (sy, sx) weighs pixel (h, w) with window[h - sy] * window[w - sx].  Prediction
+ * variant k is read through the inverse map (the three steps undone in reverse order).  Per pixel and class, in doubles, each
+ * product and sum rounded once and none contracted into an FMA:
+ *     for t ascending over the tiles covering (h, w):  wgt = window[h - sy] * window[w - sx]
+ *         for k < K:  acc = acc + wgt * (double)pred[k*T + t];  wsum = wsum + wgt
+ *     v = acc / wsum
+ * then threshold and first-maximum argmax as in pg_tiles_blend, whose result this is bit for bit when the window is all ones and
+ * K = 1.  Only the covering tiles are visited; duplicate tiles (the clamped end of an axis) each count.  mask: [C,H,W] doubles or
+ * NULL; argmax: [H,W] int64 or NULL.  PG_EINVAL before any launch: NULL tiles or window, both outputs NULL, C <= 0, ld < C,
+ * K not in {1,2,4,8}, H or W smaller than size. */
+int pg_tiles_blend_win(const float* tiles, int ld, int C, int size, int eff, int H, int W, int K, const double* window,
+                       double threshold, double* mask, long long* argmax, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -146,6 +146,9 @@ SIGNATURES = {
     'pg_tiles_count': (_i, [_i, _i, _i]),
     'pg_tiles_gather': (_i, [_p, _i, _i, _i, _i, _i, _p, _i, _p]),
     'pg_tiles_blend': (_i, [_p, _i, _i, _i, _i, _i, _i, ctypes.c_double, _p, _p, _p]),
+    'pg_tiles_tta_max': (_i, []),
+    'pg_tiles_gather_tta': (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _i, _p]),
+    'pg_tiles_blend_win': (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, ctypes.c_double, _p, _p, _p]),
 }
 
 _lib = None

@@ -1002,39 +1002,104 @@ def seg_confusion(p, y, threshold, counts):
             'pg_seg_confusion')
 
 
-def tiles_gather(image, size, overlap):
+TTA_VARIANTS = {None: 1, 'hflip': 2, 'flips': 4, 'd4': 8}
+
+
+def tta_variants(tta):
+    """Number K of test-time-augmentation variants per tile: None 1, 'hflip' 2 (horizontal flip), 'flips' 4 (both flips), 'd4' 8 (the
+    dihedral group).  Variant k is transpose(-1, -2) if k & 4, then flip(-2) if k & 2, then flip(-1) if k & 1."""
+    if not (tta is None or isinstance(tta, str)) or tta not in TTA_VARIANTS:
+        raise ValueError(f"tta must be None, 'hflip', 'flips' or 'd4', not {tta!r}")
+    return TTA_VARIANTS[tta]
+
+
+def window_table(window, size):
+    """The blend window as `size` float64 weights: None (uniform) ones, 'pyramid' min(u + 1, size - u), 'hann' the half-sample
+    sin^2 form (positive everywhere), or a 1-D sequence of `size` numbers.  A pixel may be covered by a single tile, so every weight
+    must be finite and > 0: ValueError otherwise, and for an unknown name or a wrong length."""
+    if window is None:
+        return np.ones(size, dtype=np.float64)
+    if isinstance(window, str):
+        if window == 'pyramid':
+            u = np.arange(size)
+            return np.minimum(u + 1, size - u).astype(np.float64)
+        if window == 'hann':
+            return np.sin(np.pi * (np.arange(size) + 0.5) / size) ** 2
+        raise ValueError(f"window must be None, 'pyramid', 'hann' or a sequence of {size} weights, not {window!r}")
+    try:
+        table = np.array(window, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"window must be None, 'pyramid', 'hann' or a sequence of {size} weights, not {window!r}") from None
+    if table.ndim != 1 or table.shape[0] != size:
+        raise ValueError(f"a window for {size}x{size} tiles is a 1-D sequence of {size} weights, not of shape {table.shape}")
+    if not (np.isfinite(table).all() and (table > 0).all()):
+        raise ValueError("every window weight must be finite and > 0 (a pixel may be covered by a single tile)")
+    return table
+
+
+_WINDOWS = {}
+
+
+def window_dev(window, size, device):
+    """window_table on the device, uploaded once per (window, size, device)."""
+    device = torch.device(device)
+    if device.type == 'cuda' and device.index is None:
+        device = torch.device('cuda', torch.cuda.current_device())
+    named = window is None or isinstance(window, str)
+    table = None if named else window_table(window, size)
+    key = (window if named else table.tobytes(), size, device)
+    if key not in _WINDOWS:
+        _WINDOWS[key] = torch.from_numpy(window_table(window, size) if named else table).to(device)
+    return _WINDOWS[key]
+
+
+def tiles_gather(image, size, overlap, tta=None):
     """reference infer.py:14-35 (n_crop): device image [C, H, W] -> View of the ny*nx overlapping size x size tiles in the
-    NHWC batch layout the generator kernels read."""
+    NHWC batch layout the generator kernels read.  tta ('hflip' / 'flips' / 'd4', tta_variants): K variants of every tile, variant k
+    of tile t at sample k * ny*nx + t."""
     C, H, W = image.shape
     eff = int(overlap * size)
     lib = L.load()
+    K = tta_variants(tta)
     ny, nx = lib.pg_tiles_count(H, size, eff), lib.pg_tiles_count(W, size, eff)
     if ny <= 0 or nx <= 0:
         raise ValueError(f"cannot cut {size}x{size} tiles with overlap {overlap} from a {H}x{W} image")
     image = image.to(dtype=torch.float32).contiguous()
-    tiles = View.alloc(ny * nx, size, size, C, image.device)
-    L.check(lib.pg_tiles_gather(image.data_ptr(), C, H, W, size, eff, tiles.ptr(), tiles.ld, _stream()), 'pg_tiles_gather')
+    tiles = View.alloc(K * ny * nx, size, size, C, image.device)
+    if tta is None:
+        L.check(lib.pg_tiles_gather(image.data_ptr(), C, H, W, size, eff, tiles.ptr(), tiles.ld, _stream()), 'pg_tiles_gather')
+    else:
+        L.check(lib.pg_tiles_gather_tta(image.data_ptr(), C, H, W, size, eff, K, tiles.ptr(), tiles.ld, _stream()),
+                'pg_tiles_gather_tta')
     return tiles
 
 
-def tiles_blend(tiles, image_size, threshold, overlap):
+def tiles_blend(tiles, image_size, threshold, overlap, tta=None, window=None):
     """reference infer.py:38-68 (build_mask): View of predicted tiles -> overlap-averaged mask on the device: float64
-    [H, W] for one class, int64 class index [H, W] for several (same values / dtypes as the reference returns)."""
+    [H, W] for one class, int64 class index [H, W] for several (same values / dtypes as the reference returns).  With tta and / or
+    window (window_table): the K variants of a tile read back through the inverse map, each tile weighed by window[y] * window[x]."""
     H, W = image_size
     size = tiles.H
     eff = int(overlap * size)
     lib = L.load()
-    if lib.pg_tiles_count(H, size, eff) * lib.pg_tiles_count(W, size, eff) != tiles.N or tiles.W != size:
-        raise ValueError(f"{tiles.N} tiles of {tiles.H}x{tiles.W} do not tile a {H}x{W} image with overlap {overlap}")
+    K = tta_variants(tta)
+    if K * lib.pg_tiles_count(H, size, eff) * lib.pg_tiles_count(W, size, eff) != tiles.N or tiles.W != size:
+        raise ValueError(f"{tiles.N} tiles of {tiles.H}x{tiles.W} do not tile a {H}x{W} image with overlap {overlap}"
+                         + (f" in {K} variants" if K > 1 else ""))
     dev = tiles.t.device
+    table = None if tta is None and window is None else window_dev(window, size, dev)
     if tiles.C > 1:
         out = torch.empty(H, W, dtype=torch.int64, device=dev)
         mask_p, arg_p = None, out.data_ptr()
     else:
         out = torch.empty(H, W, dtype=torch.float64, device=dev)
         mask_p, arg_p = out.data_ptr(), None
-    L.check(lib.pg_tiles_blend(tiles.ptr(), tiles.ld, tiles.C, size, eff, H, W, float(threshold), mask_p, arg_p, _stream()),
-            'pg_tiles_blend')
+    if table is None:
+        L.check(lib.pg_tiles_blend(tiles.ptr(), tiles.ld, tiles.C, size, eff, H, W, float(threshold), mask_p, arg_p, _stream()),
+                'pg_tiles_blend')
+    else:
+        L.check(lib.pg_tiles_blend_win(tiles.ptr(), tiles.ld, tiles.C, size, eff, H, W, K, table.data_ptr(), float(threshold), mask_p,
+                                       arg_p, _stream()), 'pg_tiles_blend_win')
     return out
 
 
