@@ -332,7 +332,9 @@ int pg_instnorm_act_bwd(const float* g1, int ld_g1, const float* g2, int ld_g2,
 
 /* Backward of a plain activation (+dropout) from its OUTPUT a:  dy = (g1+g2) * keep/(1-p) * act'(a).
  * act' from the output: leaky a>0?1:0.2, relu a>0, tanh 1-a^2, sigmoid a(1-a), none 1.  `a` may be NULL for
- * PG_ACT_NONE. */
+ * PG_ACT_NONE.  With drop_p > 0, `a` is the POST-dropout tensor pg_act_fwd wrote for the same (drop_p, seed) --
+ * keep/(1-p) * act(y), zeros where dropped -- and the kernel multiplies it by (1-p) before taking act'; a caller that
+ * saved the pre-dropout activation must pass drop_p = 0 and apply the mask to g itself. */
 int pg_act_bwd(const float* g1, int ld_g1, const float* g2, int ld_g2, const float* a, int ld_a,
                float* dy, int ld_dy, long npix, int C, int act, float drop_p, uint64_t seed, void* stream);
 

@@ -740,9 +740,13 @@ extern "C" {
 
 size_t pg_instnorm_workspace_bytes(int N, int HW, int C) {
     if (N <= 0 || HW <= 0 || C <= 0) return 0;
-    ChunkPlan a = chunk_plan(N, HW, C, 4), b = chunk_plan(N, HW, C, 1);
-    size_t x = a.part_bytes + a.coef_bytes;
+    ChunkPlan b = chunk_plan(N, HW, C, 1);
+    size_t x = 0;
     const size_t y = b.part_bytes + b.coef_bytes;
+    if (C >= 4) {           // fewer than 4 channels have no VEC 4 plan: its channel-group count is 0, and chunk_plan divides by it
+        ChunkPlan a = chunk_plan(N, HW, C, 4);
+        x = a.part_bytes + a.coef_bytes;
+    }
     if (C % 8 == 0) {
         ChunkPlan c = chunk_plan(N, HW, C, 8);
         x = std::max(x, c.part_bytes + c.coef_bytes);

@@ -499,7 +499,9 @@ def _rel(got, want):
 @pytest.mark.parametrize('shape', [(3, 6, 5, 7), (2, 8, 16, 32), (2, 64, 23, 23)], ids=lambda s: 'x'.join(map(str, s)))
 def test_instnorm_chunked_and_fallback_paths(shape, mix, wsmode):
     """pg_instnorm_act_fwd / _bwd (all_fp32) and their _t forms (the three storage mixes of test_instnorm_act_mixed_storage) on the
-    scalar path (C % 4 != 0), the smallest plane the chunk plan splits (HW = 512) and a ragged last chunk (HW = 529), with a workspace
+    scalar path (C % 4 != 0), the smallest plane the chunk plan splits (HW = 512; not for all_bf16, whose 8 channels are one 16-byte unit
+    there: one chunk, the one-workgroup kernels -- tests/test_normact_gpu.py has the smallest split bf16 plane, C = 16) and a ragged last
+    chunk (HW = 529), with a workspace
     of exactly pg_instnorm_workspace_bytes, NULL, and one 256-byte step too small (the last two: the one-workgroup fallback).  Against
     float64 autograd: 1e-5 forward, 5e-5 backward (fp32 results; bf16 results within one bf16 ulp of the rounded value, inputs
     bf16-representable)."""
