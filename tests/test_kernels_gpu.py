@@ -398,13 +398,14 @@ def test_bce_const_target(target):
 
 @pytest.mark.parametrize('mode_name,N,C,H,W', [('tversky', 16, 1, 256, 256), ('tversky', 3, 4, 64, 80), ('weighted_bce', 8, 4, 128, 128),
                                                ('weighted_bce', 4, 7, 64, 64), ('MAE', 2, 2, 40, 24), ('bce', 16, 1, 30, 30),
-                                               ('bce', 36, 7, 8, 8)])
+                                               ('bce', 36, 7, 8, 8), ('bce', 10, 1, 160, 160)])
 def test_two_launch_loss_equals_the_staged_one(mode_name, N, C, H, W):
     """pg_loss_reduce_parts + pg_loss_value_grad (one reduction launch, one value + gradient launch: what Trainer.batch runs in one
     process) are bit-identical to the staged pg_loss_reduce (+ combine) / pg_loss_prepare / pg_loss_finalize / pg_loss_grad chain
     that data parallelism keeps (the batch-global terms are all-reduced between its stages) -- with and without a caller-supplied
     gsum2, with and without a gradient, on split and unsplit reductions (four-channel kernel included); beyond N*C = 256 the
-    two-launch form refuses and the engine stages."""
+    two-launch form refuses and the engine stages.  10 x 1 x 160 x 160 has 25 slabs: the one-launch form's unrolled group of 16 and
+    its remainder loop in one call."""
     from patchgan_amd import engine as E, _lib as L
     from tests.gpu_util import to_view, empty_view, DEV
     lib = L.load()
