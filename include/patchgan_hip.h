@@ -511,7 +511,40 @@ int pg_adam_ema_step(float* p, const float* g, float* m, float* v, float* ema, l
 int pg_adam_ema_step_dev(float* p, const float* g, float* m, float* v, float* ema, long n, float beta1, float beta2, float eps,
                          const float* scalars, float ema_decay, void* stream);
 
-/* ---- layout (the reference is NCHW end to end; trainer.py:55-66) ---------------------------------- */
+/* ---- gradient-norm clipping and non-finite step skip (beyond the reference, whose users put torch.nn.utils.clip_grad_norm_ between
+ * backward() and optimizer.step(); the call site is patchgan_amd's Trainer._adam_step with Trainer.clip_grad_norm set) -----------------
+ * pg_grad_norm: the 2-norm of the n floats of g, the sum of squares accumulated in fp64 (the square of a float is exact there, and
+ * 1e25 * sqrt(k) is a norm, not inf).  Two launches: workgroup b of B = pg_grad_norm_workspace_bytes(n) / 8 sums the 16-byte groups
+ * b*256 + lane, + B*256, ... of g (one fp64 accumulator per lane and component, then lanes, then waves, in a fixed tree; the n % 4 tail
+ * elements go to the first lanes of workgroup 0) into ws[b]; one workgroup then sums ws[0 .. B) in a fixed order and writes `stat`.  No
+ * floating-point atomics, nothing depends on which workgroup finishes first: equal inputs give equal bits.
+ * The status block lives on the device, one per network, 64 bytes, 16-byte aligned; the caller zeroes it once (that also resets the
+ * accumulators) and every call updates it:
+ *   norm     (float)sqrt(sumsq)
+ *   coef     min(1, max_norm / (norm + 1e-6)) formed in double from the fp64 norm, rounded once (torch's clip_grad_norm_); 0 on a skip
+ *   apply    1, or 0 = "skip": sumsq is not finite (a NaN or +-inf anywhere in g)
+ *   steps, clipped (coef < 1), skipped: counts of calls;  max_norm, sum_norm: the largest and the fp64 sum of the FINITE norms
+ *   sumsq    the fp64 sum of squares of this call
+ * max_norm > 0, +inf allowed (coef == 1 exactly: a pure monitor).  PG_EINVAL before any launch, nothing touched: max_norm <= 0 or NaN,
+ * n <= 0, a NULL g, ws or stat, g or stat not 16-byte aligned, ws not 8-byte aligned, ws_bytes < pg_grad_norm_workspace_bytes(n). */
+typedef struct pg_grad_stat {
+    float norm, coef;
+    unsigned apply, reserved;
+    unsigned long long steps, clipped, skipped;
+    double max_norm, sum_norm, sumsq;
+} pg_grad_stat;
+long pg_grad_norm_workspace_bytes(long n);          /* 8 bytes per workgroup of the first launch; 0 for n <= 0 */
+int pg_grad_norm(const float* g, long n, double max_norm, void* ws, long ws_bytes, pg_grad_stat* stat, void* stream);
+/* pg_adam_step / pg_adam_ema_step (ema != NULL) / their _dev forms on g' = g * stat->coef: ONE fp32 product per element, what torch's
+ * grad.mul_(coef) stores; g itself is only read (28 / 36 bytes per parameter, as without clipping).  With stat->apply == 0 the kernel
+ * returns before it loads anything else: p, m, v and ema keep their bits.  With coef == 1 the results are bit-identical to the plain
+ * calls.  `stat` is what pg_grad_norm wrote, stream-ordered before this launch.  ema_decay is read only with ema != NULL. */
+int pg_adam_clip_step(float* p, const float* g, float* m, float* v, float* ema, long n, float lr, float beta1, float beta2, float eps,
+                      float bc1, float sqrt_bc2, float ema_decay, const pg_grad_stat* stat, void* stream);
+int pg_adam_clip_step_dev(float* p, const float* g, float* m, float* v, float* ema, long n, float beta1, float beta2, float eps,
+                          const float* scalars, float ema_decay, const pg_grad_stat* stat, void* stream);
+
+/* ---- layout(the reference is NCHW end to end; trainer.py:55-66) ---------------------------------- */
 int pg_nchw_to_nhwc(const float* src, float* dst, int ld_dst, int N, int C, int H, int W, void* stream);
 int pg_nhwc_to_nchw(const float* src, int ld_src, float* dst, int N, int C, int H, int W, void* stream);
 /* The discriminator's two concatenated inputs in one pass (trainer.py:65-66,96-99: torch.cat((x, y), 1) and torch.cat((x, gen_img), 1)):

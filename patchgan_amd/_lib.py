@@ -135,6 +135,10 @@ SIGNATURES = {
     'pg_adam_step_dev': (_i, [_p, _p, _p, _p, _l, _f, _f, _f, _p, _p]),
     'pg_adam_ema_step': (_i, [_p, _p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _f, _f, _p]),
     'pg_adam_ema_step_dev': (_i, [_p, _p, _p, _p, _p, _l, _f, _f, _f, _p, _f, _p]),
+    'pg_grad_norm_workspace_bytes': (_l, [_l]),
+    'pg_grad_norm': (_i, [_p, _l, _d, _p, _l, _p, _p]),
+    'pg_adam_clip_step': (_i, [_p, _p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _f, _f, _p, _p]),
+    'pg_adam_clip_step_dev': (_i, [_p, _p, _p, _p, _p, _l, _f, _f, _f, _p, _f, _p, _p]),
     'pg_nchw_to_nhwc': (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
     'pg_nhwc_to_nchw': (_i, [_p, _i, _p, _i, _i, _i, _i, _p]),
     'pg_copy_channels': (_i, [_p, _i, _p, _i, _l, _i, _p]),

@@ -27,10 +27,24 @@ __device__ __forceinline__ void ema_one(float& e, float p_new, float c) {
     if constexpr (EMA) e = e + (p_new - e) * c;
 }
 
-template <bool DEV, bool EMA>
+// CLIP: the gradient is scaled by the coefficient pg_grad_norm left in the status block, g' = g * coef as ONE fp32 product (what
+// torch's grad.mul_(coef) stores; g itself is only read), and a block that says "skip" ends the kernel before anything else is loaded:
+// p, m, v and ema keep their bits.  The flag is uniform for the grid.  coef == 1: g * 1.f == g, the results of the plain forms.
+template <bool CLIP>
+__device__ __forceinline__ float clip_one(float g, float coef) {
+    if constexpr (CLIP) return g * coef;
+    return g;
+}
+
+template <bool DEV, bool EMA, bool CLIP = false>
 __global__ void k_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                        long n, float lr_over_bc1, float beta1, float beta2, float eps, float sqrt_bc2, const float* __restrict__ scal,
-                       float* __restrict__ ema, float ema_decay) {
+                       float* __restrict__ ema, float ema_decay, const pg_grad_stat* __restrict__ stat = nullptr) {
+    float coef = 1.f;
+    if constexpr (CLIP) {
+        if (stat->apply == 0u) return;
+        coef = stat->coef;
+    }
     if constexpr (DEV) {
         lr_over_bc1 = scal[0];
         sqrt_bc2 = scal[1];
@@ -43,10 +57,10 @@ __global__ void k_adam(float* __restrict__ p, const float* __restrict__ g, float
         float4 mm = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
         float4 ee = {0.f, 0.f, 0.f, 0.f};
         if constexpr (EMA) ee = reinterpret_cast<float4*>(ema)[i];
-        adam_one(pp.x, gg.x, mm.x, vv.x, lr_over_bc1, beta1, beta2, eps, sqrt_bc2);
-        adam_one(pp.y, gg.y, mm.y, vv.y, lr_over_bc1, beta1, beta2, eps, sqrt_bc2);
-        adam_one(pp.z, gg.z, mm.z, vv.z, lr_over_bc1, beta1, beta2, eps, sqrt_bc2);
-        adam_one(pp.w, gg.w, mm.w, vv.w, lr_over_bc1, beta1, beta2, eps, sqrt_bc2);
+        adam_one(pp.x, clip_one<CLIP>(gg.x, coef), mm.x, vv.x, lr_over_bc1, beta1, beta2, eps, sqrt_bc2);
+        adam_one(pp.y, clip_one<CLIP>(gg.y, coef), mm.y, vv.y, lr_over_bc1, beta1, beta2, eps, sqrt_bc2);
+        adam_one(pp.z, clip_one<CLIP>(gg.z, coef), mm.z, vv.z, lr_over_bc1, beta1, beta2, eps, sqrt_bc2);
+        adam_one(pp.w, clip_one<CLIP>(gg.w, coef), mm.w, vv.w, lr_over_bc1, beta1, beta2, eps, sqrt_bc2);
         ema_one<EMA>(ee.x, pp.x, c);
         ema_one<EMA>(ee.y, pp.y, c);
         ema_one<EMA>(ee.z, pp.z, c);
@@ -57,9 +71,83 @@ __global__ void k_adam(float* __restrict__ p, const float* __restrict__ g, float
         if constexpr (EMA) reinterpret_cast<float4*>(ema)[i] = ee;
     }
     for (long i = (n4 << 2) + blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += stride) {
-        adam_one(p[i], g[i], m[i], v[i], lr_over_bc1, beta1, beta2, eps, sqrt_bc2);
+        adam_one(p[i], clip_one<CLIP>(g[i], coef), m[i], v[i], lr_over_bc1, beta1, beta2, eps, sqrt_bc2);
         if constexpr (EMA) ema_one<EMA>(ema[i], p[i], c);
     }
+}
+
+// ---- global gradient norm (pg_grad_norm) ------------------------------------------------------------------------------------------------
+// The sum of squares of n floats in fp64, in an order that depends on n alone.  k_sumsq_part: workgroup b of B (norm_blocks(n)) takes the
+// 16-byte groups b * 256 + lane + k * B * 256, k = 0, 1, ... -- one fp64 accumulator per component, so four independent chains per lane
+// --, lane t < n % 4 of workgroup 0 adds tail element (n & ~3) + t, the lane's sum is (x + y) + (z + w) (+ tail); the 64 lanes of a wave
+// are folded by halving distances 32 .. 1, the four wave sums are added in order, ws[b] gets the result.  k_sumsq_finish: one workgroup,
+// lane t sums ws[t], ws[t + 256], ... in order, the same fold, and lane 0 writes the status block.  No atomics, no arrival order.
+constexpr int NORM_THREADS = 256;
+constexpr int NORM_MAX_BLOCKS = 2048;          // 8 workgroups per CU; 16 KiB of partials
+
+__device__ __forceinline__ double norm_block_sum(double a) {
+    __shared__ double part[NORM_THREADS / 64];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) a += __shfl_down(a, off, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = a;
+    __syncthreads();
+    return ((part[0] + part[1]) + part[2]) + part[3];          // (read by every lane; lane 0's value is the one used)
+}
+
+__global__ __launch_bounds__(NORM_THREADS) void k_sumsq_part(const float* __restrict__ g, long n, double* __restrict__ ws) {
+    const long n4 = n >> 2;
+    const long stride = (long)gridDim.x * NORM_THREADS;
+    double ax = 0.0, ay = 0.0, az = 0.0, aw = 0.0;
+#pragma unroll 4
+    for (long i = blockIdx.x * (long)NORM_THREADS + threadIdx.x; i < n4; i += stride) {
+        const float4 gg = reinterpret_cast<const float4*>(g)[i];
+        const double x = gg.x, y = gg.y, z = gg.z, w = gg.w;
+        ax += x * x;
+        ay += y * y;
+        az += z * z;
+        aw += w * w;
+    }
+    double a = (ax + ay) + (az + aw);
+    if (blockIdx.x == 0 && (long)threadIdx.x < (n & 3)) {
+        const double t = g[(n4 << 2) + threadIdx.x];
+        a += t * t;
+    }
+    a = norm_block_sum(a);
+    if (threadIdx.x == 0) ws[blockIdx.x] = a;
+}
+
+__global__ __launch_bounds__(NORM_THREADS) void k_sumsq_finish(const double* __restrict__ ws, int nblocks, double max_norm,
+                                                               pg_grad_stat* __restrict__ stat) {
+    double a = 0.0;
+    for (int i = threadIdx.x; i < nblocks; i += NORM_THREADS) a += ws[i];
+    a = norm_block_sum(a);
+    if (threadIdx.x != 0) return;
+    const double norm = sqrt(a);
+    const bool finite = isfinite(a);           // (a NaN or +-inf anywhere in g makes the sum NaN or +inf: 1e38^2 * 2^40 is far from fp64's end)
+    float coef = 0.f;
+    if (finite) {
+        const double c = max_norm / (norm + 1e-6);          // torch.nn.utils.clip_grad_norm_: clamp(max_norm / (total_norm + 1e-6), max=1)
+        coef = (float)(c < 1.0 ? c : 1.0);
+    }
+    stat->norm = (float)norm;
+    stat->coef = coef;
+    stat->apply = finite ? 1u : 0u;
+    stat->sumsq = a;
+    stat->steps += 1ull;
+    if (finite) {
+        if (coef < 1.f) stat->clipped += 1ull;
+        if (norm > stat->max_norm) stat->max_norm = norm;
+        stat->sum_norm += norm;
+    } else {
+        stat->skipped += 1ull;
+    }
+}
+
+int norm_blocks(long n) {
+    long b = ((n >> 2) + NORM_THREADS - 1) / NORM_THREADS;
+    if (b > NORM_MAX_BLOCKS) b = NORM_MAX_BLOCKS;
+    if (b < 1) b = 1;
+    return (int)b;
 }
 
 // dst NHWC (pixel stride ld_dst) <- src NCHW; one thread per PIXEL: the C plane reads of a wave are C coalesced rows (one thread per
@@ -263,6 +351,48 @@ int pg_adam_ema_step_dev(float* p, const float* g, float* m, float* v, float* em
     if (al & 15) return PG_EINVAL;
     hipLaunchKernelGGL((k_adam<true, true>), dim3(blocks_for(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, 0.f, beta1, beta2,
                        eps, 0.f, scalars, ema, ema_decay);
+    return pg_launch_status();
+}
+
+long pg_grad_norm_workspace_bytes(long n) { return n > 0 ? (long)norm_blocks(n) * (long)sizeof(double) : 0; }
+
+int pg_grad_norm(const float* g, long n, double max_norm, void* ws, long ws_bytes, pg_grad_stat* stat, void* stream) {
+    if (!g || !ws || !stat || n <= 0 || !(max_norm > 0.0)) return PG_EINVAL;          // (a NaN fails the comparison)
+    if ((((uintptr_t)g | (uintptr_t)stat) & 15) || ((uintptr_t)ws & 7)) return PG_EINVAL;
+    const int nb = norm_blocks(n);
+    if (ws_bytes < (long)nb * (long)sizeof(double)) return PG_EINVAL;
+    hipLaunchKernelGGL(k_sumsq_part, dim3(nb), dim3(NORM_THREADS), 0, (hipStream_t)stream, g, n, (double*)ws);
+    hipLaunchKernelGGL(k_sumsq_finish, dim3(1), dim3(NORM_THREADS), 0, (hipStream_t)stream, (const double*)ws, nb, max_norm, stat);
+    return pg_launch_status();
+}
+
+int pg_adam_clip_step(float* p, const float* g, float* m, float* v, float* ema, long n, float lr, float beta1, float beta2, float eps,
+                      float bc1, float sqrt_bc2, float ema_decay, const pg_grad_stat* stat, void* stream) {
+    if (!p || !g || !m || !v || !stat || n <= 0 || bc1 <= 0.f || sqrt_bc2 <= 0.f) return PG_EINVAL;
+    if (ema && !(ema_decay >= 0.f && ema_decay < 1.f)) return PG_EINVAL;
+    const uintptr_t al = (uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema | (uintptr_t)stat;
+    if (al & 15) return PG_EINVAL;
+    if (ema)
+        hipLaunchKernelGGL((k_adam<false, true, true>), dim3(blocks_for(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr / bc1,
+                           beta1, beta2, eps, sqrt_bc2, (const float*)nullptr, ema, ema_decay, stat);
+    else
+        hipLaunchKernelGGL((k_adam<false, false, true>), dim3(blocks_for(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr / bc1,
+                           beta1, beta2, eps, sqrt_bc2, (const float*)nullptr, (float*)nullptr, 0.f, stat);
+    return pg_launch_status();
+}
+
+int pg_adam_clip_step_dev(float* p, const float* g, float* m, float* v, float* ema, long n, float beta1, float beta2, float eps,
+                          const float* scalars, float ema_decay, const pg_grad_stat* stat, void* stream) {
+    if (!p || !g || !m || !v || !scalars || !stat || n <= 0) return PG_EINVAL;
+    if (ema && !(ema_decay >= 0.f && ema_decay < 1.f)) return PG_EINVAL;
+    const uintptr_t al = (uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema | (uintptr_t)stat;
+    if (al & 15) return PG_EINVAL;
+    if (ema)
+        hipLaunchKernelGGL((k_adam<true, true, true>), dim3(blocks_for(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, 0.f, beta1,
+                           beta2, eps, 0.f, scalars, ema, ema_decay, stat);
+    else
+        hipLaunchKernelGGL((k_adam<true, false, true>), dim3(blocks_for(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, 0.f, beta1,
+                           beta2, eps, 0.f, scalars, (float*)nullptr, 0.f, stat);
     return pg_launch_status();
 }
 

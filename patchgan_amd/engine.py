@@ -990,6 +990,60 @@ def adam_ema_step_dev(p, g, m, v, ema, scalars, ema_decay, beta1=0.9, beta2=0.99
                                           beta2, eps, scalars.data_ptr(), ema_decay, _stream()), 'pg_adam_ema_step_dev')
 
 
+def check_clip_norm(value):
+    """Trainer.clip_grad_norm as (gen_max_norm, disc_max_norm), each None or a float > 0 (inf allowed: monitor only), or ValueError.
+    `value`: None, one positive number for both networks, or a pair whose members may be None (what pg_grad_norm accepts)."""
+    def one(x):
+        if isinstance(x, bool) or not isinstance(x, (int, float, np.floating, np.integer)):
+            raise ValueError(f"clip_grad_norm must be None, a positive float or a pair of them (members may be None), not {value!r}")
+        x = float(x)
+        if not x > 0.0:          # (a NaN fails the comparison)
+            raise ValueError(f"clip_grad_norm must be None, a positive float or a pair of them (members may be None), not {value!r}")
+        return x
+    if value is None:
+        return None, None
+    if isinstance(value, (tuple, list)):
+        if len(value) != 2:
+            raise ValueError(f"clip_grad_norm must be None, a positive float or a pair of them (members may be None), not {value!r}")
+        return tuple(None if x is None else one(x) for x in value)
+    x = one(value)
+    return x, x
+
+
+# struct pg_grad_stat (include/patchgan_hip.h): one 64-byte status block per network, read on the host as one record
+GRAD_STAT = np.dtype([('norm', '<f4'), ('coef', '<f4'), ('apply', '<u4'), ('reserved', '<u4'), ('steps', '<u8'), ('clipped', '<u8'),
+                      ('skipped', '<u8'), ('max_norm', '<f8'), ('sum_norm', '<f8'), ('sumsq', '<f8')])
+assert GRAD_STAT.itemsize == 64
+
+
+def grad_norm_workspace_bytes(n):
+    return L.load().pg_grad_norm_workspace_bytes(n)
+
+
+def grad_norm(g, max_norm, ws, stat):
+    """The 2-norm of the flat fp32 gradient `g` (fp64 sum of squares, fixed order) and the clipping coefficient for `max_norm` into the
+    device status block `stat` (64 bytes: GRAD_STAT); `ws`: grad_norm_workspace_bytes(g.numel()) bytes.  Two launches on the current
+    stream, no host read."""
+    L.check(L.load().pg_grad_norm(g.data_ptr(), g.numel(), max_norm, ws.data_ptr(), ws.numel() * ws.element_size(), stat.data_ptr(),
+                                  _stream()), 'pg_grad_norm')
+
+
+def adam_clip_step(p, g, m, v, ema, step, lr, stat, ema_decay=None, beta1=0.9, beta2=0.999, eps=1e-8):
+    """adam_step (ema None) / adam_ema_step on g * coef, coef and the skip flag read from the status block grad_norm wrote."""
+    bc1 = 1.0 - beta1 ** step
+    bc2 = 1.0 - beta2 ** step
+    L.check(L.load().pg_adam_clip_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ema.data_ptr() if ema is not None else None,
+                                       p.numel(), lr, beta1, beta2, eps, bc1, math.sqrt(bc2), ema_decay if ema is not None else 0.0,
+                                       stat.data_ptr(), _stream()), 'pg_adam_clip_step')
+
+
+def adam_clip_step_dev(p, g, m, v, ema, scalars, stat, ema_decay=None, beta1=0.9, beta2=0.999, eps=1e-8):
+    """adam_clip_step with lr / bc1 and sqrt(bc2) taken from the device tensor `scalars` (adam_step_dev)."""
+    L.check(L.load().pg_adam_clip_step_dev(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ema.data_ptr() if ema is not None else None,
+                                           p.numel(), beta1, beta2, eps, scalars.data_ptr(), ema_decay if ema is not None else 0.0,
+                                           stat.data_ptr(), _stream()), 'pg_adam_clip_step_dev')
+
+
 def seg_confusion(p, y, threshold, counts):
     """Add the confusion counts of prediction View p against target View y (fp32, the same shape) to `counts`: an int64 device tensor
     of K*K + 1 words, K = 2 for one channel (p >= threshold against y >= 0.5) and the channel count otherwise (first maximum against

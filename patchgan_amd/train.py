@@ -50,10 +50,14 @@ def parse_config(config):
 def apply_train_params(trainer, train_params):
     """The trainer settings of the YAML's train_params: loss_type, seg_alpha and -- optional, absent = off -- ema_decay, the decay of
     the generator's weight average (Trainer.ema_decay; checkpoints then include generator_ema_ep_*.pth), metrics / metric_threshold
-    (Trainer.metrics: per-epoch validation IoU / Dice from counts kept on the device) and save_best ('miou' | 'mdice': best_*.pth)."""
+    (Trainer.metrics: per-epoch validation IoU / Dice from counts kept on the device), save_best ('miou' | 'mdice': best_*.pth) and
+    clip_grad_norm (Trainer.clip_grad_norm: a number for both networks or a two-element list [generator, discriminator] whose members
+    may be null; a non-finite gradient then skips the step)."""
     trainer.loss_type = train_params['loss_type']
     trainer.seg_alpha = train_params['seg_alpha']
     trainer.ema_decay = train_params.get('ema_decay', None)
+    clip = train_params.get('clip_grad_norm', None)
+    trainer.clip_grad_norm = tuple(clip) if isinstance(clip, list) else clip
     trainer.metrics = True if train_params.get('metrics', None) else None
     trainer.metric_threshold = float(train_params.get('metric_threshold', 0.5))
     trainer.save_best = train_params.get('save_best', None)

@@ -174,6 +174,18 @@ class Trainer:
     # the same all-reduced gradient, so the averages agree without a collective.
     ema_decay = None
 
+    # Gradient-norm clipping and non-finite step skip (opt-in, beyond the reference, whose users put torch.nn.utils.clip_grad_norm_
+    # between backward() and optimizer.step()): None = off -- no buffer, the same launches.  A positive float (float('inf') = monitor
+    # only) for both networks, or a pair (gen_max_norm, disc_max_norm) whose members may be None.  In front of a network's Adam launch
+    # -- in every launch mode, on whatever stream that launch is on, under data parallelism after the all-reduce -- pg_grad_norm takes
+    # the 2-norm of its whole flat gradient (fp64, fixed order: the same bits in every mode and on every rank) and leaves
+    # coef = min(1, max_norm / (norm + 1e-6)) in a device status block; pg_adam_clip_step applies g * coef inside the fused Adam pass.
+    # A gradient with a NaN or an inf in it SKIPS the step: weights, moments and the weight average keep their bits.  The host never
+    # reads the device for this, so Adam's step count advances on a skipped step as well: the bias correction of the following steps
+    # is one step ahead (harmless after a few hundred steps), and the running statistics of nn.BatchNorm2d layers, which the FORWARD
+    # pass updates, are not protected.  read_grad_stats() / reset_grad_stats(); train() reads once per epoch into `grad_history`.
+    clip_grad_norm = None
+
     # Segmentation metrics of evaluation passes (opt-in, beyond the reference): None = off -- no launch, no buffer, no key, file or
     # printed line.  True: every batch(train=False) adds ONE launch beside its segmentation loss (engine.seg_confusion: the confusion
     # counts of G(x) against y, integers, accumulated in `seg_counts` on the device; reset_metrics() / read_metrics()), train() records
@@ -255,6 +267,8 @@ class Trainer:
         self.seg_counts = None     # metrics.SegCounts of the evaluation steps since reset_metrics() (created by the first one; `metrics`)
         self.val_history = []      # train() with metrics: one dict per epoch (losses + scores of the validation pass)
         self._best = None          # metrics.BestTracker (save_best)
+        self._clip = None          # clip_grad_norm: (status blocks of G and D: 2 x 64 bytes, G's reduction workspace, D's) on the device
+        self.grad_history = []     # train() with clip_grad_norm: one read_grad_stats() dict per epoch
 
     # -------------------------------------------------------------------------------------- optimizers
     def setup_optimizers(self, gen_lr=1e-3, dsc_lr=1e-3):
@@ -266,6 +280,55 @@ class Trainer:
         self._t_g = self._t_d = 0
         self._graphs, self._kinds = {}, {}        # captured steps update the OLD moment buffers
         self._ema_ensure()
+        if self._clip_ensure():
+            self._clip[0].zero_()
+
+    # -------------------------------------------------------------------------------------- gradient-norm clipping
+    def _clip_now(self):
+        """(gen_max_norm, disc_max_norm) of the next Adam launches, each None (the plain launch) or the validated float."""
+        if self.clip_grad_norm is None:
+            return None, None
+        return E.check_clip_norm(self.clip_grad_norm)
+
+    def _clip_ensure(self):
+        """With clip_grad_norm set: the persistent device buffers (created zeroed, re-created on another device).  -> whether they exist."""
+        if self._clip_now() == (None, None):
+            return self._clip is not None
+        G, D = self.generator, self.discriminator
+        dev = G.flat.device
+        if self._clip is None or self._clip[0].device != dev:
+            self.flush()
+            ws = [torch.zeros(max(E.grad_norm_workspace_bytes(net.flat.numel()) // 8, 1), dtype=torch.float64, device=dev) for net in (G, D)]
+            # (one workspace per network: in a two-stream step Adam(G) and Adam(D) run on different streams at the same time)
+            self._clip = (torch.zeros(2 * E.GRAD_STAT.itemsize // 8, dtype=torch.float64, device=dev), ws[0], ws[1])
+        return True
+
+    def _clip_stat(self, which):
+        k = E.GRAD_STAT.itemsize // 8
+        return self._clip[0][0:k] if which == 'g' else self._clip[0][k:2 * k]
+
+    def read_grad_stats(self):
+        """{'gen': {...}, 'disc': {...}}: norm and coef of the last step, and since reset_grad_stats() / setup_optimizers() the counts
+        `steps`, `clipped` (coef < 1), `skipped` (non-finite gradient: nothing was written), `max_norm` and `mean_norm` over the steps
+        with a finite norm.  Completes a discriminator update in flight, copies 128 bytes and waits for the device."""
+        if self._clip_now() == (None, None) or not self._clip_ensure():
+            raise RuntimeError("read_grad_stats(): Trainer.clip_grad_norm is None (gradient-norm clipping is off)")
+        self.flush()
+        rec = self._clip[0].cpu().numpy().view(E.GRAD_STAT)
+        out = {}
+        for name, r in zip(('gen', 'disc'), rec):
+            finite = int(r['steps']) - int(r['skipped'])
+            out[name] = dict(norm=float(r['norm']), coef=float(r['coef']), steps=int(r['steps']), clipped=int(r['clipped']),
+                             skipped=int(r['skipped']), max_norm=float(r['max_norm']),
+                             mean_norm=float(r['sum_norm']) / finite if finite else float('nan'))
+        return out
+
+    def reset_grad_stats(self):
+        """Clear the accumulators of read_grad_stats()."""
+        if self._clip_now() == (None, None) or not self._clip_ensure():
+            raise RuntimeError("reset_grad_stats(): Trainer.clip_grad_norm is None (gradient-norm clipping is off)")
+        self.flush()
+        self._clip[0].zero_()
 
     # -------------------------------------------------------------------------------------- the generator's weight average
     @property
@@ -424,6 +487,8 @@ class Trainer:
             self.setup_optimizers(self.gen_lr, self.dsc_lr)
         if train and self._ema is not None and self.ema_decay is not None:
             self._ema_ensure()    # (a generator moved / re-tuned since: the average follows)
+        if train and self.clip_grad_norm is not None:
+            self._clip_ensure()   # (set after setup_optimizers(), or the networks moved: never allocated inside a capture)
         self._step += 1
         ex = self._exec
         if ex is None or ex.device != dev:
@@ -724,7 +789,23 @@ class Trainer:
     def _adam_step(self, which):
         net, (m, v) = (self.generator, self._adam[0:2]) if which == 'g' else (self.discriminator, self._adam[2:4])
         decay = self._ema_now() if which == 'g' else None
-        if decay is not None:
+        max_norm = self._clip_now()[0 if which == 'g' else 1]
+        if max_norm is not None:
+            # the norm of the whole flat gradient (two short launches) and Adam on g * coef, both behind the gradient on this stream;
+            # a non-finite norm skips the update on the device -- the host's step count advances regardless
+            self._clip_ensure()
+            stat = self._clip_stat(which)
+            E.grad_norm(net.grad_flat, max_norm, self._clip[1 if which == 'g' else 2], stat)
+            ema = self._ema if decay is not None else None
+            if self._adam_dev is not None:
+                E.adam_clip_step_dev(net.flat, net.grad_flat, m, v, ema, self._adam_dev[0:2] if which == 'g' else self._adam_dev[2:4], stat, decay)
+            elif which == 'g':
+                self._t_g += 1
+                E.adam_clip_step(net.flat, net.grad_flat, m, v, ema, self._t_g, self.gen_lr, stat, decay)
+            else:
+                self._t_d += 1
+                E.adam_clip_step(net.flat, net.grad_flat, m, v, ema, self._t_d, self.dsc_lr, stat, decay)
+        elif decay is not None:
             # the generator's weight average rides in the same kernel (5 reads + 4 writes per element instead of 4 + 3 and a second pass)
             if self._adam_dev is not None:
                 E.adam_ema_step_dev(net.flat, net.grad_flat, m, v, self._ema, self._adam_dev[0:2], decay)
@@ -762,6 +843,12 @@ class Trainer:
         return ts
 
     def _kind_key(self, x, y, u8, dims, train):
+        # (the max-norms are launch arguments of pg_grad_norm, as the decay is one of Adam(G): a captured step holds the values it was
+        #  captured with, a changed value is another kind of step.  Off: the key is the one without the feature)
+        clip = self._clip_now() if train else (None, None)
+        return self._kind_key_base(x, y, u8, dims, train) + ((clip,) if clip != (None, None) else ())
+
+    def _kind_key_base(self, x, y, u8, dims, train):
         G, D = self.generator, self.discriminator
         return (bool(train), u8, dims, self.loss_type, float(self.seg_alpha), float(self.tversky_beta), float(self.tversky_gamma),
                 tuple(self.label_values) if self.label_values is not None else None, G.training, D.training,
@@ -937,7 +1024,8 @@ class Trainer:
     def _graph_ptrs(self):
         G, D = self.generator, self.discriminator
         ema = self._ema if self._ema_now() is not None else None
-        return tuple(t.data_ptr() if t is not None else 0 for t in (G.grad_flat, D.grad_flat) + tuple(self._adam) + (ema,))
+        clip = tuple(self._clip) if (self._clip is not None and self._clip_now() != (None, None)) else (None, None, None)
+        return tuple(t.data_ptr() if t is not None else 0 for t in (G.grad_flat, D.grad_flat) + tuple(self._adam) + clip + (ema,))
 
     def _capture(self, key, x, y, u8, dims, two=False):
         class _StepGraph:
@@ -977,7 +1065,8 @@ class Trainer:
         # buffers whose CONTENT matters outside the graph (gradients, moments) were replaced (_graph_ptrs).
         st.hold = (E.cur_exec(dev).buffers() + list(G.engine.__dict__.get('_upool', {}).values())
                    + list(D.engine.__dict__.get('_upool', {}).values()) + [G.grad_flat, D.grad_flat] + list(self._adam)
-                   + ([self._ema] if self._ema_now() is not None else []))
+                   + ([self._ema] if self._ema_now() is not None else [])
+                   + (list(self._clip) if (self._clip is not None and self._clip_now() != (None, None)) else []))
         st.ptrs = self._graph_ptrs()
         self._graphs[key] = st
         return st
@@ -1047,6 +1136,8 @@ class Trainer:
             train_mean = self._run_epoch(train_data, True, epoch, 'Training: ', dynamic_ncols=True)
             for key in history:
                 history[key].append(train_mean[key])
+            if self._clip_now() != (None, None):
+                self._grad_stats_epoch(epoch)
             # the reference keeps ONE running-mean dict across both loops: a validation pass without batches reports the
             # training means (trainer.py:204-262)
             if self.metrics:
@@ -1070,6 +1161,17 @@ class Trainer:
                 self.save(epoch)
         self.flush()
         return history['gen'], history['disc']
+
+    def _grad_stats_epoch(self, epoch):
+        """After an epoch's training loop with `clip_grad_norm`: the one host read of the status blocks, one printed line, reset."""
+        stats = self.read_grad_stats()
+        self.grad_history.append(dict({'epoch': epoch}, **stats))
+        self.reset_grad_stats()
+        if _dist().rank == 0:
+            def line(s):
+                return (f"mean {s['mean_norm']:.4g}  max {s['max_norm']:.4g}  clipped {s['clipped']}/{s['steps']}"
+                        f"  skipped {s['skipped']}")
+            print(f"Gradient norm -- generator: {line(stats['gen'])}  |  discriminator: {line(stats['disc'])}")
 
     def _validated(self, epoch, val_mean, val_data):
         """After an epoch's validation pass with `metrics`: read its counts (a collective under data parallelism, as is the averaged
