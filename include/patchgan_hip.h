@@ -489,6 +489,23 @@ int pg_loss_value_grad(const double* Spart, int nsplit, double* S_out, const dou
 int pg_seg_confusion_max_c(void);    /* 32 */
 int pg_seg_confusion(const float* p, int ld_p, const float* y, int ld_y, int N, int HW, int C, float threshold,
                      unsigned long long* counts, void* stream);
+/* Per-class prediction histograms: the table every score CURVE is made of (IoU / Dice / precision / recall at every threshold k / bins,
+ * average precision, the threshold to infer with; patchgan_amd's Trainer.metric_bins launches it after pg_seg_confusion on the same
+ * views).  p and y as above; `hist` holds C*2*bins + 1 64-bit words on the device and the call ADDS to them:
+ *   hist[(c*2 + t)*bins + b]  pixels of channel c with label t (one-vs-rest) whose prediction p[c] falls into bin b
+ *   hist[C*2*bins]            ignored pixels
+ *   bin:   b = bins-1 if p >= 1; b = 0 if p <= 0; otherwise b = (int)(p * (float)bins).  bins is a power of two in 16..1024, so the
+ *          product is exact in fp32 and b >= k exactly when p >= k / bins: the sums over b >= k are the counts pg_seg_confusion gives
+ *          at threshold k / bins.
+ *   label: C == 1: t = (y >= 0.5f), nothing is ignored.  C > 1: t = (c == first index of the maximum of y[0..C)), the scan of
+ *          pg_seg_confusion; a pixel whose largest y is <= 0 only adds 1 to the ignored word, every other pixel adds one count per
+ *          channel.
+ * Inputs are finite (NaN: unspecified).  Integer atomics only: the sums do not depend on arrival order.
+ * PG_EINVAL before any launch: NULL p, y or hist; N, HW or C <= 0; C > pg_seg_confusion_max_c(); bins not a power of two in
+ * 16..1024; C * bins > pg_seg_hist_max_words(); ld_p < C; ld_y < C. */
+int pg_seg_hist_max_words(void);     /* 8192: largest C * bins */
+int pg_seg_hist(const float* p, int ld_p, const float* y, int ld_y, int N, int HW, int C, int bins, unsigned long long* hist,
+                void* stream);
 
 /* ---- optimizer (torch.optim.Adam defaults, trainer.py:169-172) -----------------------------------
  * m += (g-m)*(1-b1); v = v*b2 + (1-b2)*g*g; p -= (lr/bc1) * m / (sqrt(v)/sqrt_bc2 + eps)

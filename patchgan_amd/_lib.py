@@ -131,6 +131,8 @@ SIGNATURES = {
     'pg_loss_value_grad': (_i, [_p, _i, _p, _p, _i, _i, _i, _i, _i, _f, _f, _f, _p, _i, _p, _i, _f, _p, _i, _p, _p]),
     'pg_seg_confusion_max_c': (_i, []),
     'pg_seg_confusion': (_i, [_p, _i, _p, _i, _i, _i, _i, _f, _p, _p]),
+    'pg_seg_hist_max_words': (_i, []),
+    'pg_seg_hist': (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _p, _p]),
     'pg_adam_step': (_i, [_p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _f, _p]),
     'pg_adam_step_dev': (_i, [_p, _p, _p, _p, _l, _f, _f, _f, _p, _p]),
     'pg_adam_ema_step': (_i, [_p, _p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _f, _f, _p]),

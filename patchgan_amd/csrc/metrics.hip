@@ -107,9 +107,160 @@ __global__ __launch_bounds__(256) void k_seg_confusion(const float* __restrict__
     }
 }
 
+// ---- per-class prediction histograms (pg_seg_hist): the confusion counts at EVERY threshold k / bins from one pass -----------------
+// Word (c*2 + t)*bins + b counts the pixels of channel c with one-vs-rest label t whose prediction falls into bin b; p * bins is exact
+// in fp32 for a power-of-two bin count, so floor(p * bins) >= k exactly when p >= k / bins.  The per-workgroup table of 32-bit counters
+// is DYNAMIC LDS of 2 * C * bins words (no static LDS beside it: the base stays 16-byte aligned); it moves to the 64-bit global words
+// as k_seg_confusion's does, under the same epoch scheme.
+//
+// Contention: sigmoid / softmax outputs saturate, so most lanes of a wave want bin 0 or bin bins-1 of one (channel, label) pair.  Those
+// adds never reach LDS lane by lane: per channel three ballots (label, first bin, last bin) and four scalar popcounts count the wave's
+// pixels in the four extreme (label, bin) cells, as the binary path of k_seg_confusion counts its four cells.  For one and four
+// channels the counts stay in wave-uniform registers until the epoch ends (one lane then adds them to the table); for any other channel
+// count four lanes add them to the table once per channel and trip.  Only the lanes of the bins in between issue a ds_add of 1 each.
+// (A first version selected a leader lane per counter in vector code, ~60 VALU instructions per channel and pixel where this one
+// has ~15; the time on cfg4's views did not change with it.)
+constexpr int HIST_MIN_BINS = 16, HIST_MAX_BINS = 1024;
+constexpr int HIST_MAX_WORDS = 8192;      // C * bins: 2 * 8192 counters of 4 bytes = 64 KiB of LDS, two workgroups per CU
+constexpr int HIST_FLUSH_BUDGET = 1 << 19;      // workgroups x counters: bounds the 64-bit global atomics of the flush
+
+__device__ __forceinline__ int hist_bin(float x, int bins, float fbins) {
+    int b = x >= 1.f ? bins - 1 : (x <= 0.f ? 0 : (int)(x * fbins));
+    return b < 0 ? 0 : (b > bins - 1 ? bins - 1 : b);      // (NaN is unspecified, but never an index outside the table)
+}
+
+// One channel of one trip, called by whole waves: lanes with `on` count their (label t, bin b) in `tab` (2 * bins words: [t][b]) if the
+// bin lies in between; the wave's pixels in the first / last bin are added to n[0..4): [first bin, label 0], [first, 1], [last, 0], [last, 1].
+__device__ __forceinline__ void hist_add(unsigned int* tab, bool on, bool t, int b, int bins, unsigned int (&n)[4]) {
+    const bool lo = on && b == 0, hi = on && b == bins - 1;
+    const unsigned long long bt = __ballot(t), b0 = __ballot(lo), bl = __ballot(hi);
+    n[0] += (unsigned int)__popcll(b0 & ~bt);
+    n[1] += (unsigned int)__popcll(b0 & bt);
+    n[2] += (unsigned int)__popcll(bl & ~bt);
+    n[3] += (unsigned int)__popcll(bl & bt);
+    if (on && !lo && !hi) atomicAdd(&tab[(t ? bins : 0) + b], 1u);
+}
+
+// The four extreme cells of one channel, from one lane (n wave-uniform).
+__device__ __forceinline__ void hist_add_extremes(unsigned int* tab, int bins, const unsigned int (&n)[4]) {
+    if (n[0]) atomicAdd(&tab[0], n[0]);
+    if (n[1]) atomicAdd(&tab[bins], n[1]);
+    if (n[2]) atomicAdd(&tab[bins - 1], n[2]);
+    if (n[3]) atomicAdd(&tab[2 * bins - 1], n[3]);
+}
+
+// CT as in k_seg_confusion.  hist: C * 2 * bins + 1 words, the last one counts the ignored pixels.
+// Workgroups of 512: the flush costs workgroups x counters global atomics, so a table is shared by many waves, and 256 such workgroups
+// still put 8 waves on every CU.  (Measured on cfg4's views at 256 bins, us: 64 workgroups of 256 with one pixel per trip 129, 128 of
+// 256 with four pixels loaded ahead 57, 256 of 1024 66, 256 of 512 44 -- against 23 for k_seg_confusion on 512 of 256; cfg2's views: 12.0,
+// 11.1, 9.8, 10.0 against 9.8.  EXPERIMENTS.md.)  A workgroup adds at most 512 to a counter per trip: the epoch is 2^21 trips.
+constexpr int HIST_THREADS = 512;
+constexpr long HIST_EPOCH_TRIPS = EPOCH_TRIPS * 256 / HIST_THREADS;      // 2^21 trips x 512 = 2^30 < 2^32
+
+template <int CT>
+__global__ __launch_bounds__(HIST_THREADS) void k_seg_hist(const float* __restrict__ p, int ld_p, const float* __restrict__ y, int ld_y,
+                                                           long npix, int C, int bins, unsigned long long* __restrict__ hist) {
+    extern __shared__ __attribute__((aligned(16))) unsigned int htab[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int Cn = CT ? CT : C;
+    const int words = 2 * Cn * bins;
+    const float fbins = (float)bins;
+    const long stride = (long)gridDim.x * HIST_THREADS;
+    const long trips = (npix + stride - 1) / stride;      // the same for every thread: the ballots below see whole waves
+    const bool vp = CT == 4 && vec_ok(p, ld_p), vy = CT == 4 && vec_ok(y, ld_y);
+    // (the workgroups move their tables out at about the same time: each starts at another word)
+    const int rot = (int)(((long)blockIdx.x * HIST_THREADS) % words);
+    for (long trip0 = 0; trip0 < trips; trip0 += HIST_EPOCH_TRIPS) {
+        const long trip1 = trip0 + HIST_EPOCH_TRIPS < trips ? trip0 + HIST_EPOCH_TRIPS : trips;
+        for (int i = tid; i < words; i += HIST_THREADS) htab[i] = 0u;
+        __syncthreads();
+        unsigned int nign = 0;      // ignored pixels of this wave (a wave-uniform value; at most 64 per trip)
+        unsigned int next[CT ? CT : 1][4] = {};      // CT 1 / 4: this wave's pixels in the extreme cells of every channel (wave-uniform)
+        for (long trip = trip0; trip < trip1; ++trip) {
+            const long pix = trip * stride + (long)blockIdx.x * HIST_THREADS + tid;
+            const bool valid = pix < npix;
+            if (CT == 1) {
+                float pv = 0.f, yv = 0.f;
+                if (valid) {
+                    pv = p[(size_t)pix * ld_p];
+                    yv = y[(size_t)pix * ld_y];
+                }
+                hist_add(htab, valid, yv >= 0.5f, hist_bin(pv, bins, fbins), bins, next[0]);
+            } else if (CT == 4) {
+                f4 pv = {0.f, 0.f, 0.f, 0.f}, yv = {0.f, 0.f, 0.f, 0.f};
+                if (valid) {
+                    const float* pp = p + (size_t)pix * ld_p;
+                    const float* yp = y + (size_t)pix * ld_y;
+                    pv = vp ? *reinterpret_cast<const f4*>(pp) : f4{pp[0], pp[1], pp[2], pp[3]};
+                    yv = vy ? *reinterpret_cast<const f4*>(yp) : f4{yp[0], yp[1], yp[2], yp[3]};
+                }
+                float ymax;
+                const int t = first_max(yv, 4, ymax);
+                const bool keep = valid && ymax > 0.f;
+                nign += (unsigned int)__popcll(__ballot(valid && !keep));
+#pragma unroll
+                for (int c = 0; c < 4; ++c) hist_add(htab + c * 2 * bins, keep, t == c, hist_bin(pv[c], bins, fbins), bins, next[c]);
+            } else {
+                const float* pp = p + (size_t)(valid ? pix : 0) * ld_p;
+                float ymax = 0.f;
+                int t = 0;
+                if (valid) t = first_max(y + (size_t)pix * ld_y, C, ymax);
+                const bool keep = valid && ymax > 0.f;
+                nign += (unsigned int)__popcll(__ballot(valid && !keep));
+                for (int c = 0; c < C; ++c) {
+                    const float x = keep ? pp[c] : 0.f;
+                    unsigned int n[4] = {};
+                    hist_add(htab + c * 2 * bins, keep, t == c, hist_bin(x, bins, fbins), bins, n);
+                    if (lane < 4) {      // lane k adds cell k: [k & 1 ? label 1 : 0][k & 2 ? last bin : first]
+                        const unsigned int v = lane == 0 ? n[0] : (lane == 1 ? n[1] : (lane == 2 ? n[2] : n[3]));
+                        if (v) atomicAdd(&htab[c * 2 * bins + ((lane & 1) ? bins : 0) + ((lane & 2) ? bins - 1 : 0)], v);
+                    }
+                }
+            }
+        }
+        if (CT && lane == 0) {
+#pragma unroll
+            for (int c = 0; c < (CT ? CT : 1); ++c) hist_add_extremes(htab + c * 2 * bins, bins, next[c]);
+        }
+        __syncthreads();
+        for (int j = tid; j < words; j += HIST_THREADS) {
+            int i = j + rot;
+            if (i >= words) i -= words;
+            const unsigned int v = htab[i];
+            if (v) atomicAdd(&hist[i], (unsigned long long)v);
+        }
+        if (lane == 0 && nign) atomicAdd(&hist[words], (unsigned long long)nign);
+        __syncthreads();
+    }
+}
+
 }  // namespace
 
 extern "C" {
+
+int pg_seg_hist_max_words(void) { return HIST_MAX_WORDS; }
+
+int pg_seg_hist(const float* p, int ld_p, const float* y, int ld_y, int N, int HW, int C, int bins, unsigned long long* hist,
+                void* stream) {
+    if (!p || !y || !hist || N <= 0 || HW <= 0 || C <= 0 || C > MAX_C || ld_p < C || ld_y < C) return PG_EINVAL;
+    if (bins < HIST_MIN_BINS || bins > HIST_MAX_BINS || (bins & (bins - 1)) != 0 || C * bins > HIST_MAX_WORDS) return PG_EINVAL;
+    const long npix = (long)N * HW;
+    const int words = 2 * C * bins;
+    // every workgroup ends with up to `words` global atomics: a large table gets fewer workgroups (256 up to 2048 counters, 32 at 16384)
+    long cap = HIST_FLUSH_BUDGET / words;
+    cap = cap > 256 ? 256 : (cap < 32 ? 32 : cap);
+    long b = (npix + HIST_THREADS - 1) / HIST_THREADS;
+    if (b > cap) b = cap;
+    const dim3 grid((int)b), block(HIST_THREADS);
+    const size_t lds = (size_t)words * sizeof(unsigned int);
+    if (C == 1)
+        hipLaunchKernelGGL(k_seg_hist<1>, grid, block, lds, (hipStream_t)stream, p, ld_p, y, ld_y, npix, C, bins, hist);
+    else if (C == 4)
+        hipLaunchKernelGGL(k_seg_hist<4>, grid, block, lds, (hipStream_t)stream, p, ld_p, y, ld_y, npix, C, bins, hist);
+    else
+        hipLaunchKernelGGL(k_seg_hist<0>, grid, block, lds, (hipStream_t)stream, p, ld_p, y, ld_y, npix, C, bins, hist);
+    return pg_launch_status();
+}
 
 int pg_seg_confusion_max_c(void) { return MAX_C; }
 

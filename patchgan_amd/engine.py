@@ -1056,6 +1056,16 @@ def seg_confusion(p, y, threshold, counts):
             'pg_seg_confusion')
 
 
+def seg_hist(p, y, bins, hist):
+    """Add the per-class prediction histograms of View p against target View y (fp32, the same shape) to `hist`: an int64 device tensor
+    of C*2*bins + 1 words, [channel][label][bin] and the ignored pixels in the last word (metrics.SegHist; bins a power of two in
+    16..1024, C * bins <= 8192).  pg_seg_hist, on the current stream; nothing is read back."""
+    assert (p.N, p.H, p.W, p.C) == (y.N, y.H, y.W, y.C) and not p.bf and not y.bf, 'seg_hist takes fp32 views of one shape'
+    bins = int(bins)
+    assert hist.dtype == torch.int64 and hist.numel() == p.C * 2 * bins + 1 and hist.is_contiguous() and hist.device == p.t.device
+    L.check(L.load().pg_seg_hist(p.ptr(), p.ld, y.ptr(), y.ld, p.N, p.HW, p.C, bins, hist.data_ptr(), _stream()), 'pg_seg_hist')
+
+
 TTA_VARIANTS = {None: 1, 'hflip': 2, 'flips': 4, 'd4': 8}
 
 

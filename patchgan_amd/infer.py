@@ -213,6 +213,15 @@ def patchgan_infer(argv=None):
 
     ck = config['checkpoint_paths']
     infer_params = config.get('infer_params', {})
+    threshold = infer_params.get('threshold', 0)
+    if isinstance(threshold, str):
+        # `threshold: best` -- the threshold with the best validation IoU of exactly these weights, as train() stored it in
+        # best_metrics.json beside best_generator*.pth (Trainer.metric_bins); ValueError before anything is written or processed
+        if threshold != 'best':
+            raise ValueError(f"infer_params.threshold must be a number or 'best', not {threshold!r}")
+        from .metrics import best_threshold
+        threshold = best_threshold(ck['generator'], out_channels)
+        print(f"threshold: best = {threshold} (from best_metrics.json beside {os.path.basename(ck['generator'])})")
     output_path = infer_params.get('output_path', 'predictions/')
     if not os.path.exists(output_path):
         os.makedirs(output_path)
@@ -221,8 +230,7 @@ def patchgan_infer(argv=None):
     discriminator.eval()
     generator.load_state_dict(torch.load(ck['generator'], map_location=device))
     discriminator.load_state_dict(torch.load(ck['discriminator'], map_location=device))
-    threshold = infer_params.get('threshold', 0)
-    overlap = infer_params.get('overlap', 0.9)
+    overlap =infer_params.get('overlap', 0.9)
     tta = infer_params.get('tta')                 # absent: no test-time augmentation, uniform blend
     window = infer_params.get('window')           # a name or a list of `size` weights
 

@@ -50,7 +50,8 @@ def parse_config(config):
 def apply_train_params(trainer, train_params):
     """The trainer settings of the YAML's train_params: loss_type, seg_alpha and -- optional, absent = off -- ema_decay, the decay of
     the generator's weight average (Trainer.ema_decay; checkpoints then include generator_ema_ep_*.pth), metrics / metric_threshold
-    (Trainer.metrics: per-epoch validation IoU / Dice from counts kept on the device), save_best ('miou' | 'mdice': best_*.pth) and
+    (Trainer.metrics: per-epoch validation IoU / Dice from counts kept on the device), save_best ('miou' | 'mdice': best_*.pth),
+    metric_bins (Trainer.metric_bins: a power of two in 16..1024 -- score curves, average precision and the best threshold) and
     clip_grad_norm (Trainer.clip_grad_norm: a number for both networks or a two-element list [generator, discriminator] whose members
     may be null; a non-finite gradient then skips the step)."""
     trainer.loss_type = train_params['loss_type']
@@ -61,6 +62,7 @@ def apply_train_params(trainer, train_params):
     trainer.metrics = True if train_params.get('metrics', None) else None
     trainer.metric_threshold = float(train_params.get('metric_threshold', 0.5))
     trainer.save_best = train_params.get('save_best', None)
+    trainer.metric_bins = train_params.get('metric_bins', None)
 
 
 def print_summary(name, module):

@@ -34,7 +34,7 @@ import tqdm
 
 from . import _lib as L
 from . import engine as E
-from .metrics import BestTracker, SegCounts, report
+from .metrics import CURVE_ONLY, BestTracker, SegCounts, SegHist, check_bins, report, report_curve
 from .parallel import current as _dist, GradReducer
 
 device = 'cuda' if torch.cuda.is_available() else 'cpu'
@@ -195,6 +195,14 @@ class Trainer:
     metrics = None
     metric_threshold = 0.5   # one-channel masks: prediction >= this is foreground (several channels: the first maximum, no threshold)
     save_best = None
+    # Score CURVES of evaluation passes (opt-in; needs metrics = True): None = off -- no launch, no buffer, no key, no printed line.  A
+    # power of two in 16..1024: every batch(train=False) adds ONE more launch after its seg_confusion, on the same views
+    # (engine.seg_hist: per channel and label a histogram of the prediction over `metric_bins` bins, integers, accumulated in `seg_hist`).
+    # read_metrics() / evaluate() then also return metrics.curve() of the table -- IoU / Dice / precision / recall at every threshold
+    # k / metric_bins (exactly the counts seg_confusion gives at that threshold), average precision per class, the threshold with the
+    # best IoU -- and the table itself; train() prints mean AP and the best threshold, and best_metrics.json carries best_threshold
+    # (patchgan_infer's `threshold: best`).  save_best still compares epochs at metric_threshold.
+    metric_bins = None
 
     neptune_config = None
     label_values = None      # label list of the dataset, only for the uint8 (device-side) input path of batch()
@@ -265,6 +273,7 @@ class Trainer:
         self._oom_kinds, self.oom_fallbacks = set(), 0      # kinds of step pinned to one stream after an out-of-memory two-stream step
         self._ema = self._ema_net = None      # the generator's weight average: flat fp32 buffer + the UNet that views it (ema_decay)
         self.seg_counts = None     # metrics.SegCounts of the evaluation steps since reset_metrics() (created by the first one; `metrics`)
+        self.seg_hist = None       # metrics.SegHist of the same evaluation steps (created by the first one; `metric_bins`)
         self.val_history = []      # train() with metrics: one dict per epoch (losses + scores of the validation pass)
         self._best = None          # metrics.BestTracker (save_best)
         self._clip = None          # clip_grad_norm: (status blocks of G and D: 2 x 64 bytes, G's reduction workspace, D's) on the device
@@ -383,15 +392,43 @@ class Trainer:
             sc = self.seg_counts = SegCounts(G.engine.output_nc, G.flat.device)
         return sc
 
+    def _metric_bins(self):
+        """Trainer.metric_bins checked: None (off) or the bin count as an int.  ValueError for anything else, and without `metrics`."""
+        if self.metric_bins is None:
+            return None
+        bins = check_bins(self.metric_bins)
+        if bins is None:
+            raise ValueError(f"Trainer.metric_bins = {self.metric_bins!r} must be None or a power of two in 16 .. 1024")
+        if not self.metrics:
+            raise ValueError(f"Trainer.metric_bins = {self.metric_bins!r} needs Trainer.metrics = True (the histograms are built beside the validation counts)")
+        return bins
+
+    def _seg_hist(self, bins):
+        """The histogram table evaluation steps add to, created on first use (as _seg_counts; a changed bin count starts a new one)."""
+        G = self.generator
+        sh = self.seg_hist
+        if sh is None or sh.C != G.engine.output_nc or sh.bins != bins or sh.t.device != G.flat.device:
+            sh = self.seg_hist = SegHist(G.engine.output_nc, bins, G.flat.device)
+        return sh
+
     def reset_metrics(self):
-        """Zero the counts of the evaluation steps (Trainer.metrics); the validation pass of train() starts with it."""
+        """Zero the counts of the evaluation steps (Trainer.metrics) and, with metric_bins, their histograms; the validation pass of
+        train() starts with it."""
         self._seg_counts().zero_()
+        bins = self._metric_bins()
+        if bins is not None:
+            self._seg_hist(bins).zero_()
 
     def read_metrics(self):
         """Scores of the evaluation steps since reset_metrics(): metrics.scores() of their confusion matrix plus `confusion` (np.int64
-        [K, K], [true class][predicted class]) and `ignored`.  Waits for the device; under data parallelism the ranks' counts are
-        summed, which is a collective: every rank calls it."""
-        return report(*self._seg_counts().read(_dist()))
+        [K, K], [true class][predicted class]) and `ignored`; with metric_bins also the keys of metrics.curve() and `hist` (np.int64
+        [C, 2, bins]).  Waits for the device; under data parallelism the ranks' counts are summed, which is a collective: every rank
+        calls it."""
+        out = report(*self._seg_counts().read(_dist()))
+        bins = self._metric_bins()
+        if bins is not None:
+            out.update(report_curve(self._seg_hist(bins).read(_dist())[0]))
+        return out
 
     def evaluate(self, data, generator=None):
         """A generator-only pass over `data` (an iterable of (x, y) batches as batch() takes them): no discriminator, no update.
@@ -399,8 +436,9 @@ class Trainer:
         intended other.  It runs in eval mode (restored afterwards).  Per batch: one generator forward writing into the view an
         evaluation batch() uses (so its head layer runs the same kernel: the pass is bit-comparable to batch(train=False)), the
         segmentation loss by batch()'s own calls, and the confusion counts -- into counts of this call's own, not `seg_counts`.
+        With metric_bins the histograms as well, into a table of this call's own.
         Nothing is read back per batch: the loss values are summed on the device.  Returns {'seg_loss': mean over the batches,
-        **scores, 'confusion', 'ignored'}; under data parallelism every rank passes its shard and gets the global result (collective)."""
+        **scores, 'confusion', 'ignored'} (with metric_bins: + the keys of metrics.curve() and 'hist'); under data parallelism every rank passes its shard and gets the global result (collective)."""
         net = self.generator if generator is None else generator
         G = self.generator
         ge, dev = net.engine, G.flat.device
@@ -409,6 +447,8 @@ class Trainer:
         self.flush()
         dist = _dist()
         counts = SegCounts(ge.output_nc, dev)
+        bins = self._metric_bins()
+        hist = SegHist(ge.output_nc, bins, dev) if bins is not None else None
         total = torch.zeros(1, dtype=torch.float64, device=dev)
         allred = dist.all_reduce_side if dist.on else None
         ex = self._exec
@@ -426,6 +466,8 @@ class Trainer:
                     ge.forward(net.flat, xin, gen, False, 0, sample0=dist.rank * N, bn=net.bn_run())
                     pending = E.loss_begin(gen, yv, 0.0, self.tversky_beta, allred)
                     E.seg_confusion(gen, yv, self.metric_threshold, counts.t)
+                    if hist is not None:
+                        E.seg_hist(gen, yv, bins, hist.t)
                     E.loss_finish(pending, _LOSS_MODES[self.loss_type], float(self.seg_alpha), None, loss, 0, N * dist.world,
                                   self.tversky_gamma)
                     total += loss
@@ -438,6 +480,8 @@ class Trainer:
                 total = total.cpu()
             dist.dist.all_reduce(total, op=dist.dist.ReduceOp.SUM)
         out = report(*counts.read(dist))
+        if hist is not None:
+            out.update(report_curve(hist.read(dist)[0]))
         seg = float(total.cpu()[0]) / nbatches if nbatches else float('nan')
         return dict({'seg_loss': seg}, **out)
 
@@ -481,6 +525,8 @@ class Trainer:
     def batch(self, x, y, train=False):
         t_host0 = time.perf_counter()
         G, D = self.generator, self.discriminator
+        if not train and self.metric_bins is not None:
+            self._metric_bins()   # (an evaluation step: ValueError before anything is launched)
         x, y, u8, N, H, W, Cin, Cout = self._inputs(x, y)
         dev = G.flat.device
         if train and self._adam is None:
@@ -610,6 +656,10 @@ class Trainer:
             # evaluation step: the confusion counts of G(x) against y, one more pass over the bytes the loss reduction just read (on this
             # stream in every launch mode; never in a training step, so a captured step does not hold it)
             E.seg_confusion(gen, yv, self.metric_threshold, self._seg_counts().t)
+            bins = self._metric_bins()
+            if bins is not None:
+                # (the histograms every threshold's counts follow from: one more pass over the same bytes, on this stream as well)
+                E.seg_hist(gen, yv, bins, self._seg_hist(bins).t)
         # D's weights do not change until the Adam step at the end of this call: its Winograd-transformed weights are computed
         # once per (layer, direction) and shared by the passes below through this per-step cache
         ucache = de.ucache_begin(D.flat, N, H, W, tag=bool(train))
@@ -856,7 +906,9 @@ class Trainer:
                 tuple(x.shape), tuple(y.shape), x.dtype, y.dtype, _dist().on,
                 self._ema_now(),          # (the decay is a launch argument of Adam(G): a captured step holds the value it was captured with)
                 # (an evaluation step with the metrics launch is another kind of step than one without: never timed against each other)
-                (float(self.metric_threshold) if self.metrics else None) if not train else None)
+                # (likewise one with the histogram launch of metric_bins)
+                ((float(self.metric_threshold), self.metric_bins) if self.metric_bins is not None else float(self.metric_threshold))
+                if (self.metrics and not train) else None)
 
     def _launch_mode(self, key, train):
         """'eager1' (launch by launch, one stream) | 'eager2' (launch by launch, two streams) | 'graph' (replay) for this step of kind
@@ -1096,6 +1148,7 @@ class Trainer:
                 raise ValueError(f"Trainer.save_best = {self.save_best!r} needs Trainer.metrics = True (the score comes from the validation counts)")
             if self._best is None or self._best.metric != self.save_best:
                 self._best = BestTracker(self.save_best)      # (a resumed run keeps what load_last_checkpoint() read back)
+        self._metric_bins()      # (ValueError for a bin count pg_seg_hist does not take, or one without `metrics`)
         if (lr_decay is not None) and not reduce_on_plateau:
             gen_lr = gen_learning_rate * (lr_decay) ** ((self.start - 1) / (decay_freq))
             dsc_lr = dsc_learning_rate * (lr_decay) ** ((self.start - 1) / (decay_freq))
@@ -1178,15 +1231,22 @@ class Trainer:
         generator's own pass), record and print the scores, and keep the best weights so far (save_best)."""
         live = self.read_metrics()
         entry = dict({'epoch': epoch}, **{k: val_mean[k] for k in StepLosses.KEYS if k in val_mean})
-        entry.update(live)
+        entry.update({k: v for k, v in live.items() if k not in CURVE_ONLY})
         ema = None
         if self.ema_generator is not None:
-            ema = entry['ema'] = self.evaluate(val_data, self.ema_generator)
+            ema = self.evaluate(val_data, self.ema_generator)
+            entry['ema'] = {k: v for k, v in ema.items() if k not in CURVE_ONLY}
         self.val_history.append(entry)
         rank0 = _dist().rank == 0
         if rank0:
             def line(s):
-                return f"mIoU {s['miou']:.4f}  mDice {s['mdice']:.4f}  pixel acc {s['pixel_acc']:.4f}"
+                text = f"mIoU {s['miou']:.4f}  mDice {s['mdice']:.4f}  pixel acc {s['pixel_acc']:.4f}"
+                if 'mean_ap' in s:          # (metric_bins; several channels: the first class that has a best threshold)
+                    ok = np.flatnonzero(~np.isnan(s['best_threshold']))
+                    c = int(ok[0]) if ok.size else 0
+                    text += (f"  mean AP {s['mean_ap']:.4f}  best threshold {s['best_threshold'][c]:.4f}"
+                             + (f" (class {c})" if len(s['best_threshold']) > 1 else "") + f" with IoU {s['best_iou'][c]:.4f}")
+                return text
             print(f"Validation metrics -- {line(live)}" + (f"  |  averaged generator: {line(ema)}" if ema is not None else ""))
         if self.neptune_config is not None:
             self.neptune_config['eval/miou'].append(live['miou'])

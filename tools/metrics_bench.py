@@ -3,10 +3,13 @@
   kernel   pg_seg_confusion against pg_loss_reduce_parts on the same views in the same run: HIP events around 50 back-to-back
            launches, median of 9 windows -- cfg2's views (16 x 256^2, C = 1, a slice of ld = 4) and cfg4's (8 x 512^2, C = 4, a slice
            of ld = 7).  Both read N*HW*2C*4 bytes.
-  pass     an evaluation step at cfg2 with metrics = True against None, alternating blocks of 20 steps; evaluate() per batch
+  hist     pg_seg_hist (256 bins) against pg_seg_confusion on the same views in the same run, alternating windows: cfg2's and cfg4's
+           views, once with uniform random predictions and once with saturated ones (every value 0 or 1)
+  pass     an evaluation step at cfg2 with metrics = True against None, alternating blocks of 20 steps; evaluate() per batch; the
+           same with metric_bins = 256 against None (metrics on in both)
   host     the host-side route for one cfg2 batch: to_nchw().cpu() + the NumPy confusion matrix, against the kernel
 
-    python tools/metrics_bench.py [kernel] [pass] [host]
+    python tools/metrics_bench.py [kernel] [hist] [pass] [host]
 """
 import json
 import os
@@ -72,6 +75,48 @@ def kernel():
     return res
 
 
+def timed_pair(fa, fb, launches=50, windows=9):
+    """timed() of two launches in ALTERNATING windows (a, b, a, b, ...): clock and cache state drift hits both alike."""
+    for _ in range(5):
+        fa()
+        fb()
+    torch.cuda.synchronize()
+    out = ([], [])
+    for _ in range(windows):
+        for fn, dst in ((fa, out[0]), (fb, out[1])):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(launches):
+                fn()
+            b.record()
+            b.synchronize()
+            dst.append(a.elapsed_time(b) * 1e3 / launches)
+    return tuple((statistics.median(v), min(v), max(v)) for v in out)
+
+
+def hist(bins=256):
+    lib = L.load()
+    res = {}
+    for name, (N, H, C, ld, off) in {'cfg2': (16, 256, 1, 4, 3), 'cfg4': (8, 512, 4, 7, 3)}.items():
+        for kind in ('uniform', 'saturated'):
+            p, y = views(N, H, C, ld, off)
+            if kind == 'saturated':
+                p.t.copy_((p.t > 0.5).float())
+            K = 2 if C == 1 else C
+            counts = torch.zeros(K * K + 1, dtype=torch.int64, device=DEV)
+            table = torch.zeros(C * 2 * bins + 1, dtype=torch.int64, device=DEV)
+
+            def conf():
+                L.check(lib.pg_seg_confusion(p.ptr(), p.ld, y.ptr(), y.ld, N, H * H, C, 0.5, counts.data_ptr(), E._stream()), 'pg_seg_confusion')
+
+            def hst():
+                L.check(lib.pg_seg_hist(p.ptr(), p.ld, y.ptr(), y.ld, N, H * H, C, bins, table.data_ptr(), E._stream()), 'pg_seg_hist')
+            th, tc = timed_pair(hst, conf)
+            res[f'{name}_{kind}'] = {'MB': N * H * H * 2 * C * 4 / 1e6, 'bins': bins, 'seg_hist_us': th, 'seg_confusion_us': tc,
+                                     'ratio': th[0] / tc[0]}
+    return res
+
+
 def cfg2_trainer():
     torch.manual_seed(1)
     g = pg.UNet(3, 1, 64, use_dropout=False, activation='leakyrelu', final_act='sigmoid').to(DEV)
@@ -110,6 +155,21 @@ def pass_cost():
         res['eval_step_two_streams' if two else 'eval_step_one_stream'] = {
             'off_ms': [round(v, 4) for v in ms[None]], 'on_ms': [round(v, 4) for v in ms[True]],
             'off_median_ms': statistics.median(ms[None]), 'on_median_ms': statistics.median(ms[True])}
+    t.metrics = True
+    for two in (False, True):          # the histogram launch: metric_bins = 256 against None, the confusion counts on in both
+        t.two_streams = two
+        ms = {None: [], 256: []}
+        for bins in (None, 256):
+            t.metric_bins = bins
+            block(lambda: t.batch(x, y, train=False), 5)
+        for _ in range(5):
+            for bins in (None, 256):
+                t.metric_bins = bins
+                ms[bins].append(block(lambda: t.batch(x, y, train=False)))
+        res['eval_step_bins_two_streams' if two else 'eval_step_bins_one_stream'] = {
+            'off_ms': [round(v, 4) for v in ms[None]], 'on_ms': [round(v, 4) for v in ms[256]],
+            'off_median_ms': statistics.median(ms[None]), 'on_median_ms': statistics.median(ms[256])}
+    t.metric_bins = None
     data = [(x, y)] * 20
     t.evaluate(data[:5])
     ev = []
@@ -155,7 +215,7 @@ def host():
 
 
 if __name__ == '__main__':
-    which = sys.argv[1:] or ['kernel', 'pass', 'host']
-    fns = {'kernel': kernel, 'pass': pass_cost, 'host': host}
+    which = sys.argv[1:] or ['kernel', 'hist', 'pass', 'host']
+    fns = {'kernel': kernel, 'hist': hist, 'pass': pass_cost, 'host': host}
     for w in which:
         print(json.dumps({w: fns[w]()}), flush=True)
