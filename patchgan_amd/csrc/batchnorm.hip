@@ -5,7 +5,7 @@
 // discriminator step's one pass over din[2N], which the reference runs as two calls (trainer.py:97,99): each half is normalised with
 // its own batch statistics, forward and backward.
 //
-// Same structure as InstanceNorm's kernels (norm_act.hip): fp64 partial sums per (sample, pixel chunk, channel) -- from the producing
+// Same structure as InstanceNorm's kernels (norm_act.hip) and the same per-element helpers (norm_elem.h): fp64 partial sums per (sample, pixel chunk, channel) -- from the producing
 // conv's epilogue where it emits them (pg_conv_extras.part), else from a statistics pass -- merged in a fixed order (no floating-point
 // atomics: bit-reproducible), then a vectorised apply pass.  Where InstanceNorm's chunk plan would not split a plane (planes under 512
 // pixels) a call is one kernel (a workgroup owns a group of channels of every segment and walks its pixels three times).
@@ -18,61 +18,15 @@
 #include <stdlib.h>
 #include "patchgan_hip.h"
 #include "pg_common.h"
+#include "norm_elem.h"
 
 namespace {
-
-template <int VEC>
-struct F {
-    float v[VEC];
-};
-
-template <int VEC>
-__device__ __forceinline__ F<VEC> ld(const float* p) {
-    F<VEC> r;
-    if constexpr (VEC == 4) {
-        const float4 f = *reinterpret_cast<const float4*>(p);
-        r.v[0] = f.x; r.v[1] = f.y; r.v[2] = f.z; r.v[3] = f.w;
-    } else {
-        r.v[0] = *p;
-    }
-    return r;
-}
-
-template <int VEC>
-__device__ __forceinline__ void st(float* p, const F<VEC>& r) {
-    if constexpr (VEC == 4) *reinterpret_cast<float4*>(p) = make_float4(r.v[0], r.v[1], r.v[2], r.v[3]);
-    else *p = r.v[0];
-}
-
-__device__ __forceinline__ float bn_act_grad(float z, int act) {
-    switch (act) {
-        case PG_ACT_LEAKY: return z > 0.f ? 1.f : 0.2f;
-        case PG_ACT_RELU: return z > 0.f ? 1.f : 0.f;
-        case PG_ACT_TANH: { float t = tanhf(z); return 1.f - t * t; }
-        case PG_ACT_SIGMOID: { float t = 1.f / (1.f + expf(-z)); return t * (1.f - t); }
-        default: return 1.f;
-    }
-}
-
-// tree-reduce red[k][tid] over the pixel-lane dim (tid = pl*G + cu); result in red[k][cu]
-template <int NK>
-__device__ __forceinline__ void bn_lane_tree(double (*red)[256], int tid, int G) {
-    const int PL = 256 / G;
-    for (int off = PL >> 1; off > 0; off >>= 1) {
-        __syncthreads();
-        if (tid < off * G) {
-#pragma unroll
-            for (int k = 0; k < NK; ++k) red[k][tid] += red[k][tid + off * G];
-        }
-    }
-    __syncthreads();
-}
 
 // the incoming gradient of one element after dropout and the activation: dz = (g1 + g2) * keep/(1-p) * act'(x*scale + shift)
 __device__ __forceinline__ float bn_dz(float g, float x, float scale, float shift, int act, float drop_p, float keep_scale,
                                        uint64_t seed, uint64_t e) {
     if (drop_p > 0.f) g = pg_dropout_keep(seed, e, drop_p) ? g * keep_scale : 0.f;
-    return g * bn_act_grad(__fadd_rn(__fmul_rn(x, scale), shift), act);
+    return g * pg_norm_act_grad(__fadd_rn(__fmul_rn(x, scale), shift), act);
 }
 
 // ---- one kernel per call (planes under 512 pixels): grid (channel groups), the segments one after the other
@@ -94,13 +48,13 @@ __global__ __launch_bounds__(256) void k_bn_fwd_small(const float* __restrict__ 
         for (int k = 0; k < VEC; ++k) acc[k] = 0.0;
         if (on)
             for (int p = pl; p < M; p += PL) {
-                const F<VEC> v = ld<VEC>(y + (p0 + p) * ld_y + c0);
+                const Vec<VEC> v = vload<VEC>(y + (p0 + p) * ld_y + c0);
 #pragma unroll
                 for (int k = 0; k < VEC; ++k) acc[k] += (double)v.v[k];
             }
 #pragma unroll
         for (int k = 0; k < VEC; ++k) red[k][tid] = acc[k];
-        bn_lane_tree<VEC>(red, tid, G);
+        lane_tree<VEC>(red, tid, G);
         double mean[VEC];
 #pragma unroll
         for (int k = 0; k < VEC; ++k) mean[k] = red[k][cu] / (double)M;
@@ -109,7 +63,7 @@ __global__ __launch_bounds__(256) void k_bn_fwd_small(const float* __restrict__ 
         for (int k = 0; k < VEC; ++k) acc[k] = 0.0;
         if (on)
             for (int p = pl; p < M; p += PL) {
-                const F<VEC> v = ld<VEC>(y + (p0 + p) * ld_y + c0);
+                const Vec<VEC> v = vload<VEC>(y + (p0 + p) * ld_y + c0);
 #pragma unroll
                 for (int k = 0; k < VEC; ++k) {
                     const double d = (double)v.v[k] - mean[k];
@@ -118,7 +72,7 @@ __global__ __launch_bounds__(256) void k_bn_fwd_small(const float* __restrict__ 
             }
 #pragma unroll
         for (int k = 0; k < VEC; ++k) red[k][tid] = acc[k];
-        bn_lane_tree<VEC>(red, tid, G);
+        lane_tree<VEC>(red, tid, G);
         float sc[VEC], sh[VEC];
 #pragma unroll
         for (int k = 0; k < VEC; ++k) {
@@ -142,15 +96,15 @@ __global__ __launch_bounds__(256) void k_bn_fwd_small(const float* __restrict__ 
         __syncthreads();
         if (!on) continue;
         for (int p = pl; p < M; p += PL) {
-            const F<VEC> v = ld<VEC>(y + (p0 + p) * ld_y + c0);
-            F<VEC> o;
+            const Vec<VEC> v = vload<VEC>(y + (p0 + p) * ld_y + c0);
+            Vec<VEC> o;
 #pragma unroll
             for (int k = 0; k < VEC; ++k) {
                 float a = pg_act(__fadd_rn(__fmul_rn(v.v[k], sc[k]), sh[k]), act);
                 if (drop_p > 0.f) a = pg_dropout_keep(seed, (uint64_t)(p0 + p) * C + c0 + k, drop_p) ? a * keep_scale : 0.f;
                 o.v[k] = a;
             }
-            st<VEC>(out + (p0 + p) * ld_out + c0, o);
+            vstore<VEC>(out + (p0 + p) * ld_out + c0, o);
         }
     }
 }
@@ -178,11 +132,11 @@ __global__ __launch_bounds__(256) void k_bn_bwd_small(const float* __restrict__ 
             const float* q = coef + ((long)s * C + (on ? c0 + k : 0)) * 4;
             mf[k] = q[0]; rs[k] = q[1]; sc[k] = q[2]; sh[k] = q[3];
         }
-        auto dz_of = [&](long gp, F<VEC>& xh, F<VEC>& dz) {
-            const F<VEC> v = ld<VEC>(y + gp * ld_y + c0);
-            F<VEC> g = ld<VEC>(g1 + gp * ld_g1 + c0);
+        auto dz_of = [&](long gp, Vec<VEC>& xh, Vec<VEC>& dz) {
+            const Vec<VEC> v = vload<VEC>(y + gp * ld_y + c0);
+            Vec<VEC> g = vload<VEC>(g1 + gp * ld_g1 + c0);
             if (g2) {
-                const F<VEC> h = ld<VEC>(g2 + gp * ld_g2 + c0);
+                const Vec<VEC> h = vload<VEC>(g2 + gp * ld_g2 + c0);
 #pragma unroll
                 for (int k = 0; k < VEC; ++k) g.v[k] += h.v[k];
             }
@@ -197,7 +151,7 @@ __global__ __launch_bounds__(256) void k_bn_bwd_small(const float* __restrict__ 
         for (int k = 0; k < VEC; ++k) s1[k] = s2[k] = 0.0;
         if (on)
             for (int p = pl; p < M; p += PL) {
-                F<VEC> xh, dz;
+                Vec<VEC> xh, dz;
                 dz_of(p0 + p, xh, dz);
 #pragma unroll
                 for (int k = 0; k < VEC; ++k) {
@@ -210,7 +164,7 @@ __global__ __launch_bounds__(256) void k_bn_bwd_small(const float* __restrict__ 
             red[k][tid] = s1[k];
             red[VEC + k][tid] = s2[k];
         }
-        bn_lane_tree<2 * VEC>(red, tid, G);
+        lane_tree<2 * VEC>(red, tid, G);
         float cdz[VEC], cx[VEC];
 #pragma unroll
         for (int k = 0; k < VEC; ++k) {
@@ -222,11 +176,11 @@ __global__ __launch_bounds__(256) void k_bn_bwd_small(const float* __restrict__ 
         __syncthreads();
         if (!on) continue;
         for (int p = pl; p < M; p += PL) {
-            F<VEC> xh, dz, o;
+            Vec<VEC> xh, dz, o;
             dz_of(p0 + p, xh, dz);
 #pragma unroll
             for (int k = 0; k < VEC; ++k) o.v[k] = sc[k] * (dz.v[k] - cdz[k] - xh.v[k] * cx[k]);
-            st<VEC>(dy + (p0 + p) * ld_dy + c0, o);
+            vstore<VEC>(dy + (p0 + p) * ld_dy + c0, o);
         }
     }
     if (on && pl == 0 && dw) {
@@ -265,7 +219,7 @@ __global__ __launch_bounds__(256) void k_bn_partial(const float* __restrict__ y,
     double s1[VEC], s2[VEC];
 #pragma unroll
     for (int k = 0; k < VEC; ++k) s1[k] = s2[k] = 0.0;
-    auto accumulate = [&](long gp, const F<VEC>& v, F<VEC> g, const F<VEC>& h) {
+    auto accumulate = [&](long gp, const Vec<VEC>& v, Vec<VEC> g, const Vec<VEC>& h) {
         if (!BWD) {
 #pragma unroll
             for (int k = 0; k < VEC; ++k) {
@@ -290,14 +244,14 @@ __global__ __launch_bounds__(256) void k_bn_partial(const float* __restrict__ y,
         constexpr int UNR = 4;
         int pix = p_begin + pl;
         for (; pix + (UNR - 1) * PL < p_end; pix += UNR * PL) {
-            F<VEC> v[UNR], g[UNR], h[UNR];
+            Vec<VEC> v[UNR], g[UNR], h[UNR];
 #pragma unroll
             for (int u = 0; u < UNR; ++u) {
                 const long gp = nb + pix + u * PL;
-                v[u] = ld<VEC>(y + gp * ld_y + c0);
+                v[u] = vload<VEC>(y + gp * ld_y + c0);
                 if (BWD) {
-                    g[u] = ld<VEC>(g1 + gp * ld_g1 + c0);
-                    if (HG2) h[u] = ld<VEC>(g2 + gp * ld_g2 + c0);
+                    g[u] = vload<VEC>(g1 + gp * ld_g1 + c0);
+                    if (HG2) h[u] = vload<VEC>(g2 + gp * ld_g2 + c0);
                 }
             }
 #pragma unroll
@@ -305,10 +259,10 @@ __global__ __launch_bounds__(256) void k_bn_partial(const float* __restrict__ y,
         }
         for (; pix < p_end; pix += PL) {
             const long gp = nb + pix;
-            F<VEC> v = ld<VEC>(y + gp * ld_y + c0), g, h;
+            Vec<VEC> v = vload<VEC>(y + gp * ld_y + c0), g, h;
             if (BWD) {
-                g = ld<VEC>(g1 + gp * ld_g1 + c0);
-                if (HG2) h = ld<VEC>(g2 + gp * ld_g2 + c0);
+                g = vload<VEC>(g1 + gp * ld_g1 + c0);
+                if (HG2) h = vload<VEC>(g2 + gp * ld_g2 + c0);
             }
             accumulate(gp, v, g, h);
         }
@@ -318,7 +272,7 @@ __global__ __launch_bounds__(256) void k_bn_partial(const float* __restrict__ y,
         red[k][tid] = s1[k];
         red[VEC + k][tid] = s2[k];
     }
-    bn_lane_tree<2 * VEC>(red, tid, G);
+    lane_tree<2 * VEC>(red, tid, G);
     if (on && pl == 0) {
 #pragma unroll
         for (int k = 0; k < VEC; ++k) {
@@ -357,7 +311,7 @@ __global__ __launch_bounds__(256) void k_bn_merge(const double* __restrict__ par
         }
         red[0][tid] = s1;
         red[1][tid] = s2;
-        bn_lane_tree<2>(red, tid, MERGE_CW);
+        lane_tree<2>(red, tid, MERGE_CW);
         if (on && r == 0) {
             const double t1 = red[0][cc], t2 = red[1][cc];
             if (!BWD) {
@@ -425,7 +379,7 @@ __global__ __launch_bounds__(256) void k_bn_mom_small(const float* __restrict__ 
         if (on)
             for (int p = pl; p < M; p += PL) {
                 const long gp = p0 + p;
-                const F<VEC> v = ld<VEC>(y + gp * ld_y + c0);
+                const Vec<VEC> v = vload<VEC>(y + gp * ld_y + c0);
                 if (!BWD) {
 #pragma unroll
                     for (int k = 0; k < VEC; ++k) {
@@ -434,9 +388,9 @@ __global__ __launch_bounds__(256) void k_bn_mom_small(const float* __restrict__ 
                         s2[k] += d * d;
                     }
                 } else {
-                    F<VEC> g = ld<VEC>(g1 + gp * ld_g1 + c0);
+                    Vec<VEC> g = vload<VEC>(g1 + gp * ld_g1 + c0);
                     if (g2) {
-                        const F<VEC> h = ld<VEC>(g2 + gp * ld_g2 + c0);
+                        const Vec<VEC> h = vload<VEC>(g2 + gp * ld_g2 + c0);
 #pragma unroll
                         for (int k = 0; k < VEC; ++k) g.v[k] += h.v[k];
                     }
@@ -453,7 +407,7 @@ __global__ __launch_bounds__(256) void k_bn_mom_small(const float* __restrict__ 
             red[k][tid] = s1[k];
             red[VEC + k][tid] = s2[k];
         }
-        bn_lane_tree<2 * VEC>(red, tid, G);
+        lane_tree<2 * VEC>(red, tid, G);
         if (on && pl == 0) {
 #pragma unroll
             for (int k = 0; k < VEC; ++k) {
@@ -498,7 +452,7 @@ __global__ __launch_bounds__(256) void k_bn_mom_merge(const double* __restrict__
         }
         red[0][tid] = s1;
         red[1][tid] = s2;
-        bn_lane_tree<2>(red, tid, MERGE_CW);
+        lane_tree<2>(red, tid, MERGE_CW);
         if (on && r == 0) {
             mom[((long)s * C + c) * 2 + 0] = red[0][cc];
             mom[((long)s * C + c) * 2 + 1] = red[1][cc];
@@ -576,8 +530,8 @@ __global__ __launch_bounds__(256) void k_bn_apply(const float* __restrict__ y, i
     const int first = fixed ? blockIdx.x * PL + (int)(threadIdx.x / cq) : blockIdx.x * 256 + (int)threadIdx.x;
     const int step = fixed ? gridDim.x * PL : gridDim.x * 256;
     const int limit = fixed ? HW : HW * cq;
-    auto one = [&](long gp, const F<VEC>& v, F<VEC> g, const F<VEC>& h) {
-        F<VEC> o;
+    auto one = [&](long gp, const Vec<VEC>& v, Vec<VEC> g, const Vec<VEC>& h) {
+        Vec<VEC> o;
         if (!BWD) {
 #pragma unroll
             for (int k = 0; k < VEC; ++k) {
@@ -596,20 +550,20 @@ __global__ __launch_bounds__(256) void k_bn_apply(const float* __restrict__ y, i
                 o.v[k] = sc[k] * (dz - b0[k] - (v.v[k] - mf[k]) * rs[k] * b1[k]);
             }
         }
-        st<VEC>(out + gp * ld_out + c0, o);
+        vstore<VEC>(out + gp * ld_out + c0, o);
     };
     int i = first;
     if (fixed) {
         constexpr int UNR = 4;
         for (; i + (UNR - 1) * step < limit; i += UNR * step) {
-            F<VEC> v[UNR], g[UNR], h[UNR];
+            Vec<VEC> v[UNR], g[UNR], h[UNR];
 #pragma unroll
             for (int u = 0; u < UNR; ++u) {
                 const long gp = nb + i + u * step;
-                v[u] = ld<VEC>(y + gp * ld_y + c0);
+                v[u] = vload<VEC>(y + gp * ld_y + c0);
                 if (BWD) {
-                    g[u] = ld<VEC>(g1 + gp * ld_g1 + c0);
-                    if (HG2) h[u] = ld<VEC>(g2 + gp * ld_g2 + c0);
+                    g[u] = vload<VEC>(g1 + gp * ld_g1 + c0);
+                    if (HG2) h[u] = vload<VEC>(g2 + gp * ld_g2 + c0);
                 }
             }
 #pragma unroll
@@ -624,10 +578,10 @@ __global__ __launch_bounds__(256) void k_bn_apply(const float* __restrict__ y, i
             load_coef();
         }
         const long gp = nb + p;
-        F<VEC> v = ld<VEC>(y + gp * ld_y + c0), g, h;
+        Vec<VEC> v = vload<VEC>(y + gp * ld_y + c0), g, h;
         if (BWD) {
-            g = ld<VEC>(g1 + gp * ld_g1 + c0);
-            if (HG2) h = ld<VEC>(g2 + gp * ld_g2 + c0);
+            g = vload<VEC>(g1 + gp * ld_g1 + c0);
+            if (HG2) h = vload<VEC>(g2 + gp * ld_g2 + c0);
         }
         one(gp, v, g, h);
     }

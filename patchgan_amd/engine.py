@@ -506,6 +506,13 @@ class ConvOp:
         same layer (v_pre); 0 when the two calls do not both take the polyphase Winograd path."""
         return self._query(('v',), lambda: L.load().pg_conv_v_bytes(ctypes.byref(self.g), self.algo, self.ws_arg))
 
+    def keep_v(self, want, *views):
+        """The buffer in which big2small keeps its transformed `big` tensor for the weight gradient of the same layer (v_keep, then
+        v_pre), or None: nobody wants it (`want`, KEEP_V), the two calls do not both take the polyphase Winograd path on this geometry
+        (v_bytes) or the views the calls will see are not ones that path takes."""
+        vb = self.v_bytes() if (want and KEEP_V and self._aligned(*views) and self.fits(*views)) else 0
+        return torch.empty(vb, dtype=torch.uint8, device=views[0].t.device) if vb else None
+
     def halves_same(self, whole):
         """big2small of this op (N samples) and of `whole` (the same layer on 2 N samples) do the same arithmetic per sample
         (pg_conv_batch_halves_same: same kernel, no split over K, V kept in both or in neither): two calls of this op on the halves
@@ -733,37 +740,23 @@ def _dt(*views):
     return m
 
 
-def instnorm_act_fwd(y, out, stats, act, drop_p=0.0, seed=0):
+def _pl(v):
+    """(pointer, pixel stride) of an optional View argument: (NULL, 0) for None."""
+    return (v.ptr(), v.ld) if v is not None else (None, 0)
+
+
+def _in_check(y):
     if y.HW <= 1:
         raise ValueError(f"Expected more than 1 spatial element when training, got input size "
                          f"torch.Size([{y.N}, {y.C}, {y.H}, {y.W}])")
+
+
+def instnorm_act_fwd(y, out, stats, act, drop_p=0.0, seed=0):
+    _in_check(y)
     ws = _workspace(int(L.load().pg_instnorm_workspace_bytes(y.N, y.HW, y.C)), y.t.device)
     L.check(L.load().pg_instnorm_act_fwd_t(y.ptr(), y.ld, out.ptr(), out.ld, stats.data_ptr(), y.N, y.HW, y.C, act, 1e-5,
                                            drop_p, seed & _MASK64, ws.data_ptr(), ws.numel(), _stream(), _dt(y, out)),
             'pg_instnorm_act_fwd')
-
-
-def conv_instnorm_act(op, opcode, src, flat, p_off, y, out, stats, act, drop_p=0.0, seed=0, v_keep=None, u_cache=None, u_valid=False):
-    """Conv2d / ConvTranspose2d (no bias) -> InstanceNorm2d -> activation -> dropout (unet.py:19-30,53-67).  Where the conv's
-    kernel can emit the per-sample sums of its output (polyphase Winograd output transform) the InstanceNorm statistics come
-    from those partials and the separate statistics pass over y is skipped; otherwise conv, then pg_instnorm_act_fwd."""
-    conv = op.big2small if opcode == 0 else op.small2big
-    kw = {'v_keep': v_keep} if v_keep is not None else {}
-    if u_cache is not None:
-        kw.update(u_cache=u_cache, u_valid=u_valid)
-    if y.HW <= 1:
-        raise ValueError(f"Expected more than 1 spatial element when training, got input size "
-                         f"torch.Size([{y.N}, {y.C}, {y.H}, {y.W}])")
-    chunks = op.stats_chunks(opcode, src, y) if FUSE_IN_STATS else 0
-    if chunks:
-        part = torch.empty(y.N * chunks * y.C * 2, dtype=torch.float64, device=y.t.device)
-        conv(src, flat, p_off, None, 0, y, part=part, **kw)
-        L.check(L.load().pg_instnorm_act_fwd_parts_t(y.ptr(), y.ld, out.ptr(), out.ld, stats.data_ptr(), part.data_ptr(), chunks, y.N,
-                                                     y.HW, y.C, act, 1e-5, drop_p, seed & _MASK64, _stream(), _dt(y, out)),
-                'pg_instnorm_act_fwd_parts')
-    else:
-        conv(src, flat, p_off, None, 0, y, **kw)
-        instnorm_act_fwd(y, out, stats, act, drop_p, seed)
 
 
 class BNRun:
@@ -781,6 +774,11 @@ class BNRun:
         self.train, self.bufs, self.scratch, self.slot, self.nseg = bool(train), bufs, scratch, slot, nseg if train else 1
         self.dist = dist if (train and dist is not None and dist.on) else None
         assert slot + self.nseg <= BN_SLOTS
+
+    @property
+    def world(self):
+        """Ranks whose samples one segment's statistics are taken over."""
+        return self.dist.world if self.dist is not None else 1
 
 
 def _bn_check(y, nseg, world=1):
@@ -829,10 +827,9 @@ def batchnorm_act_fwd(l, bn, flat, y, out, act, drop_p=0.0, seed=0, part=None, c
         L.check(lib.pg_batchnorm_act_apply(y.ptr(), y.ld, out.ptr(), out.ld, coef.data_ptr(), y.N, y.HW, y.C, 1, act, drop_p,
                                            seed & _MASK64, st), 'pg_batchnorm_act_apply')
         return coef
+    _bn_check(y, bn.nseg, bn.world)
     if bn.dist is not None:
-        _bn_check(y, bn.nseg, bn.dist.world)
         return _bn_sync_fwd(lib, l, bn, flat, y, out, act, drop_p, seed, part, chunks, coef, st)
-    _bn_check(y, bn.nseg)
     bstat = L.ptr(bn.scratch, l.bs_off + bn.slot * y.C * 2)
     if part is not None:
         L.check(lib.pg_batchnorm_stats(None, y.ld, part.data_ptr(), chunks, w, b, coef.data_ptr(), bstat, y.N, y.HW, y.C, bn.nseg,
@@ -846,24 +843,6 @@ def batchnorm_act_fwd(l, bn, flat, y, out, act, drop_p=0.0, seed=0, part=None, c
     return coef
 
 
-def conv_batchnorm_act(op, opcode, src, flat, l, y, out, bn, act, drop_p=0.0, seed=0, v_keep=None, u_cache=None, u_valid=False):
-    """Conv2d / ConvTranspose2d (no bias) -> BatchNorm2d -> activation -> dropout: the InstanceNorm block's schedule
-    (conv_instnorm_act) -- in training mode the batch statistics come from the conv epilogue's partial sums where it emits them."""
-    conv = op.big2small if opcode == 0 else op.small2big
-    kw = {'v_keep': v_keep} if v_keep is not None else {}
-    if u_cache is not None:
-        kw.update(u_cache=u_cache, u_valid=u_valid)
-    if bn.train:
-        _bn_check(y, bn.nseg, bn.dist.world if bn.dist is not None else 1)
-    chunks = op.stats_chunks(opcode, src, y) if (FUSE_IN_STATS and bn.train) else 0
-    if chunks:
-        part = torch.empty(y.N * chunks * y.C * 2, dtype=torch.float64, device=y.t.device)
-        conv(src, flat, l.p_off, None, 0, y, part=part, **kw)
-        return batchnorm_act_fwd(l, bn, flat, y, out, act, drop_p, seed, part=part, chunks=chunks)
-    conv(src, flat, l.p_off, None, 0, y, **kw)
-    return batchnorm_act_fwd(l, bn, flat, y, out, act, drop_p, seed)
-
-
 def batchnorm_act_bwd(l, train, nseg, gflat, g1, g2, y, coef, dy, act, drop_p=0.0, seed=0, dist=None):
     """Backward of batchnorm_act_fwd (train / nseg / dist: those of its pass).  gflat None: no weight / bias gradients (the generator
     step's pass through D); else they are WRITTEN into gflat.  dist (a training-mode pass that normalised with the global batch's
@@ -875,7 +854,7 @@ def batchnorm_act_bwd(l, train, nseg, gflat, g1, g2, y, coef, dy, act, drop_p=0.
     dw, db = (L.ptr(gflat, l.g_off), L.ptr(gflat, l.be_off)) if gflat is not None else (None, None)
     if train and dist is not None:
         st = _stream()
-        g2p, g2l = (g2.ptr(), g2.ld) if g2 is not None else (None, 0)
+        g2p, g2l = _pl(g2)
         mom = torch.empty(nseg * y.C * 2, dtype=torch.float64, device=y.t.device)
         L.check(lib.pg_batchnorm_moments_bwd(g1.ptr(), g1.ld, g2p, g2l, y.ptr(), y.ld, coef.data_ptr(), mom.data_ptr(), dw, db, y.N, y.HW,
                                              y.C, nseg, act, drop_p, seed & _MASK64, ws.data_ptr(), ws.numel(), st),
@@ -886,9 +865,9 @@ def batchnorm_act_bwd(l, train, nseg, gflat, g1, g2, y, coef, dy, act, drop_p=0.
                                            dy.ld, y.N, y.HW, y.C, nseg, act, drop_p, seed & _MASK64, ws.data_ptr(), ws.numel(), st),
                 'pg_batchnorm_bwd_apply')
         return
-    L.check(lib.pg_batchnorm_act_bwd(g1.ptr(), g1.ld, g2.ptr() if g2 is not None else None, g2.ld if g2 is not None else 0,
-                                     y.ptr(), y.ld, coef.data_ptr(), dy.ptr(), dy.ld, dw, db, y.N, y.HW, y.C, nseg, 1 if train else 0,
-                                     act, drop_p, seed & _MASK64, ws.data_ptr(), ws.numel(), _stream()), 'pg_batchnorm_act_bwd')
+    L.check(lib.pg_batchnorm_act_bwd(g1.ptr(), g1.ld, *_pl(g2), y.ptr(), y.ld, coef.data_ptr(), dy.ptr(), dy.ld, dw, db, y.N, y.HW, y.C,
+                                     nseg, 1 if train else 0, act, drop_p, seed & _MASK64, ws.data_ptr(), ws.numel(), _stream()),
+            'pg_batchnorm_act_bwd')
 
 
 def bn_update_running(layers, bufs, counters, scratch, nslots):
@@ -924,16 +903,14 @@ SPLIT_BWD_BIG = _exp_env('PATCHGAN_SPLIT_BWD_BIG') != '0'       # with the secon
 
 def instnorm_act_bwd(g1, g2, y, stats, dy, act, drop_p=0.0, seed=0):
     ws = _workspace(int(L.load().pg_instnorm_workspace_bytes(y.N, y.HW, y.C)), y.t.device)
-    L.check(L.load().pg_instnorm_act_bwd_t(g1.ptr(), g1.ld, g2.ptr() if g2 is not None else None,
-                                           g2.ld if g2 is not None else 0, y.ptr(), y.ld, stats.data_ptr(), dy.ptr(), dy.ld,
+    L.check(L.load().pg_instnorm_act_bwd_t(g1.ptr(), g1.ld, *_pl(g2), y.ptr(), y.ld, stats.data_ptr(), dy.ptr(), dy.ld,
                                            y.N, y.HW, y.C, act, drop_p, seed & _MASK64, ws.data_ptr(), ws.numel(), _stream(),
                                            _dt(g1, g2, y, dy)), 'pg_instnorm_act_bwd')
 
 
 def act_bwd(g1, g2, a, dy, act):
-    L.check(L.load().pg_act_bwd_t(g1.ptr(), g1.ld, g2.ptr() if g2 is not None else None, g2.ld if g2 is not None else 0,
-                                  a.ptr() if a is not None else None, a.ld if a is not None else 0, dy.ptr(), dy.ld,
-                                  dy.npix, dy.C, act, 0.0, 0, _stream(), _dt(g1, g2, a, dy)), 'pg_act_bwd')
+    L.check(L.load().pg_act_bwd_t(g1.ptr(), g1.ld, *_pl(g2), *_pl(a), dy.ptr(), dy.ld, dy.npix, dy.C, act, 0.0, 0, _stream(),
+                                  _dt(g1, g2, a, dy)), 'pg_act_bwd')
 
 
 def softmax_fwd(y, out):
@@ -941,9 +918,8 @@ def softmax_fwd(y, out):
 
 
 def softmax_bwd(g1, g2, out, dy):
-    L.check(L.load().pg_softmax_bwd(g1.ptr(), g1.ld, g2.ptr() if g2 is not None else None,
-                                    g2.ld if g2 is not None else 0, out.ptr(), out.ld, dy.ptr(), dy.ld, dy.npix, dy.C,
-                                    _stream()), 'pg_softmax_bwd')
+    L.check(L.load().pg_softmax_bwd(g1.ptr(), g1.ld, *_pl(g2), out.ptr(), out.ld, dy.ptr(), dy.ld, dy.npix, dy.C, _stream()),
+            'pg_softmax_bwd')
 
 
 def adam_step(p, g, m, v, step, lr, beta1=0.9, beta2=0.999, eps=1e-8):
@@ -1186,6 +1162,90 @@ def _mix_seed(base, *vals):
 
 
 # ------------------------------------------------------------------------------------------------
+# the norm blocks of a pass
+# ------------------------------------------------------------------------------------------------
+
+
+class NormPass:
+    """The norm blocks of ONE pass through a network (InstanceNorm here, BatchNorm below): which normalisation a layer has, where its
+    statistics come from and what its backward needs is decided in this class and nowhere else.  norm_pass() builds it at the top of a
+    forward pass and the context carries it to the backward.  The engines hand a block's tensors over and keep what its forward
+    returns (c.stats[i] / c.statsd[i]) without looking at it: InstanceNorm's [N*C*2] fp32 (mean, rstd), BatchNorm's coefficients.
+    train / seed / sample0: the dropout behind the generator's blocks (GeneratorEngine.forward).  A block's `key` is its place in the
+    dropout stream, (1 encoder | 2 decoder, index); None: a block without dropout (the discriminator's)."""
+    conv_sums = True          # the statistics are the batch's own: take them from the producing conv's epilogue where it emits them
+
+    def __init__(self, train=False, seed=0, sample0=0):
+        self.train, self.seed, self.sample0 = train, seed, sample0
+
+    def _dropout(self, l, key, y):
+        """(probability, seed) of the dropout behind block `key`: the masks are those of the global batch (_shift_seed)."""
+        if key is None:
+            return 0.0, 0
+        return (0.2 if (self.train and l.dropout) else 0.0), _shift_seed(_mix_seed(self.seed, *key), self.sample0 * y.HW * y.C)
+
+    def conv_norm_act(self, op, opcode, src, flat, l, key, y, out, act, v_keep=None, u_cache=None, u_valid=False):
+        """Conv2d / ConvTranspose2d (no bias) -> norm -> activation -> dropout (unet.py:19-30,53-67).  Where the conv's kernel can
+        emit the per-sample sums of its output (polyphase Winograd output transform) the statistics come from those partials and the
+        separate statistics pass over y is skipped.  Returns what backward() needs."""
+        conv = op.big2small if opcode == 0 else op.small2big
+        kw = {'v_keep': v_keep} if v_keep is not None else {}
+        if u_cache is not None:
+            kw.update(u_cache=u_cache, u_valid=u_valid)
+        self._check(y)                # (torch raises from the norm; nothing is launched for a pass it would refuse)
+        chunks = op.stats_chunks(opcode, src, y) if (FUSE_IN_STATS and self.conv_sums) else 0
+        part = torch.empty(y.N * chunks * y.C * 2, dtype=torch.float64, device=y.t.device) if chunks else None
+        conv(src, flat, l.p_off, None, 0, y, part=part, **kw)
+        return self._norm_act(l, flat, y, out, act, *self._dropout(l, key, y), part, chunks)
+
+    def norm_act(self, l, flat, y, out, act):
+        """norm -> activation on a tensor that exists already (disc.py:31-32: Conv -> Tanh -> norm).  Returns what backward() needs."""
+        return self._norm_act(l, flat, y, out, act, 0.0, 0, None, 0)
+
+    def _check(self, y):
+        _in_check(y)
+
+    def _norm_act(self, l, flat, y, out, act, drop_p, seed, part, chunks):
+        stats = torch.empty(y.N * y.C * 2, dtype=torch.float32, device=y.t.device)
+        if part is None:
+            instnorm_act_fwd(y, out, stats, act, drop_p, seed)
+        else:
+            L.check(L.load().pg_instnorm_act_fwd_parts_t(y.ptr(), y.ld, out.ptr(), out.ld, stats.data_ptr(), part.data_ptr(), chunks, y.N,
+                                                         y.HW, y.C, act, 1e-5, drop_p, seed & _MASK64, _stream(), _dt(y, out)),
+                    'pg_instnorm_act_fwd_parts')
+        return stats
+
+    def backward(self, l, gflat, g1, g2, y, saved, dy, act, key=None):
+        """dy = the gradient wrt the block's norm input y from g1 (+ g2) wrt its output; `saved`: what the forward returned.  A norm
+        with parameters WRITES their gradients into gflat (None: not wanted, the generator step's pass through D)."""
+        instnorm_act_bwd(g1, g2, y, saved, dy, act, *self._dropout(l, key, y))
+
+
+class BatchNormPass(NormPass):
+    """NormPass of a BatchNorm network under the pass's BNRun."""
+
+    def __init__(self, bn, **dropout):
+        super().__init__(**dropout)
+        self.bn, self.conv_sums = bn, bn.train
+
+    def _check(self, y):
+        if self.bn.train:
+            _bn_check(y, self.bn.nseg, self.bn.world)
+
+    def _norm_act(self, l, flat, y, out, act, drop_p, seed, part, chunks):
+        return batchnorm_act_fwd(l, self.bn, flat, y, out, act, drop_p, seed, part=part, chunks=chunks)
+
+    def backward(self, l, gflat, g1, g2, y, saved, dy, act, key=None):
+        bn = self.bn
+        batchnorm_act_bwd(l, bn.train, bn.nseg, gflat, g1, g2, y, saved, dy, act, *self._dropout(l, key, y), dist=bn.dist)
+
+
+def norm_pass(bn, **dropout):
+    """The NormPass of a pass called with bn = its BNRun (a BatchNorm network) or None (InstanceNorm)."""
+    return BatchNormPass(bn, **dropout) if bn is not None else NormPass(**dropout)
+
+
+# ------------------------------------------------------------------------------------------------
 # parameter layout
 # ------------------------------------------------------------------------------------------------
 
@@ -1385,6 +1445,23 @@ class _WeightPrep:
 
     MAX_PLANS = 8
 
+    def _init_network(self, layers, norm_kind, algo):
+        """The constructor tail of both engines: parameter / buffer layout of `layers`, norm kind (norm_kind_of's), algorithm, caches."""
+        self.layers = layers
+        self.nparams = assign_offsets(layers)
+        self.has_bn = any(l.bn for l in layers)
+        self.sync_bn = self.has_bn and norm_kind == 'syncbatch'
+        self.nbuf, self.nbn, self.nscratch = assign_buffers(layers)
+        self.algo = DEFAULT_ALGO if algo is None else algo
+        self.act_bf = False          # bf16 activation storage (set_precision('bf16'); only where bf16_storage_ok())
+        self._ops = {}
+        self._sok = {}
+
+    def _storage_ok(self, key, interior_ops):
+        if key not in self._sok:
+            self._sok[key] = _bf16_tensors_ok(interior_ops, self._LD_MULT)
+        return self._sok[key]
+
     def ucache_begin(self, flat, N, H, W, tag=None):
         key = (N, H, W, tag, self.algo, bool(self.act_bf))
         pool = self.__dict__.setdefault('_upool', {})
@@ -1420,27 +1497,12 @@ class GeneratorEngine(_WeightPrep):
     def __init__(self, input_nc, output_nc, nf, activation, final_act, use_dropout, algo=None, norm_kind='instance'):
         self.input_nc, self.output_nc, self.nf = input_nc, output_nc, nf
         self.activation, self.final_act, self.use_dropout = activation, final_act, use_dropout
-        self.sync_bn = norm_kind == 'syncbatch'
-        norm_kind = layer_kind(norm_kind)
-        self.enc, self.dec = unet_layers(input_nc, output_nc, nf, activation, final_act, use_dropout, norm_kind)
-        self.layers = self.enc + self.dec
-        self.nparams = assign_offsets(self.layers)
-        self.has_bn = norm_kind == 'batch'
-        self.nbuf, self.nbn, self.nscratch = assign_buffers(self.layers)
-        self.algo = DEFAULT_ALGO if algo is None else algo
-        self.act_bf = False          # bf16 activation storage (set_precision('bf16'); needs nf % 4 == 0 and nf >= 32)
-        self._ops = {}
+        self.enc, self.dec = unet_layers(input_nc, output_nc, nf, activation, final_act, use_dropout, layer_kind(norm_kind))
+        self._init_network(self.enc + self.dec, norm_kind, algo)
 
     def bf16_storage_ok(self):
         """Every interior tensor feeds / comes from a fast bf16 conv kernel: channel counts multiples of 4 and >= 32."""
         return self.nf % 4 == 0 and self.nf >= 32
-
-    def _storage_ok(self, key, interior_ops):
-        if not hasattr(self, '_sok'):
-            self._sok = {}
-        if key not in self._sok:
-            self._sok[key] = _bf16_tensors_ok(interior_ops, self._LD_MULT)
-        return self._sok[key]
 
     def ops(self, N, H, W):
         """ConvOps for input extent (N, H, W); cached."""
@@ -1487,8 +1549,8 @@ class GeneratorEngine(_WeightPrep):
         enc_ops, dec_ops = self.ops(N, H, W)
         F = [l.a for l in self.enc]
         c = GenContext()
-        c.N, c.H, c.W, c.xin, c.gen_out, c.seed, c.train, c.sample0 = N, H, W, xin, gen_out, seed, train, sample0
-        c.bn_train, c.bn_nseg, c.bn_dist = (bn.train, bn.nseg, bn.dist) if bn is not None else (False, 1, None)
+        c.N, c.H, c.W, c.xin, c.gen_out = N, H, W, xin, gen_out
+        norm = c.norm = norm_pass(bn, train=train, seed=seed, sample0=sample0)
         # cat_i (i = 1..6): input of decoder i = [dec_{i-1} out | enc_{6-i} out]
         # bf16 activation storage: every interior activation (conv outputs, normalised outputs, their gradients) is a bf16 tensor;
         # the image-facing tensors (x, enc0's conv output, the generator output and its gradient) stay fp32 and the InstanceNorm /
@@ -1516,21 +1578,11 @@ class GeneratorEngine(_WeightPrep):
                 out = cat.channels(cat.C - l.a, l.a)
             else:
                 out = c.hidden
-            if not l.bn:
-                stats = torch.empty(N * l.a * 2, dtype=torch.float32, device=dev)
-            drop = 0.2 if (train and l.dropout) else 0.0
-            vb = op.v_bytes() if (keep_v and KEEP_V and ConvOp._aligned(src, y) and ConvOp.fits(src, y)) else 0
-            vk = torch.empty(vb, dtype=torch.uint8, device=dev) if vb else None
+            vk = op.keep_v(keep_v, src, y)
             u, uv = _ucache(ucache, ('e', i), 0, op, dev, src, y, l.p_off)
-            if l.bn:
-                stats = conv_batchnorm_act(op, 0, src, flat, l, y, out, bn, act, drop,
-                                           _shift_seed(_mix_seed(seed, 1, i), sample0 * y.HW * y.C), v_keep=vk, u_cache=u, u_valid=uv)
-            else:
-                conv_instnorm_act(op, 0, src, flat, l.p_off, y, out, stats, act, drop, _shift_seed(_mix_seed(seed, 1, i), sample0 * y.HW * y.C),
-                                  v_keep=vk, u_cache=u, u_valid=uv)
+            c.stats.append(norm.conv_norm_act(op, 0, src, flat, l, (1, i), y, out, act, v_keep=vk, u_cache=u, u_valid=uv))
             c.v.append(vk)
             c.y.append(y)
-            c.stats.append(stats)
             c.enc_out.append(out)
             src = out
         c.yd, c.statsd = [None] * 7, [None] * 7
@@ -1551,16 +1603,8 @@ class GeneratorEngine(_WeightPrep):
             out = cat.channels(0, l.b)
             if l.norm:
                 yd = View.alloc(N, op.Hb, op.Wb, l.b, dev, bf=bf)
-                drop = 0.2 if (train and l.dropout) else 0.0
                 u, uv = _ucache(ucache, ('d', i), 1, op, dev, src, yd, l.p_off)
-                if l.bn:
-                    stats = conv_batchnorm_act(op, 1, src, flat, l, yd, out, bn, act, drop,
-                                               _shift_seed(_mix_seed(seed, 2, i), sample0 * yd.HW * yd.C), u_cache=u, u_valid=uv)
-                else:
-                    stats = torch.empty(N * l.b * 2, dtype=torch.float32, device=dev)
-                    conv_instnorm_act(op, 1, src, flat, l.p_off, yd, out, stats, act, drop,
-                                      _shift_seed(_mix_seed(seed, 2, i), sample0 * yd.HW * yd.C), u_cache=u, u_valid=uv)
-                c.yd[i], c.statsd[i] = yd, stats
+                c.yd[i], c.statsd[i] = yd, norm.conv_norm_act(op, 1, src, flat, l, (2, i), yd, out, act, u_cache=u, u_valid=uv)
             else:
                 op.small2big(src, flat, l.p_off, None, 0, out, act)
             src = cat
@@ -1612,25 +1656,18 @@ class GeneratorEngine(_WeightPrep):
             g = dcat.channels(0, l.b)
             dskip[5 - i] = dcat.channels(l.b, dcat.C - l.b)
             dy = View.alloc(N, op.Hb, op.Wb, l.b, dev, bf=bf)
-            if l.bn:
-                drop = 0.2 if (c.train and l.dropout) else 0.0
-                batchnorm_act_bwd(l, c.bn_train, c.bn_nseg, gflat, g, None, c.yd[i], c.statsd[i], dy, act, drop,
-                                  _shift_seed(_mix_seed(c.seed, 2, i), c.sample0 * dy.HW * dy.C), dist=c.bn_dist)
-            elif l.norm:
-                drop = 0.2 if (c.train and l.dropout) else 0.0
-                instnorm_act_bwd(g, None, c.yd[i], c.statsd[i], dy, act, drop,
-                                 _shift_seed(_mix_seed(c.seed, 2, i), c.sample0 * dy.HW * dy.C))
+            if l.norm:
+                c.norm.backward(l, gflat, g, None, c.yd[i], c.statsd[i], dy, act, key=(2, i))
             else:
                 act_bwd(g, None, c.cat[i + 1].channels(0, l.b), dy, act)
             src = c.hidden if i == 0 else c.cat[i]
             dsrc = View.alloc(N, op.Hs, op.Ws, l.a, dev, bf=bf)
             u, uv = _ucache(ucache, ('d', i), 0, op, dev, dy, dsrc, l.p_off)
             if (u is not None and bf) or (SPLIT_BWD_BIG and cur_exec().allow):      # bf16 tensors: the two halves as two calls, the data gradient on the forward's packed weights
-                vb = op.v_bytes() if (SHARE_DY_V and not bf and KEEP_V and ConvOp._aligned(dy, dsrc, src) and ConvOp.fits(dy, dsrc, src)) else 0
-                if vb:
+                vk = op.keep_v(SHARE_DY_V and not bf, dy, dsrc, src)
+                if vk is not None:
                     # both halves start from the polyphase transform of dy: the data gradient keeps it (v_keep), the weight gradient --
                     # on the second stream, behind this layer's data gradient instead of beside it -- takes it over (v_pre)
-                    vk = torch.empty(vb, dtype=torch.uint8, device=dev)
                     op.big2small(dy, flat, l.p_off, None, 0, dsrc, u_cache=u, u_valid=uv, v_keep=vk)
                     op.wgrad(src, dy, gflat, l.p_off, v_pre=vk)
                 else:
@@ -1646,13 +1683,7 @@ class GeneratorEngine(_WeightPrep):
         for j in range(6, -1, -1):
             l, op = self.enc[j], enc_ops[j]
             dy = View.alloc(N, op.Hs, op.Ws, l.a, dev, bf=bf and (j > 0 or c.seam8))
-            drop = 0.2 if (c.train and l.dropout) else 0.0
-            if l.bn:
-                batchnorm_act_bwd(l, c.bn_train, c.bn_nseg, gflat, g_main, dskip[j] if j < 6 else None, c.y[j], c.stats[j], dy, act, drop,
-                                  _shift_seed(_mix_seed(c.seed, 1, j), c.sample0 * dy.HW * dy.C), dist=c.bn_dist)
-            else:
-                instnorm_act_bwd(g_main, dskip[j] if j < 6 else None, c.y[j], c.stats[j], dy, act, drop,
-                                 _shift_seed(_mix_seed(c.seed, 1, j), c.sample0 * dy.HW * dy.C))
+            c.norm.backward(l, gflat, g_main, dskip[j] if j < 6 else None, c.y[j], c.stats[j], dy, act, key=(1, j))
             src = (c.xin8 if c.seam8 else c.xin) if j == 0 else c.enc_out[j - 1]
             op.wgrad(dy, src, gflat, l.p_off, v_pre=c.v[j] if ConvOp._aligned(dy, src) else None)
             done(l)
@@ -1699,7 +1730,7 @@ class DiscContext:
         assert not self.bf and not any(s is not None for s in self.stats), 'sample views: fp32 contexts without a norm layer'
         c = DiscContext()
         c.N, c.H, c.W = n, self.H, self.W
-        c.bn_train, c.bn_nseg, c.bn_dist, c.bf, c.seam8 = self.bn_train, self.bn_nseg, self.bn_dist, self.bf, self.seam8
+        c.norm, c.bf, c.seam8 = self.norm, self.bf, self.seam8
         c.din = self.din.samples(n0, n)
         c.t, c.a, c.src = ([v.samples(n0, n) for v in vs] for vs in (self.t, self.a, self.src))
         c.stats, c.v = list(self.stats), [None] * len(self.v)
@@ -1712,25 +1743,10 @@ class DiscriminatorEngine(_WeightPrep):
 
     def __init__(self, input_nc, ndf, n_layers, norm, algo=None, norm_kind='instance'):
         self.input_nc, self.ndf, self.n_layers, self.norm = input_nc, ndf, n_layers, norm
-        self.sync_bn = bool(norm) and norm_kind == 'syncbatch'
-        norm_kind = layer_kind(norm_kind)
-        self.layers = disc_layers(input_nc, ndf, n_layers, norm, norm_kind)
-        self.nparams = assign_offsets(self.layers)
-        self.has_bn = bool(norm) and norm_kind == 'batch'
-        self.nbuf, self.nbn, self.nscratch = assign_buffers(self.layers)
-        self.algo = DEFAULT_ALGO if algo is None else algo
-        self.act_bf = False          # bf16 activation storage (set_precision('bf16'); needs ndf % 4 == 0 and ndf >= 32)
-        self._ops = {}
+        self._init_network(disc_layers(input_nc, ndf, n_layers, norm, layer_kind(norm_kind)), norm_kind, algo)
 
     def bf16_storage_ok(self):
         return self.ndf % 4 == 0 and self.ndf >= 32
-
-    def _storage_ok(self, key, interior_ops):
-        if not hasattr(self, '_sok'):
-            self._sok = {}
-        if key not in self._sok:
-            self._sok[key] = _bf16_tensors_ok(interior_ops, self._LD_MULT)
-        return self._sok[key]
 
     def ops(self, N, H, W):
         key = (N, H, W)
@@ -1771,14 +1787,13 @@ class DiscriminatorEngine(_WeightPrep):
         dev = flat.device
         c = DiscContext()
         c.din, c.N, c.H, c.W = din, din.N, din.H, din.W
-        c.bn_train, c.bn_nseg, c.bn_dist, c.bf, c.seam8 = False, 1, None, False, False
+        c.norm, c.bf, c.seam8 = norm_pass(None), False, False
         c.t, c.stats, c.a, c.v, c.src = [], [], [], [], []
         src = din
         for l, op in zip(self.layers, ops):
             c.src.append(src)
             t = View.alloc(din.N, op.Hs, op.Ws, l.a, dev)
-            vb = op.v_bytes() if (keep_v and KEEP_V and ConvOp._aligned(src, t) and ConvOp.fits(src, t)) else 0
-            c.v.append(torch.empty(vb, dtype=torch.uint8, device=dev) if vb else None)
+            c.v.append(op.keep_v(keep_v, src, t))
             c.t.append(t)
             c.stats.append(None)
             c.a.append(t)
@@ -1810,7 +1825,7 @@ class DiscriminatorEngine(_WeightPrep):
         dev = flat.device
         c = DiscContext()
         c.din, c.N, c.H, c.W = din, din.N, din.H, din.W
-        c.bn_train, c.bn_nseg, c.bn_dist = (bn.train, bn.nseg, bn.dist) if bn is not None else (False, 1, None)
+        norm = c.norm = norm_pass(bn)
         c.t, c.stats, c.a, c.v, c.src = [], [], [], [], []
         # bf16 activation storage: the tensors between the first and the last layer are bf16; the input (x | mask), the first
         # layer's conv output (4-channel input: generic kernel) and the 1-channel head stay fp32
@@ -1829,17 +1844,12 @@ class DiscriminatorEngine(_WeightPrep):
             t = View.alloc(din.N, op.Hs, op.Ws, l.a, dev, bf=bf and (0 < li < last or (li == 0 and seam8)))
             bias = flat if l.bias_key is not None else None
             u, uv = _ucache(ucache, li, 0, op, dev, src, t, l.p_off)
-            vb = op.v_bytes() if (keep_v and KEEP_V and ConvOp._aligned(src, t) and ConvOp.fits(src, t)) else 0
-            vk = torch.empty(vb, dtype=torch.uint8, device=dev) if vb else None
+            vk = op.keep_v(keep_v, src, t)
             c.v.append(vk)
             op.big2small(src, flat, l.p_off, bias, l.b_off, t, L.ACT_CODES[l.act], v_keep=vk, u_cache=u, u_valid=uv)   # conv + bias + act fused
-            if l.norm:                                                              # disc.py:31-32: Conv -> Tanh -> IN
+            if l.norm:                                                              # disc.py:31-32: Conv -> Tanh -> norm
                 a = View.alloc(din.N, op.Hs, op.Ws, l.a, dev, bf=bf and li < last)
-                if l.bn:
-                    stats = batchnorm_act_fwd(l, bn, flat, t, a, L.ACT_NONE)
-                else:
-                    stats = torch.empty(din.N * l.a * 2, dtype=torch.float32, device=dev)
-                    instnorm_act_fwd(t, a, stats, L.ACT_NONE)
+                stats = norm.norm_act(l, flat, t, a, L.ACT_NONE)
             else:
                 if bf and li == 0 and not seam8:
                     t = t.converted(True)          # the next layer's kernel reads bf16
@@ -1876,11 +1886,7 @@ class DiscriminatorEngine(_WeightPrep):
             else:
                 if l.norm:
                     dt = View.alloc(c.N, op.Hs, op.Ws, l.a, dev, bf=inner)
-                    if l.bn:
-                        batchnorm_act_bwd(l, c.bn_train, c.bn_nseg, gflat if need_wgrad else None, g, None, c.t[li], c.stats[li], dt,
-                                          L.ACT_NONE, dist=c.bn_dist)
-                    else:
-                        instnorm_act_bwd(g, None, c.t[li], c.stats[li], dt, L.ACT_NONE)
+                    c.norm.backward(l, gflat if need_wgrad else None, g, None, c.t[li], c.stats[li], dt, L.ACT_NONE)
                     g = dt
                 dy = View.alloc(c.N, op.Hs, op.Ws, l.a, dev, bf=inner)
                 act_bwd(g, None, c.t[li], dy, L.ACT_CODES[l.act])
@@ -1953,7 +1959,7 @@ def loss_begin(p, y, tconst, beta=0.75, allreduce=None, need_sums=True):
     st = _stream()
     h = PendingLoss()
     h.buf, h.args, h.wait, h.sums = buf, (p, y, tconst, beta), None, None
-    yp, yl = (y.ptr(), y.ld) if y is not None else (None, 0)
+    yp, yl = _pl(y)
     exchange = allreduce is not None and need_sums
     if not exchange and p.N * p.C <= _fused_loss_max_nc():
         h.nsplit = int(lib.pg_loss_reduce_parts(p.ptr(), p.ld, yp, yl, float(tconst), p.N, p.HW, p.C, buf.S.data_ptr(), st))
@@ -1979,10 +1985,10 @@ def loss_finish(h, mode, alpha, grad_out, loss_out, loss_slot, bglobal, gamma=0.
     if h.wait is not None:
         h.wait()
     st = _stream()
-    yp, yl = (y.ptr(), y.ld) if y is not None else (None, 0)
+    yp, yl = _pl(y)
     sums = h.sums.data_ptr() if h.sums is not None else None
     if p.N * p.C <= _fused_loss_max_nc():
-        gp, gl = (grad_out.ptr(), grad_out.ld) if grad_out is not None else (None, 0)
+        gp, gl = _pl(grad_out)
         L.check(lib.pg_loss_value_grad(buf.S.data_ptr(), max(h.nsplit, 1), None, sums, mode, p.N, p.C, p.HW, bglobal, alpha, beta, gamma,
                                        p.ptr(), p.ld, yp, yl, float(tconst), gp, gl, L.ptr(loss_out, loss_slot), st), 'pg_loss_value_grad')
         return buf
