@@ -287,6 +287,31 @@ int pg_instnorm_act_fwd_parts_t(const void* y, int ld_y, void* out, int ld_out, 
 int pg_instnorm_act_bwd_t(const void* g1, int ld_g1, const void* g2, int ld_g2, const void* y, int ld_y, const float* stats,
                           void* dy, int ld_dy, int N, int HW, int C, int act, float drop_p, uint64_t seed, void* ws,
                           size_t ws_bytes, void* stream, int dt);
+/* Affine InstanceNorm2d (nn.InstanceNorm2d(C, affine=True): a learnable per-channel scale gamma and shift beta, no running
+ * statistics) + activation + dropout.  The plain *_t entry points with gamma, beta (C floats each, 4-byte aligned) after the
+ * tensors; dt masks, `ld`, nullable g2, dropout and stream as there; same plans (single-workgroup under 512 pixels, chunked above),
+ * same statistics (fp64 sums, stats = (mean, rstd)).  Every product and sum below is rounded on its own in fp32:
+ *     forward    a = rstd * gamma,  b = beta - mean * a,  z = y * a + b,  out = keep / (1 - p) * act(z)
+ *     backward   dz = g * keep / (1 - p) * act'(z)        (z: the forward's bits, recomputed from stats, gamma, beta)
+ *                s1 = sum dz,  s2 = sum dz * (y - mean)   (per (n, c), fp64: the plain kernel's sums)
+ *                dy = ((dz - s1 / HW - (y - mean) * s2 * rstd^2 / HW) * rstd) * gamma
+ * With gamma = 1, beta = 0, out and dy are the plain entry points' bit for bit.
+ * Parameter gradients: dgamma, dbeta (C floats each, NULL together: not computed -- the generator step's pass through D) are
+ * WRITTEN, not added to: the backward leaves (s1, s2 * rstd) per (n, c) in fp64 in the first N * C * 16 bytes (rounded up to 256) of
+ * ws, and one more kernel sums them over n in ascending order in fp64:  dbeta[c] = sum_n s1,  dgamma[c] = sum_n s2 * rstd.  No
+ * atomics: equal inputs give equal bits.  ws: pg_instnorm_affine_workspace_bytes (that table + the plain workspace), 16-byte
+ * aligned; REQUIRED (PG_EINVAL) where dgamma is given, otherwise as for the plain entry points. */
+size_t pg_instnorm_affine_workspace_bytes(int N, int HW, int C);
+int pg_instnorm_affine_act_fwd_t(const void* y, int ld_y, void* out, int ld_out, const float* gamma, const float* beta, float* stats,
+                                 int N, int HW, int C, int act, float eps, float drop_p, uint64_t seed, void* ws, size_t ws_bytes,
+                                 void* stream, int dt);
+int pg_instnorm_affine_act_fwd_parts_t(const void* y, int ld_y, void* out, int ld_out, const float* gamma, const float* beta,
+                                       float* stats, const double* part, int chunks, int N, int HW, int C, int act, float eps,
+                                       float drop_p, uint64_t seed, void* stream, int dt);
+int pg_instnorm_affine_act_bwd_t(const void* g1, int ld_g1, const void* g2, int ld_g2, const void* y, int ld_y, const float* gamma,
+                                 const float* beta, const float* stats, void* dy, int ld_dy, float* dgamma, float* dbeta, int N,
+                                 int HW, int C, int act, float drop_p, uint64_t seed, void* ws, size_t ws_bytes, void* stream,
+                                 int dt);
 int pg_act_fwd_t(const void* y, int ld_y, void* out, int ld_out, long npix, int C, int act, float drop_p, uint64_t seed,
                  void* stream, int dt);
 int pg_act_bwd_t(const void* g1, int ld_g1, const void* g2, int ld_g2, const void* a, int ld_a, void* dy, int ld_dy, long npix,

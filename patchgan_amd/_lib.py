@@ -105,6 +105,11 @@ SIGNATURES = {
     'pg_instnorm_act_fwd_t': (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _f, _f, _u64, _p, _sz, _p, _i]),
     'pg_instnorm_act_fwd_parts_t': (_i, [_p, _i, _p, _i, _p, _p, _i, _i, _i, _i, _i, _f, _f, _u64, _p, _i]),
     'pg_instnorm_act_bwd_t': (_i, [_p, _i, _p, _i, _p, _i, _p, _p, _i, _i, _i, _i, _i, _f, _u64, _p, _sz, _p, _i]),
+    'pg_instnorm_affine_workspace_bytes': (_sz, [_i, _i, _i]),
+    'pg_instnorm_affine_act_fwd_t': (_i, [_p, _i, _p, _i, _p, _p, _p, _i, _i, _i, _i, _f, _f, _u64, _p, _sz, _p, _i]),
+    'pg_instnorm_affine_act_fwd_parts_t': (_i, [_p, _i, _p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _u64, _p, _i]),
+    'pg_instnorm_affine_act_bwd_t': (_i, [_p, _i, _p, _i, _p, _i, _p, _p, _p, _p, _i, _p, _p, _i, _i, _i, _i, _f, _u64, _p, _sz, _p,
+                                          _i]),
     'pg_act_fwd_t': (_i, [_p, _i, _p, _i, _l, _i, _i, _f, _u64, _p, _i]),
     'pg_act_bwd_t': (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _l, _i, _i, _f, _u64, _p, _i]),
     'pg_softmax_fwd': (_i, [_p, _i, _p, _i, _l, _i, _p]),

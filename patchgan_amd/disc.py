@@ -35,7 +35,8 @@ class _DiscFn(torch.autograd.Function):
 
 class Discriminator(FlatParamModule, Transferable):
     """Discriminator(input_nc, ndf=64, n_layers=3, norm=False, norm_layer=InstanceNorm2d) -- reference disc.py:8.  norm_layer:
-    nn.InstanceNorm2d, nn.BatchNorm2d or -- for data parallelism: the global batch's statistics -- nn.SyncBatchNorm (their defaults)."""
+    nn.InstanceNorm2d, nn.BatchNorm2d or -- for data parallelism: the global batch's statistics -- nn.SyncBatchNorm (their defaults),
+    or functools.partial(nn.InstanceNorm2d, affine=True) (model.{idx}.weight / .bias of the norm modules)."""
 
     def __init__(self, input_nc, ndf=64, n_layers=3, norm=False, norm_layer=nn.InstanceNorm2d):
         super().__init__()

@@ -17,6 +17,7 @@ Nothing here touches autograd; `patchgan_amd.unet` / `.disc` wrap the engines in
 """
 import ctypes
 import os
+import functools
 import math
 import threading
 
@@ -908,6 +909,33 @@ def instnorm_act_bwd(g1, g2, y, stats, dy, act, drop_p=0.0, seed=0):
                                            _dt(g1, g2, y, dy)), 'pg_instnorm_act_bwd')
 
 
+def instnorm_affine_act_fwd(y, out, stats, flat, g_off, be_off, act, drop_p=0.0, seed=0, part=None, chunks=0):
+    """instnorm_act_fwd with the per-channel scale / shift at g_off / be_off of `flat` (nn.InstanceNorm2d(affine=True)); part / chunks:
+    the statistics come from a conv epilogue's partial sums."""
+    _in_check(y)
+    lib = L.load()
+    w, b = L.ptr(flat, g_off), L.ptr(flat, be_off)
+    if part is not None:
+        L.check(lib.pg_instnorm_affine_act_fwd_parts_t(y.ptr(), y.ld, out.ptr(), out.ld, w, b, stats.data_ptr(), part.data_ptr(), chunks,
+                                                       y.N, y.HW, y.C, act, 1e-5, drop_p, seed & _MASK64, _stream(), _dt(y, out)),
+                'pg_instnorm_affine_act_fwd_parts')
+        return
+    ws = _workspace(int(lib.pg_instnorm_affine_workspace_bytes(y.N, y.HW, y.C)), y.t.device)
+    L.check(lib.pg_instnorm_affine_act_fwd_t(y.ptr(), y.ld, out.ptr(), out.ld, w, b, stats.data_ptr(), y.N, y.HW, y.C, act, 1e-5, drop_p,
+                                             seed & _MASK64, ws.data_ptr(), ws.numel(), _stream(), _dt(y, out)),
+            'pg_instnorm_affine_act_fwd')
+
+
+def instnorm_affine_act_bwd(g1, g2, y, stats, dy, flat, gflat, g_off, be_off, act, drop_p=0.0, seed=0):
+    """Backward of instnorm_affine_act_fwd.  gflat None: no scale / shift gradients; else they are WRITTEN at g_off / be_off of it."""
+    lib = L.load()
+    ws = _workspace(int(lib.pg_instnorm_affine_workspace_bytes(y.N, y.HW, y.C)), y.t.device)
+    dw, db = (L.ptr(gflat, g_off), L.ptr(gflat, be_off)) if gflat is not None else (None, None)
+    L.check(lib.pg_instnorm_affine_act_bwd_t(g1.ptr(), g1.ld, *_pl(g2), y.ptr(), y.ld, L.ptr(flat, g_off), L.ptr(flat, be_off),
+                                             stats.data_ptr(), dy.ptr(), dy.ld, dw, db, y.N, y.HW, y.C, act, drop_p, seed & _MASK64,
+                                             ws.data_ptr(), ws.numel(), _stream(), _dt(g1, g2, y, dy)), 'pg_instnorm_affine_act_bwd')
+
+
 def act_bwd(g1, g2, a, dy, act):
     L.check(L.load().pg_act_bwd_t(g1.ptr(), g1.ld, *_pl(g2), *_pl(a), dy.ptr(), dy.ld, dy.npix, dy.C, act, 0.0, 0, _stream(),
                                   _dt(g1, g2, a, dy)), 'pg_act_bwd')
@@ -1167,8 +1195,9 @@ def _mix_seed(base, *vals):
 
 
 class NormPass:
-    """The norm blocks of ONE pass through a network (InstanceNorm here, BatchNorm below): which normalisation a layer has, where its
-    statistics come from and what its backward needs is decided in this class and nowhere else.  norm_pass() builds it at the top of a
+    """The norm blocks of ONE pass through a network (InstanceNorm, plain or affine per layer -- LayerSpec.in_affine --, here, BatchNorm
+    below): which normalisation a layer has, where its statistics come from and what its backward needs is decided in this class and
+    nowhere else.  norm_pass() builds it at the top of a
     forward pass and the context carries it to the backward.  The engines hand a block's tensors over and keep what its forward
     returns (c.stats[i] / c.statsd[i]) without looking at it: InstanceNorm's [N*C*2] fp32 (mean, rstd), BatchNorm's coefficients.
     train / seed / sample0: the dropout behind the generator's blocks (GeneratorEngine.forward).  A block's `key` is its place in the
@@ -1207,6 +1236,9 @@ class NormPass:
 
     def _norm_act(self, l, flat, y, out, act, drop_p, seed, part, chunks):
         stats = torch.empty(y.N * y.C * 2, dtype=torch.float32, device=y.t.device)
+        if l.in_affine:          # (the backward recomputes the forward's z: it is handed the scale / shift the forward read)
+            instnorm_affine_act_fwd(y, out, stats, flat, l.g_off, l.be_off, act, drop_p, seed, part, chunks)
+            return stats, flat
         if part is None:
             instnorm_act_fwd(y, out, stats, act, drop_p, seed)
         else:
@@ -1218,7 +1250,11 @@ class NormPass:
     def backward(self, l, gflat, g1, g2, y, saved, dy, act, key=None):
         """dy = the gradient wrt the block's norm input y from g1 (+ g2) wrt its output; `saved`: what the forward returned.  A norm
         with parameters WRITES their gradients into gflat (None: not wanted, the generator step's pass through D)."""
-        instnorm_act_bwd(g1, g2, y, saved, dy, act, *self._dropout(l, key, y))
+        if l.in_affine:
+            stats, flat = saved
+            instnorm_affine_act_bwd(g1, g2, y, stats, dy, flat, gflat, l.g_off, l.be_off, act, *self._dropout(l, key, y))
+        else:
+            instnorm_act_bwd(g1, g2, y, saved, dy, act, *self._dropout(l, key, y))
 
 
 class BatchNormPass(NormPass):
@@ -1252,9 +1288,10 @@ def norm_pass(bn, **dropout):
 
 class LayerSpec:
     """One conv layer of a network: state_dict key, torch weight shape [a, b, 4, 4], offsets into the flat buffer.
-    norm: the layer is followed by a norm; norm_kind 'instance' (no parameters) or 'batch' (BatchNorm2d: state_dict prefix
-    norm_key, weight / bias at g_off / be_off of the PARAMETER buffer, running statistics at rm_off / rv_off of the network's
-    BUFFER block, counter bn_idx of its counter tensor, batch statistics at bs_off of its scratch)."""
+    norm: the layer is followed by a norm; norm_kind 'instance' (no parameters), 'instance_affine' (InstanceNorm2d(affine=True):
+    state_dict prefix norm_key, weight / bias at g_off / be_off of the PARAMETER buffer, nothing else) or 'batch' (BatchNorm2d: the
+    same two parameters, and running statistics at rm_off / rv_off of the network's BUFFER block, counter bn_idx of its counter
+    tensor, batch statistics at bs_off of its scratch)."""
     __slots__ = ('key', 'a', 'b', 'stride', 'transposed', 'p_off', 'bias_key', 'b_off', 'act', 'norm', 'dropout', 'norm_kind',
                  'norm_key', 'g_off', 'be_off', 'rm_off', 'rv_off', 'bn_idx', 'bs_off')
 
@@ -1268,6 +1305,15 @@ class LayerSpec:
     @property
     def bn(self):
         return self.norm_kind == 'batch'
+
+    @property
+    def in_affine(self):
+        return self.norm_kind == 'instance_affine'
+
+    @property
+    def norm_params(self):
+        """The norm has a per-channel weight and bias in the parameter buffer."""
+        return self.norm_kind in ('batch', 'instance_affine')
 
     @property
     def cout(self):
@@ -1287,7 +1333,7 @@ def assign_offsets(layers):
         if l.bias_key is not None:
             l.b_off = off
             off += (l.cout + 3) // 4 * 4
-        if l.bn:              # BatchNorm2d weight / bias: parameters like any other (Adam, all-reduce, capture see one buffer)
+        if l.norm_params:     # a norm's weight / bias: parameters like any other (Adam, all-reduce, capture see one buffer)
             l.g_off = off
             off += (l.cout + 3) // 4 * 4
             l.be_off = off
@@ -1295,8 +1341,13 @@ def assign_offsets(layers):
     return off
 
 
+_IN_DEFAULTS = {'eps': 1e-5, 'momentum': 0.1, 'track_running_stats': False}
+
+
 def norm_kind_of(norm_layer, who):
-    """'instance' | 'batch' | 'syncbatch' for a constructor's norm_layer argument; anything else raises NotImplementedError.
+    """'instance' | 'instance_affine' | 'batch' | 'syncbatch' for a constructor's norm_layer argument; anything else raises
+    NotImplementedError.  'instance_affine' is functools.partial(nn.InstanceNorm2d, affine=True): keywords only, the others at
+    torch's defaults (affine=False or absent: 'instance').
     BatchNorm2d and SyncBatchNorm are taken with their defaults only (eps 1e-5, momentum 0.1, affine, tracked running statistics).
     'syncbatch' is 'batch' in every respect (layout, buffers, scratch, kernels) plus "synchronise the batch statistics across ranks
     while the data-parallel path is on" (layer_kind, BNRun.dist)."""
@@ -1306,8 +1357,15 @@ def norm_kind_of(norm_layer, who):
         return 'batch'
     if norm_layer is nn.SyncBatchNorm:
         return 'syncbatch'
+    if isinstance(norm_layer, functools.partial) and norm_layer.func is nn.InstanceNorm2d and not norm_layer.args:
+        kw = dict(norm_layer.keywords)
+        affine = kw.pop('affine', False)
+        if isinstance(affine, bool) and all(k in _IN_DEFAULTS and type(v) is type(_IN_DEFAULTS[k]) and v == _IN_DEFAULTS[k]
+                                            for k, v in kw.items()):
+            return 'instance_affine' if affine else 'instance'
     raise NotImplementedError(f"{who} implements norm_layer=nn.InstanceNorm2d or nn.BatchNorm2d (with their defaults) only -- and "
-                              f"nn.SyncBatchNorm, BatchNorm2d with the global batch's statistics under data parallelism --, "
+                              f"functools.partial(nn.InstanceNorm2d, affine=True), InstanceNorm2d with a learnable scale and shift, "
+                              f"and nn.SyncBatchNorm, BatchNorm2d with the global batch's statistics under data parallelism --, "
                               f"got {norm_layer!r}")
 
 
@@ -1323,7 +1381,7 @@ def param_keys(layers):
         keys.append(l.key)
         if l.bias_key is not None:
             keys.append(l.bias_key)
-        if l.bn:
+        if l.norm_params:
             keys += [l.norm_key + '.weight', l.norm_key + '.bias']
     return keys
 
@@ -1376,7 +1434,7 @@ def torch_views(flat, layers):
         out[l.key] = flat.as_strided((l.a, l.b, 4, 4), (l.b, 1, 4 * ab, ab), l.p_off)
         if l.bias_key is not None:
             out[l.bias_key] = flat.as_strided((l.cout,), (1,), l.b_off)
-        if l.bn:
+        if l.norm_params:
             out[l.norm_key + '.weight'] = flat.as_strided((l.cout,), (1,), l.g_off)
             out[l.norm_key + '.bias'] = flat.as_strided((l.cout,), (1,), l.be_off)
     return out
@@ -1395,7 +1453,7 @@ def default_init_(flat, layers, generator=None):
             if l.bias_key is not None:
                 bb = torch.empty(l.cout).uniform_(-bound, bound, generator=generator)
                 views[l.bias_key].copy_(bb)
-            if l.bn:          # BatchNorm2d.reset_parameters: weight 1, bias 0 (draws nothing from the generator)
+            if l.norm_params:     # reset_parameters of BatchNorm2d / affine InstanceNorm2d: weight 1, bias 0 (draws nothing from the generator)
                 views[l.norm_key + '.weight'].fill_(1.0)
                 views[l.norm_key + '.bias'].zero_()
 
@@ -1406,7 +1464,8 @@ def default_init_(flat, layers, generator=None):
 
 
 def unet_layers(input_nc, output_nc, nf, activation, final_act, use_dropout, norm_kind='instance'):
-    """Layer plan of reference UNet.__init__ (unet.py:84-107).  norm_kind 'batch': nn.BatchNorm2d blocks (DownNorm{i} / UpNorm{i})."""
+    """Layer plan of reference UNet.__init__ (unet.py:84-107).  norm_kind 'batch' / 'instance_affine': norm blocks with parameters
+    (DownNorm{i} / UpNorm{i})."""
     if activation not in ('tanh', 'relu', 'leakyrelu'):
         raise ValueError(f"activation must be one of tanh|relu|leakyrelu, got {activation!r}")
     if final_act not in ('tanh', 'relu', 'leakyrelu', 'sigmoid', 'softmax'):
@@ -1447,7 +1506,7 @@ class _WeightPrep:
 
     def _init_network(self, layers, norm_kind, algo):
         """The constructor tail of both engines: parameter / buffer layout of `layers`, norm kind (norm_kind_of's), algorithm, caches."""
-        self.layers = layers
+        self.layers, self.norm_kind = layers, norm_kind
         self.nparams = assign_offsets(layers)
         self.has_bn = any(l.bn for l in layers)
         self.sync_bn = self.has_bn and norm_kind == 'syncbatch'
@@ -1617,8 +1676,8 @@ class GeneratorEngine(_WeightPrep):
         start all-reducing finished buckets under the rest of the backward pass."""
         def done(l):
             if on_ready is not None:
-                # (a BatchNorm layer's weight / bias gradients follow its conv block in the flat buffer and are written before it)
-                on_ready(l.p_off, l.be_off + (l.cout + 3) // 4 * 4 if l.bn else l.p_off + 16 * l.a * l.b)
+                # (a norm's weight / bias gradients follow its conv block in the flat buffer and are written before it)
+                on_ready(l.p_off, l.be_off + (l.cout + 3) // 4 * 4 if l.norm_params else l.p_off + 16 * l.a * l.b)
         # defer_join: the caller joins the second stream itself (side_join()) before it reads the weight gradients -- the trainer puts
         # the discriminator's forward pass, which needs none of them, in between
         _side_begin(not self.act_bf or BF16_WGRAD_SIDE)       # (bf16: the two chains contend for the L1 path: 5.87 -> 5.94 ms at cfg4)

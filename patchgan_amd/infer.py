@@ -197,18 +197,13 @@ def patchgan_infer(argv=None):
         f"Dataset class {Dataset.__name__} must have the save_mask method to save a mask cube for a given filename"
     datagen = Dataset(dataset_path, **dataset_kwargs)
 
-    mp = config['model_params']
-    if 'generator' in mp:
-        gen_filts, activation = mp['generator']['filters'], mp['generator']['activation']
-        final_activation = mp['generator'].get('final_activation', 'sigmoid')
-        disc_filts, n_disc_layers = mp['discriminator']['filters'], mp['discriminator']['n_layers']
-    else:
-        gen_filts, disc_filts, n_disc_layers = mp['gen_filts'], mp['disc_filts'], mp['n_disc_layers']
-        activation, final_activation = mp['activation'], mp.get('final_activation', 'sigmoid')
-    generator = UNet(in_channels, out_channels, gen_filts, activation=activation, final_act=final_activation).to(device)
-    discriminator = Discriminator(in_channels + out_channels, disc_filts, n_layers=n_disc_layers).to(device)
+    from .train import model_cfgs, norm_layer_of, print_summary
+    gen_cfg, disc_cfg = model_cfgs(config['model_params'])      # (the norm layers the checkpoints were trained with: train.NORM_LAYERS)
+    generator = UNet(in_channels, out_channels, gen_cfg['filters'], activation=gen_cfg['activation'],
+                     final_act=gen_cfg.get('final_activation', 'sigmoid'), norm_layer=norm_layer_of(gen_cfg.get('norm_layer'))).to(device)
+    discriminator = Discriminator(in_channels + out_channels, disc_cfg['filters'], n_layers=disc_cfg['n_layers'],
+                                  norm=disc_cfg.get('norm', False), norm_layer=norm_layer_of(disc_cfg.get('norm_layer'))).to(device)
     if args.summary:
-        from .train import print_summary
         print_summary('generator', generator)
 
     ck = config['checkpoint_paths']

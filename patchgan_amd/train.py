@@ -6,21 +6,56 @@ or ``dataset.{data,train_val_split}``, nested ``model_params.{generator,discrimi
 ``examples/train_coco.yaml`` and infer.py still use (top-level ``train_data`` / ``validation_data``,
 ``model_params.{gen_filts,disc_filts,n_disc_layers,activation,use_dropout,final_activation}``).
 
+Extension: ``model_params.generator.norm_layer`` / ``model_params.discriminator.norm_layer`` (flat schema: ``gen_norm_layer`` /
+``disc_norm_layer``) name the networks' norm layer: ``instance`` (the default), ``instance_affine``, ``batch`` or ``sync_batch``
+(NORM_LAYERS); ``patchgan_infer`` reads the same keys to build the network a checkpoint was trained with.
+
 Multi-GPU: launch with ``python -m torch.distributed.run --nproc-per-node N -m patchgan_amd.train ...``; each rank
 takes a distinct shard of every epoch (DistributedSampler) and gradients are all-reduced over RCCL.
 """
 import argparse
+import functools
 import os
 
 import numpy as np
 import torch
 import yaml
+from torch import nn
 from torch.utils.data import DataLoader, random_split
 
 from .disc import Discriminator
 from .io import COCOStuffDataset, load_plugin_dataset
 from .trainer import Trainer
 from .unet import UNet
+
+
+NORM_LAYERS = {'instance': nn.InstanceNorm2d, 'instance_affine': functools.partial(nn.InstanceNorm2d, affine=True),
+               'batch': nn.BatchNorm2d, 'sync_batch': nn.SyncBatchNorm}
+
+
+def norm_layer_of(name='instance'):
+    """The norm_layer constructor argument a YAML norm-layer value names (None, the key absent: 'instance'); ValueError otherwise."""
+    name = 'instance' if name is None else name
+    if not isinstance(name, str) or name not in NORM_LAYERS:
+        raise ValueError(f"norm_layer must be one of {' | '.join(NORM_LAYERS)}, not {name!r}")
+    return NORM_LAYERS[name]
+
+
+def model_cfgs(mp):
+    """(generator_cfg, disc_cfg) of either schema's model_params; a 'norm_layer' name, where one is given, is checked (norm_layer_of:
+    ValueError before any network is built) and an absent one stays absent."""
+    if 'generator' in mp:
+        gen_cfg, disc_cfg = dict(mp['generator']), dict(mp['discriminator'])
+    else:                                                                         # flat legacy schema (infer.py:127-132)
+        gen_cfg = {'filters': mp['gen_filts'], 'activation': mp['activation'],
+                   'use_dropout': mp.get('use_dropout', True), 'final_activation': mp.get('final_activation', 'sigmoid')}
+        disc_cfg = {'filters': mp['disc_filts'], 'n_layers': mp['n_disc_layers'], 'norm': mp.get('disc_norm', False)}
+        for cfg, key in ((gen_cfg, 'gen_norm_layer'), (disc_cfg, 'disc_norm_layer')):
+            if key in mp:
+                cfg['norm_layer'] = mp[key]
+    for cfg in (gen_cfg, disc_cfg):
+        norm_layer_of(cfg.get('norm_layer'))
+    return gen_cfg, disc_cfg
 
 
 def parse_config(config):
@@ -37,13 +72,7 @@ def parse_config(config):
         raise AttributeError("Please provide either the training and validation data paths or a train/val split!")
     if 'labels' not in dataset_params and isinstance(train_paths, dict) and 'labels' in train_paths:
         dataset_params['labels'] = train_paths['labels']                          # legacy: labels next to the paths
-    mp = config['model_params']
-    if 'generator' in mp:
-        gen_cfg, disc_cfg = dict(mp['generator']), dict(mp['discriminator'])
-    else:                                                                         # flat legacy schema (infer.py:127-132)
-        gen_cfg = {'filters': mp['gen_filts'], 'activation': mp['activation'],
-                   'use_dropout': mp.get('use_dropout', True), 'final_activation': mp.get('final_activation', 'sigmoid')}
-        disc_cfg = {'filters': mp['disc_filts'], 'n_layers': mp['n_disc_layers'], 'norm': mp.get('disc_norm', False)}
+    gen_cfg, disc_cfg = model_cfgs(config['model_params'])
     return dataset_params, train_paths, val_paths, split, gen_cfg, disc_cfg
 
 
@@ -140,9 +169,10 @@ def patchgan_train(argv=None):
         val_data = DataLoader(val_datagen, batch_size=args.batch_size, shuffle=True, pin_memory=True, **dloader_kwargs)
 
     generator = UNet(in_channels, out_channels, gen_cfg['filters'], use_dropout=gen_cfg.get('use_dropout', True),
-                     activation=gen_cfg['activation'], final_act=gen_cfg.get('final_activation', 'sigmoid')).to(device)
+                     activation=gen_cfg['activation'], final_act=gen_cfg.get('final_activation', 'sigmoid'),
+                     norm_layer=norm_layer_of(gen_cfg.get('norm_layer'))).to(device)
     discriminator = Discriminator(in_channels + out_channels, disc_cfg['filters'], norm=disc_cfg.get('norm', False),
-                                  n_layers=disc_cfg['n_layers']).to(device)
+                                  n_layers=disc_cfg['n_layers'], norm_layer=norm_layer_of(disc_cfg.get('norm_layer'))).to(device)
     if world > 1:
         import torch.distributed as dist
         dist.broadcast(generator.flat, 0)          # every rank starts from rank 0's initial weights

@@ -46,7 +46,8 @@ class _UNetFn(torch.autograd.Function):
 class UNet(FlatParamModule, Transferable):
     """UNet(input_nc, output_nc, nf=64, norm_layer=InstanceNorm2d, use_dropout=False, activation='tanh',
     final_act='softmax') -- reference unet.py:76-78.  norm_layer: nn.InstanceNorm2d, nn.BatchNorm2d or -- for data
-    parallelism: the global batch's statistics -- nn.SyncBatchNorm (their defaults)."""
+    parallelism: the global batch's statistics -- nn.SyncBatchNorm (their defaults), or functools.partial(nn.InstanceNorm2d,
+    affine=True): InstanceNorm with a learnable per-channel scale and shift (DownNorm{i} / UpNorm{i} .weight / .bias)."""
 
     def __init__(self, input_nc, output_nc, nf=64, norm_layer=nn.InstanceNorm2d, use_dropout=False,
                  activation='tanh', final_act='softmax'):
@@ -65,9 +66,8 @@ class UNet(FlatParamModule, Transferable):
         eng = self.engine
         t = UNet.__new__(UNet)
         nn.Module.__init__(t)
-        kind = 'syncbatch' if eng.sync_bn else ('batch' if eng.has_bn else 'instance')
         t.engine = E.GeneratorEngine(eng.input_nc, eng.output_nc, eng.nf, eng.activation, eng.final_act, eng.use_dropout,
-                                     algo=eng.algo, norm_kind=kind)
+                                     algo=eng.algo, norm_kind=eng.norm_kind)
         t._param_keys = E.param_keys(t.engine.layers)
         t._seed_base, t._calls = self._seed_base, 0
         t._layers = t.engine.layers
