@@ -586,6 +586,50 @@ int pg_adam_clip_step(float* p, const float* g, float* m, float* v, float* ema, 
 int pg_adam_clip_step_dev(float* p, const float* g, float* m, float* v, float* ema, long n, float beta1, float beta2, float eps,
                           const float* scalars, float ema_decay, const pg_grad_stat* stat, void* stream);
 
+/* ---- spectral normalisation of conv weights (beyond the reference, whose users wrap each nn.Conv2d of the discriminator in
+ * torch.nn.utils.spectral_norm; the call sites are patchgan_amd's Discriminator(spectral_norm=True) and Trainer._enqueue_step /
+ * _adam_step) --------------------------------------------------------------------------------------------------------------------
+ * One item per conv layer, at most PG_SN_MAX_LAYERS per call.  W is the layer's PACKED block [16 taps][Cout][Cin] (tap = kh*4 + kw);
+ * torch's matrix is Wm = weight.reshape(Cout, Cin*16), Wm[o][ci*16 + tap] = W[(tap*Cout + o)*Cin + ci].  u (Cout floats) and v (Cin*16
+ * floats) are stored in torch's order -- weight_u / weight_v of the state_dict --, the kernels do the index arithmetic.  eps = 1e-12.
+ * pg_spectral_fwd, per item (what one forward of torch's hook computes, in training mode with `iterate`, in eval mode without):
+ *   iterate != 0:  t = Wm^T u;  v <- t / max(|t|_2, eps);   s = Wm v;  u <- s / max(|s|_2, eps);  sigma = u^T s with the u just stored
+ *   iterate == 0:  u, v are only read;                      s = Wm v;                             sigma = u^T s
+ *   w_hat = W / sigma, element by element in the packed layout (16*Cout*Cin floats; must not alias W).
+ *   With flat != NULL the call also copies every float of flat[0 .. nflat) that lies outside the items' blocks to the same offset of
+ *   `eff` (biases, norm parameters): the items' W are then blocks of `flat` in ascending order and w_hat == eff + (W - flat), nflat % 4
+ *   == 0 -- `eff` ends up as the network's parameter buffer with every conv weight normalised.  flat == eff == NULL: no copy.
+ *   Up to five launches (k_sn_wtu, k_sn_v -- only with an iterating item --, k_sn_wv, k_sn_u, k_sn_scale), each over all items.
+ * pg_spectral_bwd: the flat gradient `grad` (ngrad floats) holds, at g_off of each item, the gradient w.r.t. w_hat in the packed layout
+ *   and receives the gradient w.r.t. W in place, u, v, sigma constants and sigma differentiated:
+ *   c = <dw_hat, w_hat> over the layer;  dW[o][k] = (dw_hat[o][k] - c * u[o] * v[k]) / sigma.  Floats outside the blocks are not touched.
+ *   Two launches (k_sn_dot, k_sn_map); u, v, sigma, w_hat are what pg_spectral_fwd left, stream-ordered before this call.
+ * Arithmetic: every sum is fp64 in an order that depends on the shapes alone -- per lane in index order, the 64 lanes of a wave by
+ * halving distances 32 .. 1, waves and workgroup partials in index order --, phases exchange partial sums through `ws` between
+ * launches, no workgroup reads what another wrote in the same launch, no floating-point atomics: equal inputs give equal bits in
+ * every launch mode, run and rank (as pg_grad_norm).  Each stored float is ONE rounding of an fp64 expression of the stored fp32
+ * inputs: v = fl(t / max(sqrt(sum t^2), eps)) with t the fp64 column sums, u likewise from the fp64 row sums s of W and the STORED
+ * v, sigma = fl(sum_o u[o] * s[o]), w_hat = fl(W / sigma), dW = fl((dw_hat - (c * u[o]) * v[k]) / sigma) with c the fp64 dot product.
+ * `ws`: pg_spectral_workspace_bytes(n, items) bytes (0 for a bad list), 8-byte aligned, one per stream that runs these calls.
+ * PG_EINVAL before any launch, nothing touched: n <= 0 or > PG_SN_MAX_LAYERS, NULL items, a NULL W / w_hat / u / v / sigma, Cout or
+ * Cin <= 0 or > 65536, W or w_hat not 16-byte aligned, g_off < 0 or not a multiple of 4, a NULL or misaligned or too small ws;
+ * pg_spectral_fwd: flat / eff not both NULL or both 16-byte aligned with the items laid out as above; pg_spectral_bwd: a NULL or
+ * misaligned grad, a block that ends beyond ngrad.  The all-zero matrix (sigma == 0) divides by zero, as torch does. */
+#define PG_SN_MAX_LAYERS 16
+typedef struct pg_spectral_item {
+    const float* W;      /* packed weights [16][Cout][Cin] */
+    float* w_hat;        /* out: W / sigma, the same layout */
+    float* u;            /* [Cout], updated when iterate != 0 */
+    float* v;            /* [Cin*16] in torch's (ci, kh, kw) order, updated when iterate != 0 */
+    float* sigma;        /* out: one float */
+    long g_off;          /* pg_spectral_bwd: first float of the layer's block in the flat gradient */
+    int Cout, Cin, iterate;
+} pg_spectral_item;
+long pg_spectral_workspace_bytes(int n, const pg_spectral_item* items);
+int pg_spectral_fwd(int n, const pg_spectral_item* items, const float* flat, float* eff, long nflat, void* ws, long ws_bytes,
+                    void* stream);
+int pg_spectral_bwd(int n, const pg_spectral_item* items, float* grad, long ngrad, void* ws, long ws_bytes, void* stream);
+
 /* ---- layout(the reference is NCHW end to end; trainer.py:55-66) ---------------------------------- */
 int pg_nchw_to_nhwc(const float* src, float* dst, int ld_dst, int N, int C, int H, int W, void* stream);
 int pg_nhwc_to_nchw(const float* src, int ld_src, float* dst, int N, int C, int H, int W, void* stream);

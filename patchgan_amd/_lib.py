@@ -72,6 +72,16 @@ class ConvPrepItem(ctypes.Structure):
                 ('u', ctypes.c_void_p)]
 
 
+class SpectralItem(ctypes.Structure):
+    """struct pg_spectral_item: one conv layer of pg_spectral_fwd / pg_spectral_bwd"""
+    _fields_ = [('W', ctypes.c_void_p), ('w_hat', ctypes.c_void_p), ('u', ctypes.c_void_p), ('v', ctypes.c_void_p),
+                ('sigma', ctypes.c_void_p), ('g_off', ctypes.c_long), ('Cout', ctypes.c_int), ('Cin', ctypes.c_int),
+                ('iterate', ctypes.c_int)]
+
+
+SN_MAX_LAYERS = 16      # PG_SN_MAX_LAYERS
+
+
 # name -> (restype, argtypes); mirrors include/patchgan_hip.h one to one
 SIGNATURES = {
     'pg_version': (_i, []),
@@ -146,6 +156,9 @@ SIGNATURES = {
     'pg_grad_norm': (_i, [_p, _l, _d, _p, _l, _p, _p]),
     'pg_adam_clip_step': (_i, [_p, _p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _f, _f, _p, _p]),
     'pg_adam_clip_step_dev': (_i, [_p, _p, _p, _p, _p, _l, _f, _f, _f, _p, _f, _p, _p]),
+    'pg_spectral_workspace_bytes': (_l, [_i, ctypes.POINTER(SpectralItem)]),
+    'pg_spectral_fwd': (_i, [_i, ctypes.POINTER(SpectralItem), _p, _p, _l, _p, _l, _p]),
+    'pg_spectral_bwd': (_i, [_i, ctypes.POINTER(SpectralItem), _p, _l, _p, _l, _p]),
     'pg_nchw_to_nhwc': (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
     'pg_nhwc_to_nchw': (_i, [_p, _i, _p, _i, _i, _i, _i, _p]),
     'pg_copy_channels': (_i, [_p, _i, _p, _i, _l, _i, _p]),

@@ -64,6 +64,24 @@ class FlatParamModule(nn.Module):
         counters = torch.zeros(max(eng.nbn, 1), dtype=torch.int64)
         E.init_buffers_(bufs, counters, layers)
         self._bind(flat, bufs, counters)
+        if eng.spectral:
+            # spectral normalisation: u, v (module buffers weight_u / weight_v) and one sigma per layer in a block of their own, drawn
+            # after the weights as torch.nn.utils.spectral_norm draws them when it wraps the finished module
+            sn = torch.zeros(eng.nsn, dtype=torch.float32)
+            E.init_spectral_(sn, layers)
+            self._bind_spectral(sn)
+
+    def _bind_spectral(self, sn):
+        object.__setattr__(self, 'sn_bufs', sn)
+        # the effective-weight buffer and the two workspaces live on the block's device: made on first use (Discriminator.spectral_normalize)
+        object.__setattr__(self, 'sn_eff', None)
+        object.__setattr__(self, 'sn_ws', None)
+        for key, v in E.spectral_views(sn, self._layers).items():
+            mod, leaf = self._owner(key)
+            if leaf in mod._buffers:
+                mod._buffers[leaf] = v
+            else:
+                mod.register_buffer(leaf, v)
 
     def _bind(self, flat, bufs=None, counters=None):
         object.__setattr__(self, 'flat', flat)
@@ -123,6 +141,8 @@ class FlatParamModule(nn.Module):
         new_bufs = self.bn_bufs.to(new_flat.device).contiguous()
         new_counters = self.bn_counters.to(new_flat.device).contiguous()
         self._bind(new_flat.contiguous(), new_bufs, new_counters)
+        if self.engine.spectral:
+            self._bind_spectral(self.sn_bufs.to(new_flat.device).contiguous())
         for p in self.parameters():
             p.grad = None
         return self

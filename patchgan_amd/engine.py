@@ -1291,9 +1291,11 @@ class LayerSpec:
     norm: the layer is followed by a norm; norm_kind 'instance' (no parameters), 'instance_affine' (InstanceNorm2d(affine=True):
     state_dict prefix norm_key, weight / bias at g_off / be_off of the PARAMETER buffer, nothing else) or 'batch' (BatchNorm2d: the
     same two parameters, and running statistics at rm_off / rv_off of the network's BUFFER block, counter bn_idx of its counter
-    tensor, batch statistics at bs_off of its scratch)."""
+    tensor, batch statistics at bs_off of its scratch).
+    sn: the weight is spectrally normalised (the layout of torch.nn.utils.spectral_norm: `key` is ...weight_orig and follows the bias
+    in the state_dict; u / v / sigma at u_off / v_off / s_off of the network's spectral-norm block, assign_spectral)."""
     __slots__ = ('key', 'a', 'b', 'stride', 'transposed', 'p_off', 'bias_key', 'b_off', 'act', 'norm', 'dropout', 'norm_kind',
-                 'norm_key', 'g_off', 'be_off', 'rm_off', 'rv_off', 'bn_idx', 'bs_off')
+                 'norm_key', 'g_off', 'be_off', 'rm_off', 'rv_off', 'bn_idx', 'bs_off', 'sn', 'u_off', 'v_off', 's_off')
 
     def __init__(self, key, a, b, stride, transposed, act, norm, dropout=False, bias_key=None, norm_kind='instance', norm_key=None):
         self.key, self.a, self.b, self.stride, self.transposed = key, a, b, stride, transposed
@@ -1301,6 +1303,7 @@ class LayerSpec:
         self.norm_kind = norm_kind if norm else None
         self.norm_key = norm_key
         self.p_off = self.b_off = self.g_off = self.be_off = self.rm_off = self.rv_off = self.bn_idx = self.bs_off = -1
+        self.sn, self.u_off, self.v_off, self.s_off = False, -1, -1, -1
 
     @property
     def bn(self):
@@ -1378,9 +1381,8 @@ def param_keys(layers):
     """state_dict keys of a network's parameters, in the reference's order."""
     keys = []
     for l in layers:
-        keys.append(l.key)
-        if l.bias_key is not None:
-            keys.append(l.bias_key)
+        # (torch's spectral_norm deletes `weight` and registers `weight_orig`: it then follows the bias)
+        keys += [k for k in ((l.bias_key, l.key) if l.sn else (l.key, l.bias_key)) if k is not None]
         if l.norm_params:
             keys += [l.norm_key + '.weight', l.norm_key + '.bias']
     return keys
@@ -1426,13 +1428,94 @@ def init_buffers_(bufs, counters, layers):
                 bufs[l.rv_off:l.rv_off + l.cout].fill_(1.0)
 
 
+SN_EPS = 1e-12            # torch.nn.utils.spectral_norm's eps (the kernels' SN_EPS)
+
+
+def assign_spectral(layers):
+    """Lay out the spectral-norm block of a network (fp32, outside the parameter buffer like the BatchNorm buffers): per normalised
+    layer u [cout] and v [cin * 16] in torch's order (weight_u / weight_v of the state_dict), then one sigma per layer.  Returns its
+    length in floats (0 without such layers)."""
+    off = 0
+    sn = [l for l in layers if l.sn]
+    for l in sn:
+        l.u_off = off
+        off += (l.a + 3) // 4 * 4
+        l.v_off = off
+        off += l.b * 16
+    for l in sn:
+        l.s_off = off
+        off += 1
+    return (off + 3) // 4 * 4
+
+
+def spectral_views(bufs, layers):
+    """{state_dict key: view} of the spectral-norm buffers (weight_u [cout], weight_v [cin * 16])."""
+    out = {}
+    for l in layers:
+        if l.sn:
+            stem = l.key[:-len('_orig')]
+            out[stem + '_u'] = bufs.as_strided((l.a,), (1,), l.u_off)
+            out[stem + '_v'] = bufs.as_strided((l.b * 16,), (1,), l.v_off)
+    return out
+
+
+def init_spectral_(bufs, layers, generator=None):
+    """The initial u, v of torch.nn.utils.spectral_norm: normalised standard-normal draws from the CPU generator, u then v, layer by
+    layer (after the weights: the wrap follows the module's construction)."""
+    views = spectral_views(bufs, layers)
+    with torch.no_grad():
+        bufs.zero_()
+        for key, view in views.items():
+            draw = torch.empty(view.numel()).normal_(0, 1, generator=generator)
+            view.copy_(torch.nn.functional.normalize(draw, dim=0, eps=SN_EPS))
+
+
+def spectral_items(layers, flat, eff, bufs, iterate=False):
+    """The pg_spectral_item list of a network's normalised layers: weights in `flat`, normalised weights at the same offsets of `eff`
+    (which are also the offsets of the blocks in a flat gradient), u / v / sigma in `bufs`.  flat = None: shapes only."""
+    sn = [l for l in layers if l.sn]
+    items = (L.SpectralItem * len(sn))()
+    for it, l in zip(items, sn):
+        it.Cout, it.Cin, it.iterate, it.g_off = l.a, l.b, 1 if iterate else 0, l.p_off
+        if flat is not None:
+            it.W, it.w_hat = L.ptr(flat, l.p_off), L.ptr(eff, l.p_off)
+            it.u, it.v, it.sigma = L.ptr(bufs, l.u_off), L.ptr(bufs, l.v_off), L.ptr(bufs, l.s_off)
+    return items
+
+
+def spectral_workspace(layers, device):
+    """A workspace for spectral_fwd / spectral_bwd over `layers` (one per stream that runs them)."""
+    items = spectral_items(layers, None, None, None)
+    nbytes = L.load().pg_spectral_workspace_bytes(len(items), items)
+    return torch.zeros(max(nbytes // 8, 1), dtype=torch.float64, device=device)
+
+
+def spectral_fwd(layers, flat, eff, bufs, ws, iterate):
+    """eff <- flat with every normalised layer's weight block divided by its sigma, everything else copied.  iterate: one power
+    iteration first, u and v in `bufs` updated (torch's training-mode forward); else sigma from the stored u, v (eval mode).  sigma is
+    left in `bufs` as well.  Up to five launches on the current stream (pg_spectral_fwd), no host read."""
+    items = spectral_items(layers, flat, eff, bufs, iterate)
+    L.check(L.load().pg_spectral_fwd(len(items), items, flat.data_ptr(), eff.data_ptr(), flat.numel(), ws.data_ptr(),
+                                     ws.numel() * ws.element_size(), _stream()), 'pg_spectral_fwd')
+
+
+def spectral_bwd(layers, eff, bufs, ws, gflat):
+    """The weight blocks of the flat gradient `gflat` from "w.r.t. the normalised weight" to "w.r.t. the stored weight", in place, with
+    the normalised weights, u, v and sigma spectral_fwd left in `eff` / `bufs`.  Two launches on the current stream (pg_spectral_bwd)."""
+    items = spectral_items(layers, eff, eff, bufs)       # (W itself is not read by the backward pair)
+    L.check(L.load().pg_spectral_bwd(len(items), items, gflat.data_ptr(), gflat.numel(), ws.data_ptr(),
+                                     ws.numel() * ws.element_size(), _stream()), 'pg_spectral_bwd')
+
+
 def torch_views(flat, layers):
     """{state_dict key: strided view of `flat` with the reference's shape} (weights [a,b,4,4], biases [cout])."""
     out = {}
     for l in layers:
         ab = l.a * l.b
+        if l.bias_key is not None and l.sn:       # (param_keys' order)
+            out[l.bias_key] = flat.as_strided((l.cout,), (1,), l.b_off)
         out[l.key] = flat.as_strided((l.a, l.b, 4, 4), (l.b, 1, 4 * ab, ab), l.p_off)
-        if l.bias_key is not None:
+        if l.bias_key is not None and not l.sn:
             out[l.bias_key] = flat.as_strided((l.cout,), (1,), l.b_off)
         if l.norm_params:
             out[l.norm_key + '.weight'] = flat.as_strided((l.cout,), (1,), l.g_off)
@@ -1511,6 +1594,7 @@ class _WeightPrep:
         self.has_bn = any(l.bn for l in layers)
         self.sync_bn = self.has_bn and norm_kind == 'syncbatch'
         self.nbuf, self.nbn, self.nscratch = assign_buffers(layers)
+        self.spectral, self.nsn = False, 0      # (spectral normalisation: the discriminator's option, DiscriminatorEngine)
         self.algo = DEFAULT_ALGO if algo is None else algo
         self.act_bf = False          # bf16 activation storage (set_precision('bf16'); only where bf16_storage_ok())
         self._ops = {}
@@ -1761,9 +1845,9 @@ class GeneratorEngine(_WeightPrep):
 # ------------------------------------------------------------------------------------------------
 
 
-def disc_layers(input_nc, ndf, n_layers, norm, norm_kind='instance'):
+def disc_layers(input_nc, ndf, n_layers, norm, norm_kind='instance', spectral=False):
     """Layer plan of reference Discriminator.__init__ (disc.py:19-46); keys are nn.Sequential indices (a norm is the third module
-    of its block: Conv, Tanh, norm)."""
+    of its block: Conv, Tanh, norm).  spectral: every conv as torch.nn.utils.spectral_norm leaves it (weight -> weight_orig)."""
     layers = []
     idx = 0
     layers.append(LayerSpec(f'model.{idx}.weight', ndf, input_nc, 2, False, 'leakyrelu', False, bias_key=f'model.{idx}.bias'))
@@ -1779,6 +1863,9 @@ def disc_layers(input_nc, ndf, n_layers, norm, norm_kind='instance'):
                             norm_key=f'model.{idx + 2}'))
     idx += 3 if norm else 2
     layers.append(LayerSpec(f'model.{idx}.weight', 1, ndf * mult, 1, False, 'sigmoid', False, bias_key=f'model.{idx}.bias'))
+    if spectral:
+        for l in layers:
+            l.key, l.sn = l.key + '_orig', True
     return layers
 
 
@@ -1800,9 +1887,14 @@ class DiscContext:
 class DiscriminatorEngine(_WeightPrep):
     _LD_MULT = 1
 
-    def __init__(self, input_nc, ndf, n_layers, norm, algo=None, norm_kind='instance'):
+    def __init__(self, input_nc, ndf, n_layers, norm, algo=None, norm_kind='instance', spectral=False):
         self.input_nc, self.ndf, self.n_layers, self.norm = input_nc, ndf, n_layers, norm
-        self._init_network(disc_layers(input_nc, ndf, n_layers, norm, layer_kind(norm_kind)), norm_kind, algo)
+        self._init_network(disc_layers(input_nc, ndf, n_layers, norm, layer_kind(norm_kind), spectral), norm_kind, algo)
+        self.spectral = bool(spectral)
+        self.nsn = assign_spectral(self.layers)
+        if self.spectral and len(self.layers) > L.SN_MAX_LAYERS:
+            raise NotImplementedError(f"patchgan_amd: spectral_norm takes at most {L.SN_MAX_LAYERS} conv layers (n_layers <= "
+                                      f"{L.SN_MAX_LAYERS - 2}), got n_layers = {n_layers}")
 
     def bf16_storage_ok(self):
         return self.ndf % 4 == 0 and self.ndf >= 32

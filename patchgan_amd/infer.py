@@ -197,12 +197,13 @@ def patchgan_infer(argv=None):
         f"Dataset class {Dataset.__name__} must have the save_mask method to save a mask cube for a given filename"
     datagen = Dataset(dataset_path, **dataset_kwargs)
 
-    from .train import model_cfgs, norm_layer_of, print_summary
+    from .train import model_cfgs, norm_layer_of, print_summary, spectral_norm_of
     gen_cfg, disc_cfg = model_cfgs(config['model_params'])      # (the norm layers the checkpoints were trained with: train.NORM_LAYERS)
     generator = UNet(in_channels, out_channels, gen_cfg['filters'], activation=gen_cfg['activation'],
                      final_act=gen_cfg.get('final_activation', 'sigmoid'), norm_layer=norm_layer_of(gen_cfg.get('norm_layer'))).to(device)
     discriminator = Discriminator(in_channels + out_channels, disc_cfg['filters'], n_layers=disc_cfg['n_layers'],
-                                  norm=disc_cfg.get('norm', False), norm_layer=norm_layer_of(disc_cfg.get('norm_layer'))).to(device)
+                                  norm=disc_cfg.get('norm', False), norm_layer=norm_layer_of(disc_cfg.get('norm_layer')),
+                                  spectral_norm=spectral_norm_of(disc_cfg.get('spectral_norm'))).to(device)
     if args.summary:
         print_summary('generator', generator)
 

@@ -41,9 +41,19 @@ def norm_layer_of(name='instance'):
     return NORM_LAYERS[name]
 
 
+def spectral_norm_of(value=None):
+    """The spectral_norm constructor argument of the discriminator from its YAML value (None, the key absent: False); ValueError for
+    anything but a bool."""
+    value = False if value is None else value
+    if not isinstance(value, bool):
+        raise ValueError(f"spectral_norm must be true or false, not {value!r}")
+    return value
+
+
 def model_cfgs(mp):
     """(generator_cfg, disc_cfg) of either schema's model_params; a 'norm_layer' name, where one is given, is checked (norm_layer_of:
-    ValueError before any network is built) and an absent one stays absent."""
+    ValueError before any network is built) and an absent one stays absent.  Likewise the discriminator's 'spectral_norm'
+    (model_params.discriminator.spectral_norm, flat schema: disc_spectral_norm; spectral_norm_of)."""
     if 'generator' in mp:
         gen_cfg, disc_cfg = dict(mp['generator']), dict(mp['discriminator'])
     else:                                                                         # flat legacy schema (infer.py:127-132)
@@ -53,8 +63,11 @@ def model_cfgs(mp):
         for cfg, key in ((gen_cfg, 'gen_norm_layer'), (disc_cfg, 'disc_norm_layer')):
             if key in mp:
                 cfg['norm_layer'] = mp[key]
+        if 'disc_spectral_norm' in mp:
+            disc_cfg['spectral_norm'] = mp['disc_spectral_norm']
     for cfg in (gen_cfg, disc_cfg):
         norm_layer_of(cfg.get('norm_layer'))
+    spectral_norm_of(disc_cfg.get('spectral_norm'))
     return gen_cfg, disc_cfg
 
 
@@ -172,11 +185,14 @@ def patchgan_train(argv=None):
                      activation=gen_cfg['activation'], final_act=gen_cfg.get('final_activation', 'sigmoid'),
                      norm_layer=norm_layer_of(gen_cfg.get('norm_layer'))).to(device)
     discriminator = Discriminator(in_channels + out_channels, disc_cfg['filters'], norm=disc_cfg.get('norm', False),
-                                  n_layers=disc_cfg['n_layers'], norm_layer=norm_layer_of(disc_cfg.get('norm_layer'))).to(device)
+                                  n_layers=disc_cfg['n_layers'], norm_layer=norm_layer_of(disc_cfg.get('norm_layer')),
+                                  spectral_norm=spectral_norm_of(disc_cfg.get('spectral_norm'))).to(device)
     if world > 1:
         import torch.distributed as dist
         dist.broadcast(generator.flat, 0)          # every rank starts from rank 0's initial weights
         dist.broadcast(discriminator.flat, 0)
+        if discriminator.spectral_norm:
+            dist.broadcast(discriminator.sn_bufs, 0)      # ... and rank 0's u, v: the ranks' normalised weights stay equal bit for bit
     if args.summary and local_rank == 0:
         print_summary('generator', generator)
         print_summary('discriminator', discriminator)

@@ -17,6 +17,9 @@ Per-step schedule (reference trainer.py:50-115):
    Adam(D) (which then run under the NEXT step's G forward) go to the second stream; flush() joins before D's weights are read.
    How a kind of step is launched -- one stream, two streams, a replay of the captured hipGraph -- is measured, not guessed
    (_launch_mode: a tournament over the candidates the settings allow).
+   With Discriminator(spectral_norm=True) every D pass above reads ONE normalised copy of D's weights, made once per call right after
+   flush() (one power iteration while D is in training mode), and Adam(D) is preceded by the map of the flat gradient back to the stored
+   weights (_adam_step) -- one iteration per step, where torch's hook on a wrapped reference D would iterate on each of its three calls.
 
 Data parallelism: one process per GPU (torch.distributed, backend "nccl" = RCCL).  InstanceNorm is per sample,
 so the only exchanges are the SUM all-reduce of the flat gradient buffers and of two loss-normalisation terms
@@ -649,6 +652,11 @@ class Trainer:
         self._mark('G fwd done')
         self.flush()          # D's deferred all-reduce + Adam from the previous step ran under this G forward
         self._mark('flushed')
+        # D's weights as the step's passes read them.  A spectrally normalised discriminator (Discriminator(spectral_norm=True)): ONE
+        # normalisation per call, here -- behind the previous step's Adam(D), ahead of the fork of the early D forward --, with one power
+        # iteration when D is in training mode; every D pass of this call, forward and backward, and the weight preparation read that
+        # one buffer (a stable address).  Otherwise the flat buffer itself: no launch.
+        dw = D.spectral_normalize() if de.spectral else D.flat
         # seg loss, phase 1 (per-sample reductions); under data parallelism its two batch-global terms are summed across
         # ranks on the comm stream while the discriminator's forward pass over the fake batch runs
         seg_pending = E.loss_begin(gen, yv, 0.0, self.tversky_beta, allred)
@@ -662,7 +670,7 @@ class Trainer:
                 E.seg_hist(gen, yv, bins, self._seg_hist(bins).t)
         # D's weights do not change until the Adam step at the end of this call: its Winograd-transformed weights are computed
         # once per (layer, direction) and shared by the passes below through this per-step cache
-        ucache = de.ucache_begin(D.flat, N, H, W, tag=bool(train))
+        ucache = de.ucache_begin(dw, N, H, W, tag=bool(train))
         # two-stream step: the discriminator step's forward over din[2N] (trainer.py:96-99) needs only the generator's OUTPUT and D's
         # weights, both final here -- it is enqueued on the second stream now and runs under the rest of the generator step (same
         # kernels, same 2N plan: bit-identical); joined where the discriminator step reads its output
@@ -671,7 +679,7 @@ class Trainer:
         # real half (x | y and D's weights only) wherever the 2N pass would run.  Its tensors are allocated here, on this stream, before
         # the fork: both streams write into them, and they are released only after the streams have joined.
         # (both halves of din on one 16-byte phase: the first layer then takes the same kernel for either as for the whole buffer)
-        shared = (de.context(D.flat, din, keep_v=train)
+        shared = (de.context(dw, din, keep_v=train)
                   if (SHARE_D_FAKE and de.halves_ok(N, H, W) and (fake.ptr() - real.ptr()) % 16 == 0) else None)
         real_done = False
         # (evaluation passes and data-parallel steps too; under data parallelism D's deferred update of the previous step has been
@@ -680,10 +688,10 @@ class Trainer:
             n_prepared = len(ucache)
             with E.on_side():
                 if shared is not None:
-                    de.forward_part(D.flat, shared, 0, N, ucache=ucache)
+                    de.forward_part(dw, shared, 0, N, ucache=ucache)
                     real_done = True
                 else:
-                    dc2 = de.forward(D.flat, din, ucache=ucache, keep_v=train, bn=D.bn_run(1, 2))
+                    dc2 = de.forward(dw, din, ucache=ucache, keep_v=train, bn=D.bn_run(1, 2))
                 self._mark('side: dc2 fwd done')
             if len(ucache) != n_prepared:
                 # (a transformed-weight entry the batched preparation did not cover was made by a kernel on the second stream -- the
@@ -692,10 +700,10 @@ class Trainer:
         # (BatchNorm discriminator: this pass's batch statistics go to slot 0, the 2N pass's halves to slots 1 and 2 -- the order of the
         #  reference's three calls, trainer.py:66,97,99, whichever pass runs first here)
         if shared is not None:
-            de.forward_part(D.flat, shared, N, N, ucache=ucache)                              # trainer.py:66 (and the fake half of :98-99)
+            de.forward_part(dw, shared, N, N, ucache=ucache)                                  # trainer.py:66 (and the fake half of :98-99)
             dc = shared.samples(N, N)
         else:
-            dc = de.forward(D.flat, fake, ucache=ucache, bn=D.bn_run(0, 1))                   # trainer.py:66
+            dc = de.forward(dw, fake, ucache=ucache, bn=D.bn_run(0, 1))                       # trainer.py:66
         gseg = E.View.alloc(N, H, W, Cout, dev) if train else None
         E.loss_finish(seg_pending, _LOSS_MODES[self.loss_type], float(self.seg_alpha), gseg, losses, 0, Bglobal,
                       self.tversky_gamma)                                                     # trainer.py:71-82
@@ -706,7 +714,7 @@ class Trainer:
         self._mark('D(fake) fwd + losses done')
         if train:
             gflat = G.ensure_grad_flat()
-            ddin = de.backward(D.flat, None, dc, gd, need_wgrad=False, need_dx=True, ucache=ucache)   # dL/d(x|gen)
+            ddin = de.backward(dw, None, dc, gd, need_wgrad=False, need_dx=True, ucache=ucache)       # dL/d(x|gen)
             self._mark('D dgrad done')
             if dist.on:
                 # buckets of the flat G gradient are all-reduced on RCCL's stream as backward finishes them; the
@@ -734,10 +742,10 @@ class Trainer:
         # ---- discriminator step: real and (pre-update, detached) fake in one 2N batch        trainer.py:96-99
         if shared is not None:
             if not real_done:
-                de.forward_part(D.flat, shared, 0, N, ucache=ucache)                          # trainer.py:96-97
+                de.forward_part(dw, shared, 0, N, ucache=ucache)                              # trainer.py:96-97
             dc2 = shared
         elif dc2 is None:
-            dc2 = de.forward(D.flat, din, ucache=ucache, keep_v=train, bn=D.bn_run(1, 2))
+            dc2 = de.forward(dw, din, ucache=ucache, keep_v=train, bn=D.bn_run(1, 2))
         if ex.pending or ex.keep:
             E.side_join()
         D.bn_update(3)        # BatchNorm discriminator in training mode: the three passes' updates in the reference's order (on this stream, after the join)
@@ -768,7 +776,7 @@ class Trainer:
                 # bit-identical; flush() joins before anything reads D's weights (the next step's D passes, save / load, the end of train,
                 # state_dict() / forward of the module).  The pass's operands stay referenced until then.
                 with E.on_side():
-                    de.backward(D.flat, dflat, dc2, god, need_wgrad=True, need_dx=False, ucache=ucache)   # trainer.py:106
+                    de.backward(dw, dflat, dc2, god, need_wgrad=True, need_dx=False, ucache=ucache)       # trainer.py:106
                     if g_reducer is not None:
                         self._pending_d = dist.all_reduce_side(dflat)      # (behind the pass on the second stream; Adam(D) in flush())
                     else:
@@ -786,7 +794,7 @@ class Trainer:
                     self._adam_step('g')
                     self._mark('Adam(G) done')
             else:
-                de.backward(D.flat, dflat, dc2, god, need_wgrad=True, need_dx=False, ucache=ucache)   # trainer.py:106
+                de.backward(dw, dflat, dc2, god, need_wgrad=True, need_dx=False, ucache=ucache)       # trainer.py:106
                 if g_reducer is not None:
                     # D's gradient (11 MB at ndf=64) is all-reduced asynchronously and applied by flush() at the first use of
                     # D's weights -- after the NEXT step's generator forward, which does not read them (trainer.py:63-66); handed to
@@ -840,6 +848,10 @@ class Trainer:
         net, (m, v) = (self.generator, self._adam[0:2]) if which == 'g' else (self.discriminator, self._adam[2:4])
         decay = self._ema_now() if which == 'g' else None
         max_norm = self._clip_now()[0 if which == 'g' else 1]
+        if which == 'd' and net.engine.spectral:
+            # the passes ran on W / sigma: the flat gradient (all-reduced already under data parallelism -- the map is linear in it, and
+            # u, v, sigma agree on every rank) becomes the gradient of the stored weights, on this stream, ahead of the norm and Adam
+            net.spectral_grad_map(net.grad_flat)
         if max_norm is not None:
             # the norm of the whole flat gradient (two short launches) and Adam on g * coef, both behind the gradient on this stream;
             # a non-finite norm skips the update on the device -- the host's step count advances regardless
@@ -1118,7 +1130,8 @@ class Trainer:
         st.hold = (E.cur_exec(dev).buffers() + list(G.engine.__dict__.get('_upool', {}).values())
                    + list(D.engine.__dict__.get('_upool', {}).values()) + [G.grad_flat, D.grad_flat] + list(self._adam)
                    + ([self._ema] if self._ema_now() is not None else [])
-                   + (list(self._clip) if (self._clip is not None and self._clip_now() != (None, None)) else []))
+                   + (list(self._clip) if (self._clip is not None and self._clip_now() != (None, None)) else [])
+                   + ([D.sn_bufs, D.sn_eff] + list(D.sn_ws) if D.engine.spectral else []))
         st.ptrs = self._graph_ptrs()
         self._graphs[key] = st
         return st
