@@ -55,9 +55,12 @@ extern "C" {
 #define PG_ACT_SIGMOID 4
 
 /* algorithm selector for the three conv entry points */
-#define PG_ALGO_AUTO 0   /* fastest fp32 kernel for the geometry: PG_ALGO_MFMA, except Winograd on MFMA (fp32; 1.5e-6 .. 4e-6
-                            relative error instead of 1e-7) for wide stride-1 layers (F(2x2,4x4) / F(3x3,4x4); weight gradient
-                            F(4x4,2x2)) and channel-heavy stride-2 layers (polyphase F(3x3,2x2)) */
+#define PG_ALGO_AUTO 0   /* fastest fp32 kernel for the geometry: PG_ALGO_MFMA, except Winograd on MFMA (fp32; 0.6e-6 .. 4e-6
+                            relative error in the max norm, max |error| / max |result|, forward and data gradient, 4e-6 .. 8e-6
+                            weight gradient over 8 k summed pixels and growing with their number, instead of 1e-7; per element
+                            at most 1.7e-6 of sum |x| |w|, 3 .. 6e-8 rms: tests/test_wino1_gpu.py) for wide stride-1 layers
+                            (F(2x2,4x4) / F(3x3,4x4); weight gradient F(4x4,2x2) / F(4x4,3x3)) and channel-heavy stride-2
+                            layers (polyphase F(3x3,2x2)) */
 #define PG_ALGO_DIRECT 1 /* one-thread-per-output reference-quality kernels (any channel count) */
 #define PG_ALGO_MFMA 2   /* LDS-tiled implicit GEMM on v_mfma_f32_32x32x2_f32 (channels % 4 == 0) */
 #define PG_ALGO_BF16 3   /* same kernels with operand tiles rounded to bf16 in LDS and v_mfma_f32_32x32x16_bf16 (fp32

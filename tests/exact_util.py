@@ -38,13 +38,14 @@ GAIN_IN, GAIN_W, LSB_W, TERMS_OUT = _gain(BT3) ** 2, _gain(G3) ** 2, 0.25, int(_
 GAIN_DY, LSB_DY, TERMS_OUT_W = _gain(G23) ** 2, 0.25, int(_gain(A2T) ** 2)
 
 
-def source_tables(path):
-    """The same tables parsed out of conv_wino.hip."""
+def source_tables(path, names=None):
+    """The same tables parsed out of conv_wino.hip (names: default those of TABLES).  An entry is a literal or a quotient of two
+    (`-16.f / 15`), evaluated as the compiler does: in fp32."""
     src = open(path).read()
     out = {}
-    for name, ref in TABLES.items():
-        m = re.search(r'float %s\[(\d+)\]\[(\d+)\] = (\{.*?\});' % name, src)
-        vals = [float(v.rstrip('f')) for v in re.findall(r'-?\d+\.?\d*f?', m.group(3))]
+    for name in (TABLES if names is None else names):
+        m = re.search(r'float %s\[(\d+)\]\[(\d+)\] = (\{.*?\});' % name, src, re.S)
+        vals = [np.float32(num) / np.float32(den or 1) for num, den in re.findall(r'(-?\d+\.?\d*)f?(?:\s*/\s*(\d+\.?\d*)f?)?', m.group(3))]
         out[name] = np.array(vals, np.float32).reshape(int(m.group(1)), int(m.group(2)))
     return out
 
