@@ -694,6 +694,45 @@ int pg_tiles_gather_tta(const float* image, int C, int H, int W, int size, int e
 int pg_tiles_blend_win(const float* tiles, int ld, int C, int size, int eff, int H, int W, int K, const double* window,
                        double threshold, double* mask, long long* argmax, void* stream);
 
+/* ---- differentiable augmentation of the discriminator's inputs (beyond the reference; Zhao et al. 2020, "Differentiable Augmentation
+ * for Data-Efficient GAN Training": the call sites are patchgan_amd's Trainer.diffaug) ---------------------------------------------------
+ * A per-sample map T of pixels -- horizontal flip, then translation with zero padding, then a zeroed box --, applied to what the
+ * discriminator reads (real and fake alike) and, as its exact adjoint, to the gradient that returns to the generator.  Policy bits: */
+#define PG_AUG_FLIP 1
+#define PG_AUG_TRANSLATION 2
+#define PG_AUG_CUTOUT 4
+/* The table: params[N][8] int32 on the device, row n = {flip, ty, tx, cut_top, cut_left, cut_h, cut_w, 0} of GLOBAL sample sample0 + n.
+ * Every draw is a pure function of (seed, step count t, global sample index s, draw index k), all arithmetic modulo 2^64, with
+ * mix64 = pg_mix64 of csrc/pg_common.h (x ^= x >> 30; x *= 0xbf58476d1ce4e5b9; x ^= x >> 27; x *= 0x94d049bb133111eb; x ^= x >> 31),
+ * GOLD = 0x9e3779b97f4a7c15 and DOMAIN = 0x6469666661756721:
+ *     key  = mix64(mix64((seed ^ DOMAIN) + GOLD * (t + 1)) + GOLD * (s + 1))
+ *     r[k] = mix64(key + GOLD * (k + 1))
+ *     flip     = r[0] >> 63
+ *     ty       = (r[1] >> 32) % (2 * (H / 8) + 1) - H / 8          tx = (r[2] >> 32) % (2 * (W / 8) + 1) - W / 8
+ *     cut_h    = H / 2,  cut_w = W / 2
+ *     cut_top  = (r[3] >> 32) % (H + 1) - cut_h / 2                 cut_left = (r[4] >> 32) % (W + 1) - cut_w / 2
+ * (integer divisions; the modulo bias of 32 random bits over at most a few thousand values is ignored).  The box covers rows
+ * cut_top <= h < cut_top + cut_h and columns likewise, and may hang over the border.  A policy bit that is off gives the neutral
+ * value: flip 0, ty = tx = 0, the empty box {0, 0, 0, 0}.  A counter-based stream like the dropout mask's: a table split into two
+ * calls with shifted sample0 has the same rows, and the ranks of a data-parallel job draw what the single process draws.
+ * The step count t: with counter != NULL (a 64-bit device word, 8-byte aligned) t = *counter and the kernel stores t + 1 behind
+ * every read of it -- the launch then carries nothing that changes from step to step, so a captured step replays with fresh draws
+ * (as pg_adam_step_dev and pg_batchnorm_update_running do); with counter == NULL, t is the host argument `step`.  One workgroup.
+ * Writes the N * 8 table words and the counter word, nothing else.  PG_EINVAL before any launch: NULL or misaligned params,
+ * misaligned counter, N, H or W <= 0, sample0 < 0, policy outside 0 .. 7. */
+int pg_diffaug_params(uint64_t seed, unsigned long long* counter, uint64_t step, int policy, long sample0, int N, int H, int W, int* params,
+                      void* stream);
+/* dst = T(src): fp32 NHWC channel slices [N,H,W,C] (C need not be a multiple of 4; 16-byte moves where bases, ld and C allow).  Per
+ * output pixel (h, w) of sample n, with row n of the table:  inside the box -> 0;  hs = h - ty, ws = w - tx, outside the image -> 0;
+ * if flip: ws = W - 1 - ws;  dst[n,h,w,:] = src[n,hs,ws,:].  Values are moved, never computed on: bit-exact.  The table is trusted
+ * for its VALUES only (any int32 content is safe: coordinates are checked before the read).  Writes the C channels of each dst
+ * pixel.  PG_EINVAL before any launch: NULL pointers, ld < C, N*H*W >= 2^31, src and dst ranges that intersect. */
+int pg_diffaug_fwd(const float* src, int ld_src, float* dst, int ld_dst, const int* params, int N, int H, int W, int C, void* stream);
+/* dsrc = T^t(g), the exact adjoint, written as a gather: T is an injective partial map of pixels, so every dsrc element is one g
+ * element or 0 and is written exactly once -- no atomics.  Per dsrc pixel (hs, w0):  ws = flip ? W - 1 - w0 : w0;  h = hs + ty,
+ * w = ws + tx;  outside the image or inside the box -> 0;  dsrc[n,hs,w0,:] = g[n,h,w,:].  Same argument rules as pg_diffaug_fwd. */
+int pg_diffaug_bwd(const float* g, int ld_g, float* dsrc, int ld_dsrc, const int* params, int N, int H, int W, int C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,7 @@ TUNE_BF16X_OFF, TUNE_BF16X_RING, TUNE_BF16X_FLAT = 0x2000, 0x4000, 0x8000
 TUNE_S3_OFF = 0x40000        # the three Winograd GEMM families on the fp32 MFMA instead of their split-bf16 forms k_*_s3 (PG_TUNE_S3_OFF)
 LOSS_TVERSKY, LOSS_WBCE, LOSS_MAE, LOSS_BCE = 0, 1, 2, 3
 OP_BIG2SMALL, OP_SMALL2BIG, OP_WGRAD = 0, 1, 2
+AUG_FLIP, AUG_TRANSLATION, AUG_CUTOUT = 1, 2, 4      # PG_AUG_*
 
 _ERR = {-1: 'PG_EINVAL (bad shape / null or misaligned pointer)', -2: 'PG_EWORKSPACE (workspace too small)',
         -3: 'PG_ELAUNCH (HIP launch failed)'}
@@ -173,6 +174,9 @@ SIGNATURES = {
     'pg_tiles_tta_max': (_i, []),
     'pg_tiles_gather_tta': (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _i, _p]),
     'pg_tiles_blend_win': (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, ctypes.c_double, _p, _p, _p]),
+    'pg_diffaug_params': (_i, [_u64, _p, _u64, _i, _l, _i, _i, _i, _p, _p]),
+    'pg_diffaug_fwd': (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _p]),
+    'pg_diffaug_bwd': (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _p]),
 }
 
 _lib = None

@@ -1081,6 +1081,73 @@ def tta_variants(tta):
     return TTA_VARIANTS[tta]
 
 
+AUG_POLICIES = {'flip': L.AUG_FLIP, 'translation': L.AUG_TRANSLATION, 'cutout': L.AUG_CUTOUT}
+
+
+def diffaug_policy(policy):
+    """The PG_AUG_* bits of a differentiable-augmentation policy: None, a comma-separated string or a sequence of names out of
+    'flip', 'translation', 'cutout' (the order of application is fixed: flip, translation, cutout).  The empty policy equals None:
+    0.  ValueError for anything else, naming the allowed words."""
+    if policy is None:
+        return 0
+    if isinstance(policy, str):
+        names = [w.strip() for w in policy.split(',') if w.strip()]
+    elif isinstance(policy, (list, tuple)):
+        names = list(policy)
+    else:
+        names = [policy]
+    bits = 0
+    for w in names:
+        if not isinstance(w, str) or w not in AUG_POLICIES:
+            raise ValueError(f"diffaug must be None or made of {', '.join(AUG_POLICIES)} (a comma-separated string or a list), not {policy!r}")
+        bits |= AUG_POLICIES[w]
+    return bits
+
+
+def diffaug_seed(seed):
+    """Trainer.diffaug_seed checked: an int in 0 .. 2^64 - 1 (bool excluded).  ValueError otherwise."""
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) <= _MASK64:
+        raise ValueError(f"diffaug_seed must be an integer in 0 .. 2**64 - 1, not {seed!r}")
+    return int(seed)
+
+
+def diffaug_params(seed, counter, step, policy, sample0, N, H, W, params=None, device=None):
+    """The parameter table of one step (pg_diffaug_params): an int32 device tensor [N, 8], rows {flip, ty, tx, cut_top, cut_left, cut_h,
+    cut_w, 0} of global samples sample0 .. sample0 + N.  `counter`: a one-word int64 device tensor holding the step count, advanced by
+    the launch -- or None, then the host value `step` is the step count.  `policy`: PG_AUG_* bits.  On the current stream."""
+    if params is None:
+        params = torch.empty(N, 8, dtype=torch.int32, device=counter.device if counter is not None else device)
+    assert params.dtype == torch.int32 and params.is_contiguous() and params.numel() == N * 8
+    assert counter is None or (counter.dtype == torch.int64 and counter.numel() == 1 and counter.device == params.device)
+    L.check(L.load().pg_diffaug_params(int(seed) & _MASK64, counter.data_ptr() if counter is not None else None, int(step) & _MASK64,
+                                       int(policy), int(sample0), N, H, W, params.data_ptr(), _stream()), 'pg_diffaug_params')
+    return params
+
+
+def _diffaug_rows(view, params, n0):
+    assert not view.bf, 'the augmentation moves fp32 views'
+    assert params.dtype == torch.int32 and params.is_contiguous() and params.dim() == 2 and params.shape[1] == 8
+    assert 0 <= n0 and n0 + view.N <= params.shape[0], (n0, view.N, tuple(params.shape))
+    return params.data_ptr() + n0 * 32
+
+
+def diffaug_fwd(src, dst, params, n0=0):
+    """dst = T(src) for fp32 Views of one shape (pg_diffaug_fwd); sample i of the views takes row n0 + i of the table -- a half of a
+    2N buffer is passed as View.samples(...) with the rows of the samples it pairs with.  On the current stream."""
+    assert (src.N, src.H, src.W, src.C) == (dst.N, dst.H, dst.W, dst.C) and not dst.bf
+    L.check(L.load().pg_diffaug_fwd(src.ptr(), src.ld, dst.ptr(), dst.ld, _diffaug_rows(src, params, n0), src.N, src.H, src.W, src.C,
+                                    _stream()), 'pg_diffaug_fwd')
+    return dst
+
+
+def diffaug_bwd(g, dsrc, params, n0=0):
+    """dsrc = T^t(g), the exact adjoint of diffaug_fwd with the same rows (pg_diffaug_bwd): every element of dsrc is written."""
+    assert (g.N, g.H, g.W, g.C) == (dsrc.N, dsrc.H, dsrc.W, dsrc.C) and not dsrc.bf
+    L.check(L.load().pg_diffaug_bwd(g.ptr(), g.ld, dsrc.ptr(), dsrc.ld, _diffaug_rows(g, params, n0), g.N, g.H, g.W, g.C, _stream()),
+            'pg_diffaug_bwd')
+    return dsrc
+
+
 def window_table(window, size):
     """The blend window as `size` float64 weights: None (uniform) ones, 'pyramid' min(u + 1, size - u), 'hann' the half-sample
     sin^2 form (positive everywhere), or a 1-D sequence of `size` numbers.  A pixel may be covered by a single tile, so every weight

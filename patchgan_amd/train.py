@@ -95,7 +95,8 @@ def apply_train_params(trainer, train_params):
     (Trainer.metrics: per-epoch validation IoU / Dice from counts kept on the device), save_best ('miou' | 'mdice': best_*.pth),
     metric_bins (Trainer.metric_bins: a power of two in 16..1024 -- score curves, average precision and the best threshold) and
     clip_grad_norm (Trainer.clip_grad_norm: a number for both networks or a two-element list [generator, discriminator] whose members
-    may be null; a non-finite gradient then skips the step)."""
+    may be null; a non-finite gradient then skips the step), diffaug / diffaug_seed (Trainer.diffaug: differentiable augmentation of
+    the discriminator's inputs; diffaug_of)."""
     trainer.loss_type = train_params['loss_type']
     trainer.seg_alpha = train_params['seg_alpha']
     trainer.ema_decay = train_params.get('ema_decay', None)
@@ -105,6 +106,18 @@ def apply_train_params(trainer, train_params):
     trainer.metric_threshold = float(train_params.get('metric_threshold', 0.5))
     trainer.save_best = train_params.get('save_best', None)
     trainer.metric_bins = train_params.get('metric_bins', None)
+    trainer.diffaug, trainer.diffaug_seed = diffaug_of(train_params.get('diffaug', None), train_params.get('diffaug_seed', None))
+
+
+def diffaug_of(policy=None, seed=None):
+    """(Trainer.diffaug, Trainer.diffaug_seed) from the YAML's train_params.diffaug -- a comma-separated string or a list out of flip,
+    translation, cutout; absent or empty = off -- and train_params.diffaug_seed (an int; absent = 0).  ValueError for anything else,
+    before any batch is read."""
+    from . import engine as E
+    seed = E.diffaug_seed(0 if seed is None else seed)
+    if policy is not None and not isinstance(policy, (str, list)):
+        raise ValueError(f"diffaug must be a string or a list out of {', '.join(E.AUG_POLICIES)}, not {policy!r}")
+    return (policy if E.diffaug_policy(policy) else None), seed
 
 
 def print_summary(name, module):

@@ -20,6 +20,9 @@ Per-step schedule (reference trainer.py:50-115):
    With Discriminator(spectral_norm=True) every D pass above reads ONE normalised copy of D's weights, made once per call right after
    flush() (one power iteration while D is in training mode), and Adam(D) is preceded by the map of the flat gradient back to the stored
    weights (_adam_step) -- one iteration per step, where torch's hook on a wrapped reference D would iterate on each of its three calls.
+   With Trainer.diffaug set, a training step's D passes read T(din), a per-sample flip / translation / cutout of the input buffer
+   made by two moves (the real half ahead of the generator forward, the fake half behind it), and the gradient returns to G through
+   the adjoint move; the draws come from a device-resident counter-based stream, so every launch mode sees the same tables.
 
 Data parallelism: one process per GPU (torch.distributed, backend "nccl" = RCCL).  InstanceNorm is per sample,
 so the only exchanges are the SUM all-reduce of the flat gradient buffers and of two loss-normalisation terms
@@ -189,6 +192,21 @@ class Trainer:
     # pass updates, are not protected.  read_grad_stats() / reset_grad_stats(); train() reads once per epoch into `grad_history`.
     clip_grad_norm = None
 
+    # Differentiable augmentation of what the discriminator sees (opt-in, beyond the reference; Zhao et al. 2020): None = off -- no buffer,
+    # the same launches, the same kind key, the same bits.  A comma-separated string or a sequence out of 'flip', 'translation', 'cutout'
+    # (engine.diffaug_policy; applied in that order): in a TRAINING step every discriminator pass -- the generator step's D(x | G(x)), the
+    # discriminator step's real and fake halves, and both backward passes -- reads T(din) instead of din, T a per-sample map of pixels
+    # (horizontal flip, translation by up to 1/8 of the extent with zero padding, a zeroed box of half the extent; pg_diffaug_fwd),
+    # and the gradient returns to the generator through its exact adjoint (pg_diffaug_bwd).  Real sample i and fake sample i take the SAME
+    # row of the step's parameter table (the condition image stays consistent), drawn once per call on the device by pg_diffaug_params
+    # from (diffaug_seed, a step count kept in a device word, the GLOBAL sample index): a captured step replays with fresh draws, and
+    # the ranks of a data-parallel job draw what the single process draws for the large batch.  The generator's output, the segmentation
+    # loss, the metrics and evaluation steps stay on the un-augmented tensors; evaluation steps do not advance the count.
+    # read_diffaug_params() returns the last step's table.  Neither the count nor the seed is checkpointed (dropout's stream is not
+    # either): a resumed run starts the stream again.
+    diffaug = None
+    diffaug_seed = 0         # a stream of its own, independent of dropout's
+
     # Segmentation metrics of evaluation passes (opt-in, beyond the reference): None = off -- no launch, no buffer, no key, file or
     # printed line.  True: every batch(train=False) adds ONE launch beside its segmentation loss (engine.seg_confusion: the confusion
     # counts of G(x) against y, integers, accumulated in `seg_counts` on the device; reset_metrics() / read_metrics()), train() records
@@ -281,6 +299,8 @@ class Trainer:
         self._best = None          # metrics.BestTracker (save_best)
         self._clip = None          # clip_grad_norm: (status blocks of G and D: 2 x 64 bytes, G's reduction workspace, D's) on the device
         self.grad_history = []     # train() with clip_grad_norm: one read_grad_stats() dict per epoch
+        self._aug_counter = None   # diffaug: the step count of the parameter stream, one int64 word on the device (persistent)
+        self._aug_params = None    # diffaug: the last training step's parameter table (int32 [N, 8] on the device)
 
     # -------------------------------------------------------------------------------------- optimizers
     def setup_optimizers(self, gen_lr=1e-3, dsc_lr=1e-3):
@@ -341,6 +361,43 @@ class Trainer:
             raise RuntimeError("reset_grad_stats(): Trainer.clip_grad_norm is None (gradient-norm clipping is off)")
         self.flush()
         self._clip[0].zero_()
+
+    # -------------------------------------------------------------------------------------- differentiable augmentation
+    def _aug_now(self):
+        """None (off) or (policy bits, seed) of the next training step, both validated."""
+        if self.diffaug is None:
+            return None
+        bits = E.diffaug_policy(self.diffaug)
+        return (bits, E.diffaug_seed(self.diffaug_seed)) if bits else None
+
+    def _aug_ensure(self):
+        """With diffaug set: the persistent step-count word (created zeroed outside any capture, re-created on another device)."""
+        if self._aug_now() is None:
+            return
+        dev = self.generator.flat.device
+        if self._aug_counter is None or self._aug_counter.device != dev:
+            self._aug_counter = torch.zeros(1, dtype=torch.int64, device=dev)
+
+    def _aug_begin(self, aug, din, real, rank):
+        """The step's parameter table and the augmented discriminator input, on the current stream: one parameter launch, din_aug
+        allocated beside din (same shape and pixel stride: its halves keep din's 16-byte phase relation) and its real half filled.
+        -> (din_aug, its real half, its fake half -- still to be filled once the generator has written din's --, the table)."""
+        N = real.N
+        self._aug_ensure()
+        params = self._aug_params = E.diffaug_params(aug[1], self._aug_counter, 0, aug[0], rank * N, N, real.H, real.W)
+        # (8-float pixels of fewer channels: the pad channels are zero as din's are)
+        t = (torch.zeros if din.ld != din.C else torch.empty)(din.N * din.H * din.W * din.ld, dtype=torch.float32, device=din.t.device)
+        din_aug = E.View(t, 0, din.ld, din.N, din.H, din.W, din.C)
+        real_aug, fake_aug = din_aug.samples(0, N), din_aug.samples(N, N)
+        E.diffaug_fwd(real, real_aug, params, 0)
+        return din_aug, real_aug, fake_aug, params
+
+    def read_diffaug_params(self):
+        """The parameter table of the last training step: int32 NumPy array [N, 8], rows {flip, ty, tx, cut_top, cut_left, cut_h, cut_w,
+        0} of this rank's samples (one synchronising copy; for tests and inspection)."""
+        if self._aug_params is None:
+            raise RuntimeError("read_diffaug_params(): no training step with Trainer.diffaug set has run")
+        return self._aug_params.cpu().numpy().copy()
 
     # -------------------------------------------------------------------------------------- the generator's weight average
     @property
@@ -538,6 +595,8 @@ class Trainer:
             self._ema_ensure()    # (a generator moved / re-tuned since: the average follows)
         if train and self.clip_grad_norm is not None:
             self._clip_ensure()   # (set after setup_optimizers(), or the networks moved: never allocated inside a capture)
+        if train and self.diffaug is not None:
+            self._aug_ensure()    # (the step-count word: never allocated inside a capture)
         self._step += 1
         ex = self._exec
         if ex is None or ex.device != dev:
@@ -637,6 +696,14 @@ class Trainer:
 
         din, real, fake = self._din(x, y, u8, N, H, W, Cin, Cout)
         xin, yv, gen = fake.channels(0, Cin), real.channels(Cin, Cout), fake.channels(Cin, Cout)
+        # differentiable augmentation (training steps with Trainer.diffaug): every D pass below reads din_d = T(din) instead of din.  The
+        # table and the real half (x | y only) are made here, on this stream, ahead of the fork of the early D forward; the fake half
+        # follows the generator forward; real sample i and fake sample i share row i.  Off: din_d IS din -- no launch, no buffer.
+        aug = self._aug_now() if train else None
+        if aug is not None:
+            din_d, real_d, fake_d, aug_params = self._aug_begin(aug, din, real, dist.rank)
+        else:
+            din_d, real_d, fake_d, aug_params = din, real, fake, None
 
         losses = torch.empty(4, dtype=torch.float32, device=dev)   # seg, gdisc, real*0.5, fake*0.5 (each written by its loss kernel)
         allred = dist.all_reduce_side if dist.on else None
@@ -649,6 +716,8 @@ class Trainer:
         gc = ge.forward(G.flat, xin, gen, G.training, seed, sample0=dist.rank * N, keep_v=train, ucache=gcache,
                         bn=G.bn_run())                                                        # trainer.py:63
         G.bn_update(1)        # BatchNorm generator in training mode: its one running-statistics update of the step
+        if aug is not None:
+            E.diffaug_fwd(fake, fake_d, aug_params, 0)      # x | G(x) under the rows of the real samples it is paired with
         self._mark('G fwd done')
         self.flush()          # D's deferred all-reduce + Adam from the previous step ran under this G forward
         self._mark('flushed')
@@ -679,8 +748,8 @@ class Trainer:
         # real half (x | y and D's weights only) wherever the 2N pass would run.  Its tensors are allocated here, on this stream, before
         # the fork: both streams write into them, and they are released only after the streams have joined.
         # (both halves of din on one 16-byte phase: the first layer then takes the same kernel for either as for the whole buffer)
-        shared = (de.context(dw, din, keep_v=train)
-                  if (SHARE_D_FAKE and de.halves_ok(N, H, W) and (fake.ptr() - real.ptr()) % 16 == 0) else None)
+        shared = (de.context(dw, din_d, keep_v=train)
+                  if (SHARE_D_FAKE and de.halves_ok(N, H, W) and (fake_d.ptr() - real_d.ptr()) % 16 == 0) else None)
         real_done = False
         # (evaluation passes and data-parallel steps too; under data parallelism D's deferred update of the previous step has been
         #  applied by flush() above, and on_side() orders the second stream behind it)
@@ -691,7 +760,7 @@ class Trainer:
                     de.forward_part(dw, shared, 0, N, ucache=ucache)
                     real_done = True
                 else:
-                    dc2 = de.forward(dw, din, ucache=ucache, keep_v=train, bn=D.bn_run(1, 2))
+                    dc2 = de.forward(dw, din_d, ucache=ucache, keep_v=train, bn=D.bn_run(1, 2))
                 self._mark('side: dc2 fwd done')
             if len(ucache) != n_prepared:
                 # (a transformed-weight entry the batched preparation did not cover was made by a kernel on the second stream -- the
@@ -703,7 +772,7 @@ class Trainer:
             de.forward_part(dw, shared, N, N, ucache=ucache)                                  # trainer.py:66 (and the fake half of :98-99)
             dc = shared.samples(N, N)
         else:
-            dc = de.forward(dw, fake, ucache=ucache, bn=D.bn_run(0, 1))                       # trainer.py:66
+            dc = de.forward(dw, fake_d, ucache=ucache, bn=D.bn_run(0, 1))                     # trainer.py:66
         gseg = E.View.alloc(N, H, W, Cout, dev) if train else None
         E.loss_finish(seg_pending, _LOSS_MODES[self.loss_type], float(self.seg_alpha), gseg, losses, 0, Bglobal,
                       self.tversky_gamma)                                                     # trainer.py:71-82
@@ -715,6 +784,10 @@ class Trainer:
         if train:
             gflat = G.ensure_grad_flat()
             ddin = de.backward(dw, None, dc, gd, need_wgrad=False, need_dx=True, ucache=ucache)       # dL/d(x|gen)
+            dgen = ddin.channels(Cin, Cout)
+            if aug is not None:
+                # D read T(x | G(x)): the gradient returns to G's output through the adjoint, into a view of its own
+                dgen = E.diffaug_bwd(dgen, E.View.alloc(N, H, W, Cout, dev), aug_params, 0)
             self._mark('D dgrad done')
             if dist.on:
                 # buckets of the flat G gradient are all-reduced on RCCL's stream as backward finishes them; the
@@ -727,7 +800,7 @@ class Trainer:
             # trainer.py:98), so the join and G's Adam update come after it
             two = bool(ex.enabled)
             late_adam_g = two and g_reducer is None
-            ge.backward(G.flat, gflat, gc, gseg, ddin.channels(Cin, Cout),                    # trainer.py:88-89
+            ge.backward(G.flat, gflat, gc, gseg, dgen,                                        # trainer.py:88-89
                         on_ready=g_reducer.ready if g_reducer is not None else None, ucache=gcache, defer_join=two)
             ge.ucache_end(gcache)
             self._mark('G bwd (main chain) done')
@@ -745,7 +818,7 @@ class Trainer:
                 de.forward_part(dw, shared, 0, N, ucache=ucache)                              # trainer.py:96-97
             dc2 = shared
         elif dc2 is None:
-            dc2 = de.forward(dw, din, ucache=ucache, keep_v=train, bn=D.bn_run(1, 2))
+            dc2 = de.forward(dw, din_d, ucache=ucache, keep_v=train, bn=D.bn_run(1, 2))
         if ex.pending or ex.keep:
             E.side_join()
         D.bn_update(3)        # BatchNorm discriminator in training mode: the three passes' updates in the reference's order (on this stream, after the join)
@@ -908,7 +981,10 @@ class Trainer:
         # (the max-norms are launch arguments of pg_grad_norm, as the decay is one of Adam(G): a captured step holds the values it was
         #  captured with, a changed value is another kind of step.  Off: the key is the one without the feature)
         clip = self._clip_now() if train else (None, None)
-        return self._kind_key_base(x, y, u8, dims, train) + ((clip,) if clip != (None, None) else ())
+        # (likewise the augmentation's policy and seed, launch arguments of pg_diffaug_params)
+        aug = self._aug_now() if train else None
+        return (self._kind_key_base(x, y, u8, dims, train) + ((clip,) if clip != (None, None) else ())
+                + ((('diffaug',) + aug,) if aug is not None else ()))
 
     def _kind_key_base(self, x, y, u8, dims, train):
         G, D = self.generator, self.discriminator
@@ -1083,6 +1159,7 @@ class Trainer:
         st.scal.copy_(host, non_blocking=True)
         st.graph.replay()
         self._last_gen = st.gen
+        self._aug_params = st.aug_params
         return st.losses
 
     def _graph_ptrs(self):
@@ -1119,6 +1196,7 @@ class Trainer:
                 if two and (ex.pending or ex.keep):
                     E.side_join()
                 st.gen = self._last_gen
+                st.aug_params = self._aug_params if self._aug_now() is not None else None
         finally:
             ex.enabled = False
             self._adam_dev = None
@@ -1131,7 +1209,8 @@ class Trainer:
                    + list(D.engine.__dict__.get('_upool', {}).values()) + [G.grad_flat, D.grad_flat] + list(self._adam)
                    + ([self._ema] if self._ema_now() is not None else [])
                    + (list(self._clip) if (self._clip is not None and self._clip_now() != (None, None)) else [])
-                   + ([D.sn_bufs, D.sn_eff] + list(D.sn_ws) if D.engine.spectral else []))
+                   + ([D.sn_bufs, D.sn_eff] + list(D.sn_ws) if D.engine.spectral else [])
+                   + ([self._aug_counter] if st.aug_params is not None else []))
         st.ptrs = self._graph_ptrs()
         self._graphs[key] = st
         return st
