@@ -733,6 +733,49 @@ int pg_diffaug_fwd(const float* src, int ld_src, float* dst, int ld_dst, const i
  * w = ws + tx;  outside the image or inside the box -> 0;  dsrc[n,hs,w0,:] = g[n,h,w,:].  Same argument rules as pg_diffaug_fwd. */
 int pg_diffaug_bwd(const float* g, int ld_g, float* dsrc, int ld_dsrc, const int* params, int N, int H, int W, int C, void* stream);
 
+/* ---- GAN objectives on the discriminator's patch map (beyond the reference, whose objective is nn.BCELoss on a sigmoid map; the call
+ * sites are patchgan_amd's Trainer.gan_mode) -------------------------------------------------------------------------------------------
+ * A term is one mean over the n = N*HW values d[i * ld] of a one-channel patch map -- logits, or probabilities for PG_GAN_LSGAN on a
+ * sigmoid head --, its per-element value e(d) by `kind`:
+ *   PG_GAN_LSGAN       e = (d - target)^2                                           de/dd = 2 (d - target)        (F.mse_loss)
+ *   PG_GAN_HINGE_D     target == 1:  e = max(0, 1 - d)                              de/dd = -1 where 1 - d > 0, else 0
+ *                      target == 0:  e = max(0, 1 + d)                              de/dd = +1 where 1 + d > 0, else 0   (F.relu)
+ *   PG_GAN_HINGE_G     e = -d                                                       de/dd = -1
+ *   PG_GAN_BCE_LOGITS  e = max(d, 0) - d * target + log1p(exp(-|d|))                de/dd = sigmoid(d) - target
+ *                                                                                   (F.binary_cross_entropy_with_logits)
+ * A value exactly on a hinge margin contributes 0 to value and gradient (torch's relu backward).  A NaN in d gives a NaN value and a
+ * NaN gradient at that element in every kind, the hinges included.
+ *   *value = fl32(scale * sum_i e(d[i])),  scale = alpha / (Bglobal * HW) formed by the caller in double: this rank's partial of the
+ *            global mean (the sum over ranks is the loss; PG_LOSS_BCE's convention).  e is fp32 arithmetic, the sum fp64 in an order
+ *            that depends on n alone (per lane in index order, a halving tree over the workgroup, workgroup partials in index order).
+ *   g[i * ld_g] = fl32(scale) * de/dd, in fp32, seeded for a SUM all-reduce; g == NULL: value only.
+ * Up to PG_GAN_MAX_TERMS terms per call run in ONE launch, one workgroup per term, while every n <= pg_gan_loss_single_max(); a call
+ * with a larger term takes the partial-slab path instead -- one launch that writes each workgroup's partial sum into `ws` (and the
+ * gradients) and one that adds them in index order -- and needs pg_gan_loss_workspace_bytes(nterms, terms) bytes of 8-byte-aligned
+ * `ws` (0 on the one-launch path, where ws may be NULL).  No workgroup reads what another wrote in the same launch; the path and the
+ * result bits are functions of the arguments alone.
+ * PG_EINVAL before any launch, nothing written: NULL terms, nterms <= 0 or > pg_gan_loss_max_terms(), a NULL d or value, n <= 0,
+ * ld < 1, g with ld_g < 1, an unknown kind, PG_GAN_HINGE_D with a target other than 0 or 1, a NULL, misaligned or too small ws where
+ * one is needed. */
+#define PG_GAN_LSGAN 0
+#define PG_GAN_HINGE_D 1
+#define PG_GAN_HINGE_G 2
+#define PG_GAN_BCE_LOGITS 3
+#define PG_GAN_MAX_TERMS 4
+typedef struct pg_gan_term {
+    const float* d;      /* patch values, element i at d[i * ld] */
+    float* g;            /* out: gradient, element i at g[i * ld_g]; NULL = value only */
+    float* value;        /* out: one float */
+    double scale;        /* alpha / (Bglobal * HW) */
+    long n;              /* N * HW */
+    int ld, ld_g, kind;
+    float target;
+} pg_gan_term;
+int pg_gan_loss_max_terms(void);      /* PG_GAN_MAX_TERMS */
+long pg_gan_loss_single_max(void);    /* the largest n of the one-launch path */
+long pg_gan_loss_workspace_bytes(int nterms, const pg_gan_term* terms);      /* 0 for a bad list as well */
+int pg_gan_loss(int nterms, const pg_gan_term* terms, void* ws, long ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,7 @@ TUNE_S3_OFF = 0x40000        # the three Winograd GEMM families on the fp32 MFMA
 LOSS_TVERSKY, LOSS_WBCE, LOSS_MAE, LOSS_BCE = 0, 1, 2, 3
 OP_BIG2SMALL, OP_SMALL2BIG, OP_WGRAD = 0, 1, 2
 AUG_FLIP, AUG_TRANSLATION, AUG_CUTOUT = 1, 2, 4      # PG_AUG_*
+GAN_LSGAN, GAN_HINGE_D, GAN_HINGE_G, GAN_BCE_LOGITS = 0, 1, 2, 3      # PG_GAN_*
 
 _ERR = {-1: 'PG_EINVAL (bad shape / null or misaligned pointer)', -2: 'PG_EWORKSPACE (workspace too small)',
         -3: 'PG_ELAUNCH (HIP launch failed)'}
@@ -81,6 +82,15 @@ class SpectralItem(ctypes.Structure):
 
 
 SN_MAX_LAYERS = 16      # PG_SN_MAX_LAYERS
+
+
+class GanTerm(ctypes.Structure):
+    """struct pg_gan_term: one term of pg_gan_loss"""
+    _fields_ = [('d', ctypes.c_void_p), ('g', ctypes.c_void_p), ('value', ctypes.c_void_p), ('scale', ctypes.c_double),
+                ('n', ctypes.c_long), ('ld', ctypes.c_int), ('ld_g', ctypes.c_int), ('kind', ctypes.c_int), ('target', ctypes.c_float)]
+
+
+GAN_MAX_TERMS = 4       # PG_GAN_MAX_TERMS
 
 
 # name -> (restype, argtypes); mirrors include/patchgan_hip.h one to one
@@ -177,6 +187,10 @@ SIGNATURES = {
     'pg_diffaug_params': (_i, [_u64, _p, _u64, _i, _l, _i, _i, _i, _p, _p]),
     'pg_diffaug_fwd': (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _p]),
     'pg_diffaug_bwd': (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _p]),
+    'pg_gan_loss_max_terms': (_i, []),
+    'pg_gan_loss_single_max': (_l, []),
+    'pg_gan_loss_workspace_bytes': (_l, [_i, ctypes.POINTER(GanTerm)]),
+    'pg_gan_loss': (_i, [_i, ctypes.POINTER(GanTerm), _p, _l, _p]),
 }
 
 _lib = None

@@ -43,26 +43,37 @@ class _DiscFn(torch.autograd.Function):
 
 
 class Discriminator(FlatParamModule, Transferable):
-    """Discriminator(input_nc, ndf=64, n_layers=3, norm=False, norm_layer=InstanceNorm2d, spectral_norm=False) -- reference disc.py:8.
+    """Discriminator(input_nc, ndf=64, n_layers=3, norm=False, norm_layer=InstanceNorm2d, spectral_norm=False, final_act='sigmoid') --
+    reference disc.py:8.
     norm_layer: nn.InstanceNorm2d, nn.BatchNorm2d or -- for data parallelism: the global batch's statistics -- nn.SyncBatchNorm (their
     defaults), or functools.partial(nn.InstanceNorm2d, affine=True) (model.{idx}.weight / .bias of the norm modules).
     spectral_norm (opt-in, beyond the reference's constructor): every convolution as torch.nn.utils.spectral_norm(conv) leaves it --
     state_dict keys model.{i}.bias, .weight_orig (the parameter), .weight_u, .weight_v (buffers), one power iteration per
     training-mode forward(); the kernels run on W / sigma (spectral_normalize) and the gradient is mapped back to weight_orig
-    (spectral_grad_map).  Trainer.batch iterates ONCE per call and uses that one normalised weight for all of the step's D passes."""
+    (spectral_grad_map).  Trainer.batch iterates ONCE per call and uses that one normalised weight for all of the step's D passes.
+    final_act (opt-in, beyond the reference's constructor): 'sigmoid' (the reference's nn.Sigmoid) or 'none' -- forward() returns the
+    head conv's logits, what Trainer.gan_mode = 'hinge' needs and 'lsgan' / 'vanilla' accept.  nn.Sigmoid has no state: state_dict,
+    parameter order and .pth files are the same for both values."""
 
-    def __init__(self, input_nc, ndf=64, n_layers=3, norm=False, norm_layer=nn.InstanceNorm2d, spectral_norm=False):
+    def __init__(self, input_nc, ndf=64, n_layers=3, norm=False, norm_layer=nn.InstanceNorm2d, spectral_norm=False, final_act='sigmoid'):
         super().__init__()
+        if not isinstance(final_act, str) or final_act not in E.DISC_FINAL_ACTS:
+            raise ValueError(f"patchgan_amd.Discriminator: final_act must be one of {' | '.join(E.DISC_FINAL_ACTS)}, got {final_act!r}")
         if not isinstance(spectral_norm, bool):
             raise TypeError(f"patchgan_amd.Discriminator: spectral_norm must be a bool, got {spectral_norm!r}")
         kind = E.norm_kind_of(norm_layer, 'patchgan_amd.Discriminator') if norm else 'instance'
-        self.engine = E.DiscriminatorEngine(input_nc, ndf, n_layers, norm, norm_kind=kind, spectral=spectral_norm)
+        self.engine = E.DiscriminatorEngine(input_nc, ndf, n_layers, norm, norm_kind=kind, spectral=spectral_norm, final_act=final_act)
         self._param_keys = E.param_keys(self.engine.layers)
         self._init_flat(self.engine.layers, self.engine.nparams)
 
     @property
     def spectral_norm(self):
         return self.engine.spectral
+
+    @property
+    def final_act(self):
+        """'sigmoid': forward() returns probabilities (the reference); 'none': the head's logits."""
+        return self.engine.final_act
 
     def _spectral_state(self):
         if not self.engine.spectral:

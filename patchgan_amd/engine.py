@@ -1912,9 +1912,16 @@ class GeneratorEngine(_WeightPrep):
 # ------------------------------------------------------------------------------------------------
 
 
-def disc_layers(input_nc, ndf, n_layers, norm, norm_kind='instance', spectral=False):
+DISC_FINAL_ACTS = ('sigmoid', 'none')
+
+
+def disc_layers(input_nc, ndf, n_layers, norm, norm_kind='instance', spectral=False, final_act='sigmoid'):
     """Layer plan of reference Discriminator.__init__ (disc.py:19-46); keys are nn.Sequential indices (a norm is the third module
-    of its block: Conv, Tanh, norm).  spectral: every conv as torch.nn.utils.spectral_norm leaves it (weight -> weight_orig)."""
+    of its block: Conv, Tanh, norm).  spectral: every conv as torch.nn.utils.spectral_norm leaves it (weight -> weight_orig).
+    final_act: 'sigmoid' (the reference's nn.Sigmoid behind the head conv) or 'none' (the head's logits; nn.Sigmoid has no state, so
+    keys, offsets and the flat buffer are the same)."""
+    if final_act not in DISC_FINAL_ACTS:
+        raise ValueError(f"final_act must be one of {' | '.join(DISC_FINAL_ACTS)}, got {final_act!r}")
     layers = []
     idx = 0
     layers.append(LayerSpec(f'model.{idx}.weight', ndf, input_nc, 2, False, 'leakyrelu', False, bias_key=f'model.{idx}.bias'))
@@ -1929,7 +1936,7 @@ def disc_layers(input_nc, ndf, n_layers, norm, norm_kind='instance', spectral=Fa
     layers.append(LayerSpec(f'model.{idx}.weight', ndf * mult, ndf * prev, 1, False, 'tanh', norm, norm_kind=norm_kind,
                             norm_key=f'model.{idx + 2}'))
     idx += 3 if norm else 2
-    layers.append(LayerSpec(f'model.{idx}.weight', 1, ndf * mult, 1, False, 'sigmoid', False, bias_key=f'model.{idx}.bias'))
+    layers.append(LayerSpec(f'model.{idx}.weight', 1, ndf * mult, 1, False, final_act, False, bias_key=f'model.{idx}.bias'))
     if spectral:
         for l in layers:
             l.key, l.sn = l.key + '_orig', True
@@ -1954,9 +1961,10 @@ class DiscContext:
 class DiscriminatorEngine(_WeightPrep):
     _LD_MULT = 1
 
-    def __init__(self, input_nc, ndf, n_layers, norm, algo=None, norm_kind='instance', spectral=False):
+    def __init__(self, input_nc, ndf, n_layers, norm, algo=None, norm_kind='instance', spectral=False, final_act='sigmoid'):
         self.input_nc, self.ndf, self.n_layers, self.norm = input_nc, ndf, n_layers, norm
-        self._init_network(disc_layers(input_nc, ndf, n_layers, norm, layer_kind(norm_kind), spectral), norm_kind, algo)
+        self._init_network(disc_layers(input_nc, ndf, n_layers, norm, layer_kind(norm_kind), spectral, final_act), norm_kind, algo)
+        self.final_act = final_act
         self.spectral = bool(spectral)
         self.nsn = assign_spectral(self.layers)
         if self.spectral and len(self.layers) > L.SN_MAX_LAYERS:
@@ -2033,7 +2041,7 @@ class DiscriminatorEngine(_WeightPrep):
                          v_part=op.v_part(whole[li], n0) if vk is not None else (0, 0))
 
     def forward(self, flat, din, ucache=None, keep_v=False, bn=None):
-        """din: View [N,H,W,input_nc].  Returns a context; ctx.out is the sigmoid patch map View [N,h,w,1].
+        """din: View [N,H,W,input_nc].  Returns a context; ctx.out is the patch map View [N,h,w,1] (probabilities, or logits with final_act='none').
         ucache: a dict owned by the caller that lives exactly as long as the weights in `flat` stay unchanged (Trainer.batch: one
         step) -- the Winograd-transformed weights are computed once per (layer, direction) and reused by every pass that
         shares the dict.  keep_v: a backward pass with weight gradients follows (see GeneratorEngine.forward).  bn: a BNRun (BatchNorm
@@ -2106,8 +2114,11 @@ class DiscriminatorEngine(_WeightPrep):
                     dt = View.alloc(c.N, op.Hs, op.Ws, l.a, dev, bf=inner)
                     c.norm.backward(l, gflat if need_wgrad else None, g, None, c.t[li], c.stats[li], dt, L.ACT_NONE)
                     g = dt
-                dy = View.alloc(c.N, op.Hs, op.Ws, l.a, dev, bf=inner)
-                act_bwd(g, None, c.t[li], dy, L.ACT_CODES[l.act])
+                if li == last and not l.norm and L.ACT_CODES[l.act] == L.ACT_NONE:
+                    dy = g          # a logit head: its activation backward is the identity -- no launch, gout is the head's dy
+                else:
+                    dy = View.alloc(c.N, op.Hs, op.Ws, l.a, dev, bf=inner)
+                    act_bwd(g, None, c.t[li], dy, L.ACT_CODES[l.act])
             src = c.src[li]
             if need_wgrad:
                 op.wgrad(dy, src, gflat, l.p_off, gflat if l.bias_key is not None else None, l.b_off,
@@ -2226,3 +2237,50 @@ def loss_value_and_grad(p, y, tconst, mode, alpha, grad_out, loss_out, loss_slot
     `allreduce(tensor)` starts the SUM of the two global reduction terms across ranks and returns wait()."""
     h = loss_begin(p, y, tconst, beta, allreduce, need_sums=mode in (L.LOSS_TVERSKY, L.LOSS_WBCE))
     return loss_finish(h, mode, alpha, grad_out, loss_out, loss_slot, bglobal, gamma)
+
+
+GAN_MODES = ('vanilla', 'lsgan', 'hinge')
+
+
+def check_gan_mode(gan_mode, real_label, final_act):
+    """Trainer.gan_mode / real_label against the discriminator's head, validated: -> (gan_mode, float(real_label)).  ValueError for an
+    unknown mode, a real label outside (0, 1], hinge on a sigmoid head (margins at +-1 mean nothing on (0, 1)) or with a smoothed label."""
+    if not isinstance(gan_mode, str) or gan_mode not in GAN_MODES:
+        raise ValueError(f"gan_mode must be one of {' | '.join(GAN_MODES)}, not {gan_mode!r}")
+    if isinstance(real_label, bool) or not isinstance(real_label, (int, float)) or not 0.0 < float(real_label) <= 1.0:
+        raise ValueError(f"real_label must be a number in (0, 1], not {real_label!r}")
+    if gan_mode == 'hinge' and final_act != 'none':
+        raise ValueError("gan_mode = 'hinge' needs a discriminator that returns logits (Discriminator(final_act='none')): "
+                         "margins at +-1 mean nothing on a sigmoid's (0, 1)")
+    if gan_mode == 'hinge' and float(real_label) != 1.0:
+        raise ValueError(f"gan_mode = 'hinge' takes no label smoothing: real_label must be 1, not {real_label!r}")
+    return gan_mode, float(real_label)
+
+
+def gan_kinds(gan_mode, final_act):
+    """(generator term, discriminator terms): the PG_GAN_* kind of pg_gan_loss for each, None where the step keeps PG_LOSS_BCE
+    (vanilla on a sigmoid head)."""
+    if gan_mode == 'hinge':
+        return L.GAN_HINGE_G, L.GAN_HINGE_D
+    if gan_mode == 'lsgan':
+        return L.GAN_LSGAN, L.GAN_LSGAN
+    return (L.GAN_BCE_LOGITS, L.GAN_BCE_LOGITS) if final_act == 'none' else (None, None)
+
+
+def gan_loss(terms, loss_out, bglobal):
+    """Up to GAN_MAX_TERMS terms in ONE pg_gan_loss call.  terms: (d, kind, target, alpha, grad, slot) -- d a one-channel patch View,
+    grad a View of its shape or None (value only), the value alpha * sum e / (bglobal * HW) going to loss_out[slot] (this rank's partial
+    of the global mean) and the gradient seeded with the same factor.  Returns the workspace of the partial-slab path (None on the
+    one-launch path): scratch the caller keeps until the launches are enqueued."""
+    lib = L.load()
+    items = (L.GanTerm * len(terms))()
+    for it, (d, kind, target, alpha, grad, slot) in zip(items, terms):
+        assert d.C == 1 and not d.bf and (grad is None or (grad.C == 1 and grad.npix == d.npix and not grad.bf))
+        it.d, it.ld, it.n, it.kind, it.target = d.ptr(), d.ld, d.npix, kind, float(target)
+        it.scale = float(alpha) / (float(bglobal) * float(d.HW))
+        it.g, it.ld_g = (grad.ptr(), grad.ld) if grad is not None else (None, 0)
+        it.value = L.ptr(loss_out, slot)
+    nb = int(lib.pg_gan_loss_workspace_bytes(len(terms), items))
+    ws = torch.empty(nb // 8, dtype=torch.float64, device=loss_out.device) if nb else None
+    L.check(lib.pg_gan_loss(len(terms), items, ws.data_ptr() if ws is not None else None, nb, _stream()), 'pg_gan_loss')
+    return ws

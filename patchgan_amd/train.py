@@ -50,10 +50,29 @@ def spectral_norm_of(value=None):
     return value
 
 
+def disc_final_act_of(value=None):
+    """The final_act constructor argument of the discriminator from its YAML value (None, the key absent: 'sigmoid'); ValueError for
+    anything but sigmoid | none."""
+    from . import engine as E
+    value = 'sigmoid' if value is None else value
+    if not isinstance(value, str) or value not in E.DISC_FINAL_ACTS:
+        raise ValueError(f"the discriminator's final_act must be one of {' | '.join(E.DISC_FINAL_ACTS)}, not {value!r}")
+    return value
+
+
+def gan_mode_of(mode=None, real_label=None, final_act='sigmoid'):
+    """(Trainer.gan_mode, Trainer.real_label) from the YAML's train_params.gan_mode (vanilla | lsgan | hinge; absent = vanilla) and
+    train_params.real_label (a number in (0, 1]; absent = 1), checked against the discriminator's final_act as Trainer.batch checks
+    them.  ValueError for anything else, before any network is built."""
+    from . import engine as E
+    return E.check_gan_mode('vanilla' if mode is None else mode, 1.0 if real_label is None else real_label, final_act)
+
+
 def model_cfgs(mp):
     """(generator_cfg, disc_cfg) of either schema's model_params; a 'norm_layer' name, where one is given, is checked (norm_layer_of:
     ValueError before any network is built) and an absent one stays absent.  Likewise the discriminator's 'spectral_norm'
-    (model_params.discriminator.spectral_norm, flat schema: disc_spectral_norm; spectral_norm_of)."""
+    (model_params.discriminator.spectral_norm, flat schema: disc_spectral_norm; spectral_norm_of) and its 'final_act'
+    (model_params.discriminator.final_act, flat schema: disc_final_act; disc_final_act_of)."""
     if 'generator' in mp:
         gen_cfg, disc_cfg = dict(mp['generator']), dict(mp['discriminator'])
     else:                                                                         # flat legacy schema (infer.py:127-132)
@@ -65,9 +84,12 @@ def model_cfgs(mp):
                 cfg['norm_layer'] = mp[key]
         if 'disc_spectral_norm' in mp:
             disc_cfg['spectral_norm'] = mp['disc_spectral_norm']
+        if 'disc_final_act' in mp:
+            disc_cfg['final_act'] = mp['disc_final_act']
     for cfg in (gen_cfg, disc_cfg):
         norm_layer_of(cfg.get('norm_layer'))
     spectral_norm_of(disc_cfg.get('spectral_norm'))
+    disc_final_act_of(disc_cfg.get('final_act'))
     return gen_cfg, disc_cfg
 
 
@@ -96,7 +118,7 @@ def apply_train_params(trainer, train_params):
     metric_bins (Trainer.metric_bins: a power of two in 16..1024 -- score curves, average precision and the best threshold) and
     clip_grad_norm (Trainer.clip_grad_norm: a number for both networks or a two-element list [generator, discriminator] whose members
     may be null; a non-finite gradient then skips the step), diffaug / diffaug_seed (Trainer.diffaug: differentiable augmentation of
-    the discriminator's inputs; diffaug_of)."""
+    the discriminator's inputs; diffaug_of), gan_mode / real_label (Trainer.gan_mode: the adversarial objective; gan_mode_of)."""
     trainer.loss_type = train_params['loss_type']
     trainer.seg_alpha = train_params['seg_alpha']
     trainer.ema_decay = train_params.get('ema_decay', None)
@@ -107,6 +129,8 @@ def apply_train_params(trainer, train_params):
     trainer.save_best = train_params.get('save_best', None)
     trainer.metric_bins = train_params.get('metric_bins', None)
     trainer.diffaug, trainer.diffaug_seed = diffaug_of(train_params.get('diffaug', None), train_params.get('diffaug_seed', None))
+    trainer.gan_mode, trainer.real_label = gan_mode_of(train_params.get('gan_mode', None), train_params.get('real_label', None),
+                                                       trainer.discriminator.final_act)
 
 
 def diffaug_of(policy=None, seed=None):
@@ -156,6 +180,8 @@ def patchgan_train(argv=None):
     with open(args.config_file, 'r') as infile:
         config = yaml.safe_load(infile)
     dataset_params, train_paths, val_paths, split, gen_cfg, disc_cfg = parse_config(config)
+    # (the objective against the discriminator's head: a ValueError here, before any data set or network is built)
+    gan_mode_of(config['train_params'].get('gan_mode'), config['train_params'].get('real_label'), disc_final_act_of(disc_cfg.get('final_act')))
 
     size = dataset_params.get('size', 256)
     augmentation = dataset_params.get('augmentation', 'randomcrop')
@@ -199,7 +225,8 @@ def patchgan_train(argv=None):
                      norm_layer=norm_layer_of(gen_cfg.get('norm_layer'))).to(device)
     discriminator = Discriminator(in_channels + out_channels, disc_cfg['filters'], norm=disc_cfg.get('norm', False),
                                   n_layers=disc_cfg['n_layers'], norm_layer=norm_layer_of(disc_cfg.get('norm_layer')),
-                                  spectral_norm=spectral_norm_of(disc_cfg.get('spectral_norm'))).to(device)
+                                  spectral_norm=spectral_norm_of(disc_cfg.get('spectral_norm')),
+                                  final_act=disc_final_act_of(disc_cfg.get('final_act'))).to(device)
     if world > 1:
         import torch.distributed as dist
         dist.broadcast(generator.flat, 0)          # every rank starts from rank 0's initial weights

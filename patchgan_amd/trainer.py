@@ -23,6 +23,9 @@ Per-step schedule (reference trainer.py:50-115):
    With Trainer.diffaug set, a training step's D passes read T(din), a per-sample flip / translation / cutout of the input buffer
    made by two moves (the real half ahead of the generator forward, the fake half behind it), and the gradient returns to G through
    the adjoint move; the draws come from a device-resident counter-based stream, so every launch mode sees the same tables.
+   With Trainer.gan_mode / real_label set, or a Discriminator(final_act='none'), the three BCE terms above become the terms of the chosen
+   objective (least squares, hinge, BCE with logits), evaluated by pg_gan_loss: one launch for the generator step's term, one for the
+   discriminator step's two.
 
 Data parallelism: one process per GPU (torch.distributed, backend "nccl" = RCCL).  InstanceNorm is per sample,
 so the only exchanges are the SUM all-reduce of the flat gradient buffers and of two loss-normalisation terms
@@ -206,6 +209,20 @@ class Trainer:
     # either): a resumed run starts the stream again.
     diffaug = None
     diffaug_seed = 0         # a stream of its own, independent of dropout's
+
+    # The adversarial objective (opt-in, beyond the reference, whose objective is nn.BCELoss on a sigmoid patch map): 'vanilla' with
+    # real_label = 1 on a sigmoid discriminator = off -- the same launches, buffers, bits and kind key.  d_f = D(T(x | G(x))),
+    # d_r = D(T(x | y)), means over all values of a term, r = real_label (the discriminator's real term only: one-sided smoothing),
+    # disc = (real + fake) / 2 and gen = seg + gdisc as in the reference:
+    #   'vanilla'   sigmoid D: BCE(d_f, 1) | BCE(d_r, r), BCE(d_f, 0) (today's kernels);  logit D (Discriminator(final_act='none')):
+    #               the same objective as F.binary_cross_entropy_with_logits -- no saturating division by p (1 - p)
+    #   'lsgan'     mean (d_f - 1)^2 | mean (d_r - r)^2, mean d_f^2; either head (on a sigmoid D the gradient goes back through it)
+    #   'hinge'     -mean d_f | mean max(0, 1 - d_r), mean max(0, 1 + d_f); logit D only, r = 1 only (what spectral normalisation
+    #               was published with)
+    # Everything but vanilla on a sigmoid D is ONE launch per group of terms (engine.gan_loss -> pg_gan_loss: the generator step's term,
+    # then the discriminator step's two terms together) in place of two launches per term.  Checked at the top of batch(): ValueError.
+    gan_mode = 'vanilla'
+    real_label = 1.0
 
     # Segmentation metrics of evaluation passes (opt-in, beyond the reference): None = off -- no launch, no buffer, no key, file or
     # printed line.  True: every batch(train=False) adds ONE launch beside its segmentation loss (engine.seg_confusion: the confusion
@@ -399,6 +416,12 @@ class Trainer:
             raise RuntimeError("read_diffaug_params(): no training step with Trainer.diffaug set has run")
         return self._aug_params.cpu().numpy().copy()
 
+    # -------------------------------------------------------------------------------------- the adversarial objective
+    def _gan_now(self):
+        """(gan_mode, real_label, the discriminator's final_act) of the next step, validated (ValueError)."""
+        fa = self.discriminator.final_act
+        return E.check_gan_mode(self.gan_mode, self.real_label, fa) + (fa,)
+
     # -------------------------------------------------------------------------------------- the generator's weight average
     @property
     def ema_generator(self):
@@ -585,6 +608,7 @@ class Trainer:
     def batch(self, x, y, train=False):
         t_host0 = time.perf_counter()
         G, D = self.generator, self.discriminator
+        self._gan_now()           # (ValueError before anything is launched)
         if not train and self.metric_bins is not None:
             self._metric_bins()   # (an evaluation step: ValueError before anything is launched)
         x, y, u8, N, H, W, Cin, Cout = self._inputs(x, y)
@@ -706,6 +730,9 @@ class Trainer:
             din_d, real_d, fake_d, aug_params = din, real, fake, None
 
         losses = torch.empty(4, dtype=torch.float32, device=dev)   # seg, gdisc, real*0.5, fake*0.5 (each written by its loss kernel)
+        # the adversarial objective: kind_g / kind_d None = nn.BCELoss on the sigmoid map (the reference), else the terms of pg_gan_loss
+        gan_mode, real_label, d_act = self._gan_now()
+        kind_g, kind_d = E.gan_kinds(gan_mode, d_act)
         allred = dist.all_reduce_side if dist.on else None
 
         # ---- generator step
@@ -778,7 +805,10 @@ class Trainer:
                       self.tversky_gamma)                                                     # trainer.py:71-82
         o = dc.out
         gd = E.View.alloc(o.N, o.H, o.W, 1, dev) if train else None
-        E.loss_value_and_grad(o, None, 1.0, L.LOSS_BCE, 1.0, gd, losses, 1, Bglobal)          # trainer.py:84
+        if kind_g is None:
+            E.loss_value_and_grad(o, None, 1.0, L.LOSS_BCE, 1.0, gd, losses, 1, Bglobal)      # trainer.py:84
+        else:
+            E.gan_loss([(o, kind_g, 1.0, 1.0, gd, 1)], losses, Bglobal)                       # (the generator's target is never smoothed)
         g_reducer, late_adam_g = None, False
         self._mark('D(fake) fwd + losses done')
         if train:
@@ -829,10 +859,15 @@ class Trainer:
             self._adam_step('g')                                                              # trainer.py:90
         o2 = dc2.out
         god = E.View.alloc(o2.N, o2.H, o2.W, 1, dev) if train else None
-        E.loss_value_and_grad(o2.samples(0, N), None, 1.0, L.LOSS_BCE, 0.5, god.samples(0, N) if train else None,
-                              losses, 2, Bglobal)                                             # loss_real
-        E.loss_value_and_grad(o2.samples(N, N), None, 0.0, L.LOSS_BCE, 0.5, god.samples(N, N) if train else None,
-                              losses, 3, Bglobal)                                             # loss_fake
+        if kind_d is None:
+            E.loss_value_and_grad(o2.samples(0, N), None, real_label, L.LOSS_BCE, 0.5, god.samples(0, N) if train else None,
+                                  losses, 2, Bglobal)                                         # loss_real
+            E.loss_value_and_grad(o2.samples(N, N), None, 0.0, L.LOSS_BCE, 0.5, god.samples(N, N) if train else None,
+                                  losses, 3, Bglobal)                                         # loss_fake
+        else:
+            # loss_real and loss_fake, the two sample halves of the one 2N map, as two terms of ONE launch
+            E.gan_loss([(o2.samples(0, N), kind_d, real_label, 0.5, god.samples(0, N) if train else None, 2),
+                        (o2.samples(N, N), kind_d, 0.0, 0.5, god.samples(N, N) if train else None, 3)], losses, Bglobal)
         wait_losses = None
         if dist.on:
             # the step's loss scalars for logging: seg is already global for tversky, the BCE / MAE terms are per-rank partial
@@ -996,7 +1031,13 @@ class Trainer:
                 # (an evaluation step with the metrics launch is another kind of step than one without: never timed against each other)
                 # (likewise one with the histogram launch of metric_bins)
                 ((float(self.metric_threshold), self.metric_bins) if self.metric_bins is not None else float(self.metric_threshold))
-                if (self.metrics and not train) else None)
+                if (self.metrics and not train) else None) + self._gan_key()
+
+    def _gan_key(self):
+        # (the objective's kinds, targets and scales are launch arguments: a captured step holds what it was captured with.  The
+        #  default: the key is the one without the feature)
+        gan = self._gan_now()
+        return (gan,) if gan != ('vanilla', 1.0, 'sigmoid') else ()
 
     def _launch_mode(self, key, train):
         """'eager1' (launch by launch, one stream) | 'eager2' (launch by launch, two streams) | 'graph' (replay) for this step of kind
