@@ -384,7 +384,10 @@ int pg_dropout_mask(float* mask, long nelem, float drop_p, uint64_t seed, void* 
  * discriminator step's one pass over din[2N], which the reference runs as two calls (trainer.py:97,99).
  *   coef[(s*C + c)*4 + {0..3}] = (mean, rstd, scale = weight*rstd, shift = bias - mean*scale);  out = drop(act(y*scale + shift)).
  *   bstat[(s*C + c)*2 + {0,1}] = (batch mean, unbiased batch variance), fp64 (may be NULL): the input of the running update.
- * Statistics: fp64 partial sums per (sample, pixel chunk, channel), merged in a fixed order (bit-reproducible).  Every
+ * Statistics: fp64 partial sums per (sample, pixel chunk, channel), merged in a fixed order (bit-reproducible).  Where a call is one
+ * kernel (planes the chunk plan does not split) the variance is two passes, a sum of (y - mean)^2.  Everywhere else -- the chunked
+ * path, pg_batchnorm_stats, `part`, the split form -- it is E[y^2] - mean^2 in fp64, clamped at 0: rstd carries a relative
+ * 2^-48 (1 + mean^2 / (var + eps)) there on top of its fp32 rounding.  Every
  * (N / nseg) * HW must be > 1 (torch raises "Expected more than 1 value per channel when training" there).  Dropout as
  * pg_instnorm_act_fwd.  ws: pg_batchnorm_workspace_bytes -- REQUIRED: unlike the InstanceNorm entry points, pg_batchnorm_act_fwd,
  * pg_batchnorm_stats (from y; with `part` it takes none) and pg_batchnorm_act_bwd do not fall back: a NULL or smaller workspace

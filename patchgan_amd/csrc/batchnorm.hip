@@ -679,8 +679,10 @@ extern "C" {
 
 size_t pg_batchnorm_workspace_bytes(int N, int HW, int C, int nseg) {
     if (bad_geom(N, HW, C, nseg, 1)) return 0;
-    const BnPlan a = bn_plan(N, HW, C, 4), b = bn_plan(N, HW, C, 1);
-    return std::max(a.part_bytes, b.part_bytes) + bcoef_bytes(nseg, C);
+    const BnPlan b = bn_plan(N, HW, C, 1);
+    // fewer than 4 channels have no VEC 4 plan: its channel-group count is 0, and bn_plan divides by it
+    const size_t a = C >= 4 ? bn_plan(N, HW, C, 4).part_bytes : 0;
+    return std::max(a, b.part_bytes) + bcoef_bytes(nseg, C);
 }
 
 // One rule for the three entry points that take a workspace, whatever kernel the views select (the one-workgroup kernels of small
