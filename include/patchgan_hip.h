@@ -592,6 +592,27 @@ int pg_adam_clip_step(float* p, const float* g, float* m, float* v, float* ema, 
 int pg_adam_clip_step_dev(float* p, const float* g, float* m, float* v, float* ema, long n, float beta1, float beta2, float eps,
                           const float* scalars, float ema_decay, const pg_grad_stat* stat, void* stream);
 
+/* ---- decoupled weight decay (beyond the reference, whose users swap optim.Adam for optim.AdamW; the call site is patchgan_amd's
+ * Trainer._adam_step with Trainer.weight_decay set) ---------------------------------------------------------------------------------
+ * Per element: p0 = p * decay_mul as ONE fp32 product, then exactly the update of pg_adam_step on (p0, g * coef, m, v), then the
+ * average of pg_adam_ema_step from the stored p.  decay_mul is formed by the caller in double and rounded once,
+ * (float)(1.0 - (double)lr * weight_decay): torch.optim.AdamW's param.mul_(1 - lr * weight_decay) ahead of the moment updates -- the
+ * decay uses lr, not lr / bc1 --, so m and v do not depend on it.  One multiply and no memory access more: 28 / 36 bytes per
+ * parameter as without it.
+ * ema == NULL: no weight average (ema_decay is not read).  stat == NULL: no clipping (coef = 1, no skip); otherwise `stat` is what
+ * pg_grad_norm wrote, and stat->apply == 0 ends the kernel before it loads anything else: p (its decay included), m, v and ema keep
+ * their bits.  All four combinations are legal.  With decay_mul == 1 the results are bit-identical to pg_adam_step /
+ * pg_adam_ema_step / pg_adam_clip_step (and their _dev forms) for the same (ema, stat).
+ * The _dev form reads scalars[0] = lr / bc1, scalars[1] = sqrt(bc2), scalars[2] = decay_mul from device memory (pg_adam_step_dev).
+ * PG_EINVAL before any launch, nothing touched: the pointer and alignment rules of pg_adam_step (ema and stat, where given, 16-byte
+ * aligned as well; bc1, sqrt_bc2 > 0; a NULL scalars); decay_mul NaN or outside (0, 1]; beta1 or beta2 NaN or outside [0, 1);
+ * with ema != NULL an ema_decay NaN or outside [0, 1). */
+int pg_adamw_step(float* p, const float* g, float* m, float* v, float* ema, long n, float lr, float beta1, float beta2, float eps,
+                  float bc1, float sqrt_bc2, float decay_mul, float ema_decay, const pg_grad_stat* stat, void* stream);
+int pg_adamw_step_dev(float* p, const float* g, float* m, float* v, float* ema, long n, float beta1, float beta2, float eps,
+                      const float* scalars /* [0] lr / bc1, [1] sqrt(bc2), [2] decay_mul */, float ema_decay,
+                      const pg_grad_stat* stat, void* stream);
+
 /* ---- spectral normalisation of conv weights (beyond the reference, whose users wrap each nn.Conv2d of the discriminator in
  * torch.nn.utils.spectral_norm; the call sites are patchgan_amd's Discriminator(spectral_norm=True) and Trainer._enqueue_step /
  * _adam_step) --------------------------------------------------------------------------------------------------------------------

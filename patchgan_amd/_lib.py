@@ -167,6 +167,8 @@ SIGNATURES = {
     'pg_grad_norm': (_i, [_p, _l, _d, _p, _l, _p, _p]),
     'pg_adam_clip_step': (_i, [_p, _p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _f, _f, _p, _p]),
     'pg_adam_clip_step_dev': (_i, [_p, _p, _p, _p, _p, _l, _f, _f, _f, _p, _f, _p, _p]),
+    'pg_adamw_step': (_i, [_p, _p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _f, _f, _f, _p, _p]),
+    'pg_adamw_step_dev': (_i, [_p, _p, _p, _p, _p, _l, _f, _f, _f, _p, _f, _p, _p]),
     'pg_spectral_workspace_bytes': (_l, [_i, ctypes.POINTER(SpectralItem)]),
     'pg_spectral_fwd': (_i, [_i, ctypes.POINTER(SpectralItem), _p, _p, _l, _p, _l, _p]),
     'pg_spectral_bwd': (_i, [_i, ctypes.POINTER(SpectralItem), _p, _l, _p, _l, _p]),

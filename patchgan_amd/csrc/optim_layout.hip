@@ -36,10 +36,20 @@ __device__ __forceinline__ float clip_one(float g, float coef) {
     return g;
 }
 
-template <bool DEV, bool EMA, bool CLIP = false>
+// WD: decoupled weight decay (pg_adamw_step*), p0 = p * decay_mul as ONE fp32 product ahead of the moment updates -- what torch's
+// single-tensor AdamW does with param.mul_(1 - lr * weight_decay) --, then adam_one on p0: one multiply, no memory access; m and v do
+// not see it.  The caller forms decay_mul in double and rounds once; the DEV form reads it as scal[2].  decay_mul == 1: p * 1.f == p,
+// the results of the forms without it.  Behind the CLIP early return: a skipped step does not decay either.
+template <bool WD>
+__device__ __forceinline__ float decay_one(float p, float decay_mul) {
+    if constexpr (WD) return p * decay_mul;
+    return p;
+}
+
+template <bool DEV, bool EMA, bool CLIP = false, bool WD = false>
 __global__ void k_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                        long n, float lr_over_bc1, float beta1, float beta2, float eps, float sqrt_bc2, const float* __restrict__ scal,
-                       float* __restrict__ ema, float ema_decay, const pg_grad_stat* __restrict__ stat = nullptr) {
+                       float* __restrict__ ema, float ema_decay, const pg_grad_stat* __restrict__ stat = nullptr, float decay_mul = 1.f) {
     float coef = 1.f;
     if constexpr (CLIP) {
         if (stat->apply == 0u) return;
@@ -48,6 +58,7 @@ __global__ void k_adam(float* __restrict__ p, const float* __restrict__ g, float
     if constexpr (DEV) {
         lr_over_bc1 = scal[0];
         sqrt_bc2 = scal[1];
+        if constexpr (WD) decay_mul = scal[2];
     }
     const float c = 1.f - ema_decay;
     const long n4 = n >> 2;
@@ -57,6 +68,10 @@ __global__ void k_adam(float* __restrict__ p, const float* __restrict__ g, float
         float4 mm = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
         float4 ee = {0.f, 0.f, 0.f, 0.f};
         if constexpr (EMA) ee = reinterpret_cast<float4*>(ema)[i];
+        pp.x = decay_one<WD>(pp.x, decay_mul);
+        pp.y = decay_one<WD>(pp.y, decay_mul);
+        pp.z = decay_one<WD>(pp.z, decay_mul);
+        pp.w = decay_one<WD>(pp.w, decay_mul);
         adam_one(pp.x, clip_one<CLIP>(gg.x, coef), mm.x, vv.x, lr_over_bc1, beta1, beta2, eps, sqrt_bc2);
         adam_one(pp.y, clip_one<CLIP>(gg.y, coef), mm.y, vv.y, lr_over_bc1, beta1, beta2, eps, sqrt_bc2);
         adam_one(pp.z, clip_one<CLIP>(gg.z, coef), mm.z, vv.z, lr_over_bc1, beta1, beta2, eps, sqrt_bc2);
@@ -71,8 +86,10 @@ __global__ void k_adam(float* __restrict__ p, const float* __restrict__ g, float
         if constexpr (EMA) reinterpret_cast<float4*>(ema)[i] = ee;
     }
     for (long i = (n4 << 2) + blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += stride) {
-        adam_one(p[i], clip_one<CLIP>(g[i], coef), m[i], v[i], lr_over_bc1, beta1, beta2, eps, sqrt_bc2);
-        if constexpr (EMA) ema_one<EMA>(ema[i], p[i], c);
+        float pi = decay_one<WD>(p[i], decay_mul);
+        adam_one(pi, clip_one<CLIP>(g[i], coef), m[i], v[i], lr_over_bc1, beta1, beta2, eps, sqrt_bc2);
+        p[i] = pi;
+        if constexpr (EMA) ema_one<EMA>(ema[i], pi, c);
     }
 }
 
@@ -306,6 +323,33 @@ int blocks_for(long total) {
     return (int)b;
 }
 
+// (a NaN fails every comparison below)
+bool adamw_args_ok(float beta1, float beta2, float decay_mul, const float* ema, float ema_decay) {
+    if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f)) return false;
+    if (!(decay_mul > 0.f && decay_mul <= 1.f)) return false;
+    return !ema || (ema_decay >= 0.f && ema_decay < 1.f);
+}
+
+template <bool DEV>
+void adamw_launch(float* p, const float* g, float* m, float* v, float* ema, long n, float lr_over_bc1, float beta1, float beta2,
+                         float eps, float sqrt_bc2, const float* scalars, float decay_mul, float ema_decay, const pg_grad_stat* stat,
+                         void* stream) {
+    const dim3 grid(blocks_for(n / 4 + 1)), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    if (ema && stat)
+        hipLaunchKernelGGL((k_adam<DEV, true, true, true>), grid, block, 0, s, p, g, m, v, n, lr_over_bc1, beta1, beta2, eps, sqrt_bc2, scalars,
+                           ema, ema_decay, stat, decay_mul);
+    else if (ema)
+        hipLaunchKernelGGL((k_adam<DEV, true, false, true>), grid, block, 0, s, p, g, m, v, n, lr_over_bc1, beta1, beta2, eps, sqrt_bc2, scalars,
+                           ema, ema_decay, (const pg_grad_stat*)nullptr, decay_mul);
+    else if (stat)
+        hipLaunchKernelGGL((k_adam<DEV, false, true, true>), grid, block, 0, s, p, g, m, v, n, lr_over_bc1, beta1, beta2, eps, sqrt_bc2, scalars,
+                           (float*)nullptr, 0.f, stat, decay_mul);
+    else
+        hipLaunchKernelGGL((k_adam<DEV, false, false, true>), grid, block, 0, s, p, g, m, v, n, lr_over_bc1, beta1, beta2, eps, sqrt_bc2, scalars,
+                           (float*)nullptr, 0.f, (const pg_grad_stat*)nullptr, decay_mul);
+}
+
 }  // namespace
 
 extern "C" {
@@ -393,6 +437,26 @@ int pg_adam_clip_step_dev(float* p, const float* g, float* m, float* v, float* e
     else
         hipLaunchKernelGGL((k_adam<true, false, true>), dim3(blocks_for(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, 0.f, beta1,
                            beta2, eps, 0.f, scalars, (float*)nullptr, 0.f, stat);
+    return pg_launch_status();
+}
+
+int pg_adamw_step(float* p, const float* g, float* m, float* v, float* ema, long n, float lr, float beta1, float beta2, float eps,
+                  float bc1, float sqrt_bc2, float decay_mul, float ema_decay, const pg_grad_stat* stat, void* stream) {
+    if (!p || !g || !m || !v || n <= 0 || !(bc1 > 0.f) || !(sqrt_bc2 > 0.f)) return PG_EINVAL;
+    if (!adamw_args_ok(beta1, beta2, decay_mul, ema, ema_decay)) return PG_EINVAL;
+    const uintptr_t al = (uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema | (uintptr_t)stat;
+    if (al & 15) return PG_EINVAL;
+    adamw_launch<false>(p, g, m, v, ema, n, lr / bc1, beta1, beta2, eps, sqrt_bc2, nullptr, decay_mul, ema_decay, stat, stream);
+    return pg_launch_status();
+}
+
+int pg_adamw_step_dev(float* p, const float* g, float* m, float* v, float* ema, long n, float beta1, float beta2, float eps,
+                      const float* scalars, float ema_decay, const pg_grad_stat* stat, void* stream) {
+    if (!p || !g || !m || !v || !scalars || n <= 0) return PG_EINVAL;
+    if (!adamw_args_ok(beta1, beta2, 1.f, ema, ema_decay)) return PG_EINVAL;      // (decay_mul lives on the device: scalars[2])
+    const uintptr_t al = (uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema | (uintptr_t)stat;
+    if (al & 15) return PG_EINVAL;
+    adamw_launch<true>(p, g, m, v, ema, n, 0.f, beta1, beta2, eps, 0.f, scalars, 1.f, ema_decay, stat, stream);
     return pg_launch_status();
 }
 

@@ -958,10 +958,12 @@ def adam_step(p, g, m, v, step, lr, beta1=0.9, beta2=0.999, eps=1e-8):
                                   eps, bc1, math.sqrt(bc2), _stream()), 'pg_adam_step')
 
 
-def adam_scalars(step, lr, beta1=0.9, beta2=0.999):
-    """(lr / bc1, sqrt(bc2)) as the float32 values pg_adam_step forms from its arguments: what pg_adam_step_dev reads from device memory."""
+def adam_scalars(step, lr, beta1=0.9, beta2=0.999, weight_decay=None):
+    """(lr / bc1, sqrt(bc2)) as the float32 values pg_adam_step forms from its arguments: what pg_adam_step_dev reads from device memory.
+    With a weight_decay also decay_mul(lr, weight_decay), the third float pg_adamw_step_dev reads."""
     bc1 = np.float32(1.0 - beta1 ** step)
-    return np.float32(lr) / bc1, np.float32(math.sqrt(1.0 - beta2 ** step))
+    sc = np.float32(lr) / bc1, np.float32(math.sqrt(1.0 - beta2 ** step))
+    return sc if weight_decay is None else sc + (np.float32(decay_mul(lr, weight_decay)),)
 
 
 def adam_step_dev(p, g, m, v, scalars, beta1=0.9, beta2=0.999, eps=1e-8):
@@ -1046,6 +1048,78 @@ def adam_clip_step_dev(p, g, m, v, ema, scalars, stat, ema_decay=None, beta1=0.9
     L.check(L.load().pg_adam_clip_step_dev(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ema.data_ptr() if ema is not None else None,
                                            p.numel(), beta1, beta2, eps, scalars.data_ptr(), ema_decay if ema is not None else 0.0,
                                            stat.data_ptr(), _stream()), 'pg_adam_clip_step_dev')
+
+
+_BETAS_MSG = "betas must be None, a pair (beta1, beta2) of floats in [0, 1) or a pair of such pairs (generator, discriminator), not {!r}"
+_WD_MSG = "weight_decay must be None, a finite number >= 0 or a pair of them (generator, discriminator; members may be None), not {!r}"
+
+
+def _is_number(x):
+    return not isinstance(x, bool) and isinstance(x, (int, float, np.floating, np.integer))
+
+
+def check_betas(value):
+    """Trainer.betas as ((gen_beta1, gen_beta2), (disc_beta1, disc_beta2)), or ValueError.  `value`: None (torch.optim.Adam's
+    (0.9, 0.999) for both networks), one pair for both, or a pair of pairs; every beta a float in [0, 1) that stays below 1 as a
+    float32 (what pg_adam_step* and pg_adamw_step* take)."""
+    def pair(x):
+        if not isinstance(x, (tuple, list)) or len(x) != 2 or not all(_is_number(b) for b in x):
+            raise ValueError(_BETAS_MSG.format(value))
+        x = tuple(float(b) for b in x)
+        if not all(0.0 <= b < 1.0 and float(np.float32(b)) < 1.0 for b in x):          # (a NaN fails the comparison)
+            raise ValueError(_BETAS_MSG.format(value))
+        return x
+    if value is None:
+        return (0.9, 0.999), (0.9, 0.999)
+    if isinstance(value, (tuple, list)) and len(value) == 2 and all(isinstance(x, (tuple, list)) for x in value):
+        return pair(value[0]), pair(value[1])
+    both = pair(value)
+    return both, both
+
+
+def check_weight_decay(value):
+    """Trainer.weight_decay as (gen, disc), each None (the network takes the entry points without a decay) or a float > 0, or
+    ValueError.  `value`: None, one finite number >= 0 for both networks, or a pair whose members may be None; 0 counts as None."""
+    def one(x):
+        if not _is_number(x) or not (0.0 <= float(x) < float('inf')):          # (a NaN fails the comparison)
+            raise ValueError(_WD_MSG.format(value))
+        return float(x) or None
+    if value is None:
+        return None, None
+    if isinstance(value, (tuple, list)):
+        if len(value) != 2:
+            raise ValueError(_WD_MSG.format(value))
+        return tuple(None if x is None else one(x) for x in value)
+    x = one(value)
+    return x, x
+
+
+def decay_mul(lr, weight_decay):
+    """1 - lr * weight_decay formed in double: torch.optim.AdamW's param.mul_(1 - lr * weight_decay); pg_adamw_step takes it rounded
+    once to a float32, which must land in (0, 1].  ValueError for lr * weight_decay >= 1 (the decay would flip or zero the weights)."""
+    dm = 1.0 - float(lr) * float(weight_decay)
+    if not (dm > 0.0 and 0.0 < float(np.float32(dm)) <= 1.0):
+        raise ValueError(f"lr * weight_decay must be < 1 (lr = {lr!r}, weight_decay = {weight_decay!r})")
+    return dm
+
+
+def adamw_step(p, g, m, v, step, lr, weight_decay, ema=None, ema_decay=None, stat=None, beta1=0.9, beta2=0.999, eps=1e-8):
+    """adam_step on p * (1 - lr * weight_decay): torch.optim.AdamW's decoupled decay, one more multiply in the same pass.  ema / stat
+    as adam_ema_step / adam_clip_step take them, each optional."""
+    bc1 = 1.0 - beta1 ** step
+    bc2 = 1.0 - beta2 ** step
+    L.check(L.load().pg_adamw_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ema.data_ptr() if ema is not None else None,
+                                   p.numel(), lr, beta1, beta2, eps, bc1, math.sqrt(bc2), decay_mul(lr, weight_decay),
+                                   ema_decay if ema is not None else 0.0, stat.data_ptr() if stat is not None else None, _stream()),
+            'pg_adamw_step')
+
+
+def adamw_step_dev(p, g, m, v, scalars, ema=None, ema_decay=None, stat=None, beta1=0.9, beta2=0.999, eps=1e-8):
+    """adamw_step with lr / bc1, sqrt(bc2) and the decay multiplier taken from the device tensor `scalars` (3 floats: adam_scalars with a
+    weight_decay)."""
+    L.check(L.load().pg_adamw_step_dev(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ema.data_ptr() if ema is not None else None,
+                                       p.numel(), beta1, beta2, eps, scalars.data_ptr(), ema_decay if ema is not None else 0.0,
+                                       stat.data_ptr() if stat is not None else None, _stream()), 'pg_adamw_step_dev')
 
 
 def seg_confusion(p, y, threshold, counts):

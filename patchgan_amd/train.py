@@ -68,6 +68,37 @@ def gan_mode_of(mode=None, real_label=None, final_act='sigmoid'):
     return E.check_gan_mode('vanilla' if mode is None else mode, 1.0 if real_label is None else real_label, final_act)
 
 
+def optimizer_of(betas=None, weight_decay=None, save_optimizer=None, lrs=None):
+    """(Trainer.betas, Trainer.weight_decay, Trainer.save_optimizer) from the YAML's train_params.betas -- a two-element list
+    [beta1, beta2] for both networks or a mapping {gen: [..], disc: [..]} (a missing member: Adam's (0.9, 0.999)) --,
+    train_params.weight_decay -- a number or a two-element list [generator, discriminator] whose members may be null -- and
+    train_params.save_optimizer (true | false); absent = off.  With `lrs` = (gen, disc) the decay is also held against the learning
+    rates (lr * weight_decay < 1).  ValueError for anything else, before any network is built."""
+    from . import engine as E
+    if isinstance(betas, dict):
+        if not betas or set(betas) - {'gen', 'disc'}:
+            raise ValueError(f"betas must be a list [beta1, beta2] or a mapping with the keys gen / disc, not {betas!r}")
+        betas = tuple(tuple(b) if isinstance(b, list) else ((0.9, 0.999) if b is None else b)
+                      for b in (betas.get('gen'), betas.get('disc')))
+    elif isinstance(betas, list):
+        betas = tuple(tuple(b) if isinstance(b, list) else b for b in betas)
+    weight_decay = tuple(weight_decay) if isinstance(weight_decay, list) else weight_decay
+    E.check_betas(betas)
+    wd = E.check_weight_decay(weight_decay)
+    if lrs is not None:
+        for lr, w in zip(lrs, wd):
+            if w is not None:
+                E.decay_mul(lr, w)
+    if save_optimizer is not None and not isinstance(save_optimizer, bool):
+        raise ValueError(f"save_optimizer must be true or false, not {save_optimizer!r}")
+    return betas, weight_decay, (True if save_optimizer else None)
+
+
+def _optimizer_of_params(tp):
+    return optimizer_of(tp.get('betas', None), tp.get('weight_decay', None), tp.get('save_optimizer', None),
+                        (tp.get('gen_learning_rate', 1e-3), tp.get('disc_learning_rate', 1e-3)))
+
+
 def model_cfgs(mp):
     """(generator_cfg, disc_cfg) of either schema's model_params; a 'norm_layer' name, where one is given, is checked (norm_layer_of:
     ValueError before any network is built) and an absent one stays absent.  Likewise the discriminator's 'spectral_norm'
@@ -118,7 +149,9 @@ def apply_train_params(trainer, train_params):
     metric_bins (Trainer.metric_bins: a power of two in 16..1024 -- score curves, average precision and the best threshold) and
     clip_grad_norm (Trainer.clip_grad_norm: a number for both networks or a two-element list [generator, discriminator] whose members
     may be null; a non-finite gradient then skips the step), diffaug / diffaug_seed (Trainer.diffaug: differentiable augmentation of
-    the discriminator's inputs; diffaug_of), gan_mode / real_label (Trainer.gan_mode: the adversarial objective; gan_mode_of)."""
+    the discriminator's inputs; diffaug_of), gan_mode / real_label (Trainer.gan_mode: the adversarial objective; gan_mode_of), betas /
+    weight_decay / save_optimizer (Trainer.betas, Trainer.weight_decay: Adam's betas and AdamW's decoupled decay per network;
+    Trainer.save_optimizer: optimizer_ep_*.pth beside the checkpoints, for an exact resume; optimizer_of)."""
     trainer.loss_type = train_params['loss_type']
     trainer.seg_alpha = train_params['seg_alpha']
     trainer.ema_decay = train_params.get('ema_decay', None)
@@ -131,6 +164,7 @@ def apply_train_params(trainer, train_params):
     trainer.diffaug, trainer.diffaug_seed = diffaug_of(train_params.get('diffaug', None), train_params.get('diffaug_seed', None))
     trainer.gan_mode, trainer.real_label = gan_mode_of(train_params.get('gan_mode', None), train_params.get('real_label', None),
                                                        trainer.discriminator.final_act)
+    trainer.betas, trainer.weight_decay, trainer.save_optimizer = _optimizer_of_params(train_params)
 
 
 def diffaug_of(policy=None, seed=None):
@@ -182,6 +216,7 @@ def patchgan_train(argv=None):
     dataset_params, train_paths, val_paths, split, gen_cfg, disc_cfg = parse_config(config)
     # (the objective against the discriminator's head: a ValueError here, before any data set or network is built)
     gan_mode_of(config['train_params'].get('gan_mode'), config['train_params'].get('real_label'), disc_final_act_of(disc_cfg.get('final_act')))
+    _optimizer_of_params(config['train_params'])      # (likewise the optimizer's settings)
 
     size = dataset_params.get('size', 256)
     augmentation = dataset_params.get('augmentation', 'randomcrop')

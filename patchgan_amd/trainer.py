@@ -205,8 +205,8 @@ class Trainer:
     # from (diffaug_seed, a step count kept in a device word, the GLOBAL sample index): a captured step replays with fresh draws, and
     # the ranks of a data-parallel job draw what the single process draws for the large batch.  The generator's output, the segmentation
     # loss, the metrics and evaluation steps stay on the un-augmented tensors; evaluation steps do not advance the count.
-    # read_diffaug_params() returns the last step's table.  Neither the count nor the seed is checkpointed (dropout's stream is not
-    # either): a resumed run starts the stream again.
+    # read_diffaug_params() returns the last step's table.  The count is checkpointed with save_optimizer (as is the step number
+    # dropout's seeds derive from); without it a resumed run starts the stream again.
     diffaug = None
     diffaug_seed = 0         # a stream of its own, independent of dropout's
 
@@ -223,6 +223,26 @@ class Trainer:
     # then the discriminator step's two terms together) in place of two launches per term.  Checked at the top of batch(): ValueError.
     gan_mode = 'vanilla'
     real_label = 1.0
+
+    # The optimizer's settings (opt-in, beyond the reference, whose optimizers are optim.Adam(lr, betas=(0.9, 0.999))): None = off -- the
+    # same launches with the same arguments, the same kind key, the same files.
+    #   betas         (beta1, beta2) for both networks, or ((gen_beta1, gen_beta2), (disc_beta1, disc_beta2)); each in [0, 1).  They are
+    #                 launch arguments of whichever Adam entry point the step takes (pix2pix: beta1 = 0.5; hinge + spectral
+    #                 normalisation: (0.0, 0.9)).
+    #   weight_decay  a finite number >= 0 for both networks, or a pair (gen, disc) whose members may be None; 0 / None = that network
+    #                 keeps today's entry points.  torch.optim.AdamW(net.parameters(), weight_decay=wd): p *= 1 - lr * wd ahead of the
+    #                 moment updates, inside the fused Adam pass (pg_adamw_step: one multiply, no memory access), over the network's WHOLE
+    #                 flat parameter buffer -- biases and norm parameters included, with spectral normalisation the stored weight_orig.
+    #                 No parameter groups.  The multiplier is formed from the step's own gen_lr / dsc_lr, so lr_decay and the plateau
+    #                 schedule carry over; lr * weight_decay must be < 1.
+    #   save_optimizer  truthy: save() also writes optimizer_ep_%03d.pth (optimizer_state()) and load_last_checkpoint() reads it back
+    #                 (load_optimizer_state()): the next setup_optimizers() -- train() calls it -- then keeps moments and step counts
+    #                 instead of zeroing them, and the run resumes exactly.  Off: the files and the behaviour of before, even where
+    #                 such a file exists.
+    # Checked at the top of batch() and in setup_optimizers(): ValueError.
+    betas = None
+    weight_decay = None
+    save_optimizer = None
 
     # Segmentation metrics of evaluation passes (opt-in, beyond the reference): None = off -- no launch, no buffer, no key, file or
     # printed line.  True: every batch(train=False) adds ONE launch beside its segmentation loss (engine.seg_confusion: the confusion
@@ -318,19 +338,64 @@ class Trainer:
         self.grad_history = []     # train() with clip_grad_norm: one read_grad_stats() dict per epoch
         self._aug_counter = None   # diffaug: the step count of the parameter stream, one int64 word on the device (persistent)
         self._aug_params = None    # diffaug: the last training step's parameter table (int32 [N, 8] on the device)
+        self._resume = None        # load_optimizer_state(): moments, step counts and trainer state the next setup_optimizers() takes over
+        self._plateau = None       # train(reduce_on_plateau=True): the two _Plateau objects (optimizer_state() records them)
+        self._resume_plateau = None      # their restored state, from setup_optimizers() to the train() that called it
 
     # -------------------------------------------------------------------------------------- optimizers
     def setup_optimizers(self, gen_lr=1e-3, dsc_lr=1e-3):
-        """Fresh Adam state (the reference re-creates both optimizers on every train() call, trainer.py:169-172)."""
+        """Fresh Adam state (the reference re-creates both optimizers on every train() call, trainer.py:169-172) -- unless
+        load_optimizer_state() left a restored one pending: this call then takes over its moments, step counts, dropout step number and
+        augmentation count (the learning rates are this call's arguments) and the state is consumed."""
+        self._optim_now((gen_lr, dsc_lr))      # (ValueError before anything changes)
         self.flush()              # an Adam(D) still running on the second stream reads and writes the OLD moments
         self.gen_lr, self.dsc_lr = gen_lr, dsc_lr
         g, d = self.generator.flat, self.discriminator.flat
-        self._adam = (torch.zeros_like(g), torch.zeros_like(g), torch.zeros_like(d), torch.zeros_like(d))
-        self._t_g = self._t_d = 0
+        resume, self._resume, self._resume_plateau = self._resume, None, None
+        if resume is None:
+            self._adam = (torch.zeros_like(g), torch.zeros_like(g), torch.zeros_like(d), torch.zeros_like(d))
+            self._t_g = self._t_d = 0
+        else:
+            self._adam = tuple(t.to(net.device) for t, net in zip(resume['adam'], (g, g, d, d)))
+            self._t_g, self._t_d = resume['t_g'], resume['t_d']
+            tr = resume['trainer']
+            if tr is not None:
+                self._step = int(tr['step'])
+                if tr.get('diffaug_counter') is not None:
+                    self._aug_counter = torch.tensor([int(tr['diffaug_counter'])], dtype=torch.int64, device=g.device)
+                self._resume_plateau = tr.get('plateau')
         self._graphs, self._kinds = {}, {}        # captured steps update the OLD moment buffers
         self._ema_ensure()
         if self._clip_ensure():
             self._clip[0].zero_()
+
+    # -------------------------------------------------------------------------------------- betas, weight decay
+    _OPTIM_OFF = (((0.9, 0.999), (0.9, 0.999)), (None, None))
+
+    def _optim_now(self, lrs=None):
+        """(((gen_beta1, gen_beta2), (disc_beta1, disc_beta2)), (gen_weight_decay, disc_weight_decay)) of the next Adam launches,
+        validated (ValueError), the decays also against the learning rates `lrs` (default: the current ones)."""
+        if self.betas is None and self.weight_decay is None:
+            return self._OPTIM_OFF
+        betas, wd = E.check_betas(self.betas), E.check_weight_decay(self.weight_decay)
+        for lr, w in zip(lrs if lrs is not None else (self.gen_lr, self.dsc_lr), wd):
+            if w is not None:
+                E.decay_mul(lr, w)
+        return betas, wd
+
+    def _optim_key(self):
+        # (betas and the decay are launch arguments of the Adam kernels: a captured step holds the betas it was captured with and,
+        #  per network, the entry point with or without a decay.  Off: the key is the one without the feature)
+        if self.betas is None and self.weight_decay is None:
+            return ()
+        return (('optim',) + self._optim_now(),)
+
+    def _adam_scalars(self, which, k):
+        """The `k` floats (2, or 3 with a decay set for either network) a captured step's Adam launch of network `which` reads."""
+        betas, wd = self._optim_now()
+        i = 0 if which == 'g' else 1
+        sc = E.adam_scalars(self._t_g if i == 0 else self._t_d, self.gen_lr if i == 0 else self.dsc_lr, betas[i][0], betas[i][1], wd[i])
+        return sc + (np.float32(1.0),) * (k - len(sc))
 
     # -------------------------------------------------------------------------------------- gradient-norm clipping
     def _clip_now(self):
@@ -609,6 +674,7 @@ class Trainer:
         t_host0 = time.perf_counter()
         G, D = self.generator, self.discriminator
         self._gan_now()           # (ValueError before anything is launched)
+        self._optim_now()         # (likewise)
         if not train and self.metric_bins is not None:
             self._metric_bins()   # (an evaluation step: ValueError before anything is launched)
         x, y, u8, N, H, W, Cin, Cout = self._inputs(x, y)
@@ -956,41 +1022,61 @@ class Trainer:
         net, (m, v) = (self.generator, self._adam[0:2]) if which == 'g' else (self.discriminator, self._adam[2:4])
         decay = self._ema_now() if which == 'g' else None
         max_norm = self._clip_now()[0 if which == 'g' else 1]
+        betas, wds = self._optim_now()
+        (b1, b2), wd = (betas[0], wds[0]) if which == 'g' else (betas[1], wds[1])
+        bk = dict(beta1=b1, beta2=b2) if self.betas is not None else {}      # (off: the calls of before, argument for argument)
+        dev = self._adam_dev
+        if dev is not None:
+            k = dev.numel() // 2          # floats per network: 2, or 3 with a decay set (_capture)
+            dev = dev[0:k] if which == 'g' else dev[k:2 * k]
         if which == 'd' and net.engine.spectral:
             # the passes ran on W / sigma: the flat gradient (all-reduced already under data parallelism -- the map is linear in it, and
             # u, v, sigma agree on every rank) becomes the gradient of the stored weights, on this stream, ahead of the norm and Adam
             net.spectral_grad_map(net.grad_flat)
+        stat = None
         if max_norm is not None:
             # the norm of the whole flat gradient (two short launches) and Adam on g * coef, both behind the gradient on this stream;
             # a non-finite norm skips the update on the device -- the host's step count advances regardless
             self._clip_ensure()
             stat = self._clip_stat(which)
             E.grad_norm(net.grad_flat, max_norm, self._clip[1 if which == 'g' else 2], stat)
+        if wd is not None:
+            # decoupled weight decay: p * (1 - lr * wd) rides in the same kernel, with the average and the clipping where they are set
             ema = self._ema if decay is not None else None
-            if self._adam_dev is not None:
-                E.adam_clip_step_dev(net.flat, net.grad_flat, m, v, ema, self._adam_dev[0:2] if which == 'g' else self._adam_dev[2:4], stat, decay)
+            if dev is not None:
+                E.adamw_step_dev(net.flat, net.grad_flat, m, v, dev, ema, decay, stat, **bk)
             elif which == 'g':
                 self._t_g += 1
-                E.adam_clip_step(net.flat, net.grad_flat, m, v, ema, self._t_g, self.gen_lr, stat, decay)
+                E.adamw_step(net.flat, net.grad_flat, m, v, self._t_g, self.gen_lr, wd, ema, decay, stat, **bk)
             else:
                 self._t_d += 1
-                E.adam_clip_step(net.flat, net.grad_flat, m, v, ema, self._t_d, self.dsc_lr, stat, decay)
+                E.adamw_step(net.flat, net.grad_flat, m, v, self._t_d, self.dsc_lr, wd, ema, decay, stat, **bk)
+        elif stat is not None:
+            ema = self._ema if decay is not None else None
+            if dev is not None:
+                E.adam_clip_step_dev(net.flat, net.grad_flat, m, v, ema, dev, stat, decay, **bk)
+            elif which == 'g':
+                self._t_g += 1
+                E.adam_clip_step(net.flat, net.grad_flat, m, v, ema, self._t_g, self.gen_lr, stat, decay, **bk)
+            else:
+                self._t_d += 1
+                E.adam_clip_step(net.flat, net.grad_flat, m, v, ema, self._t_d, self.dsc_lr, stat, decay, **bk)
         elif decay is not None:
             # the generator's weight average rides in the same kernel (5 reads + 4 writes per element instead of 4 + 3 and a second pass)
-            if self._adam_dev is not None:
-                E.adam_ema_step_dev(net.flat, net.grad_flat, m, v, self._ema, self._adam_dev[0:2], decay)
+            if dev is not None:
+                E.adam_ema_step_dev(net.flat, net.grad_flat, m, v, self._ema, dev, decay, **bk)
             else:
                 self._t_g += 1
-                E.adam_ema_step(net.flat, net.grad_flat, m, v, self._ema, self._t_g, self.gen_lr, decay)
-        elif self._adam_dev is not None:
+                E.adam_ema_step(net.flat, net.grad_flat, m, v, self._ema, self._t_g, self.gen_lr, decay, **bk)
+        elif dev is not None:
             # a step being captured: lr / bc1 and sqrt(bc2) come from device memory (written before every replay, _batch_graph)
-            E.adam_step_dev(net.flat, net.grad_flat, m, v, self._adam_dev[0:2] if which == 'g' else self._adam_dev[2:4])
+            E.adam_step_dev(net.flat, net.grad_flat, m, v, dev, **bk)
         elif which == 'g':
             self._t_g += 1
-            E.adam_step(net.flat, net.grad_flat, m, v, self._t_g, self.gen_lr)
+            E.adam_step(net.flat, net.grad_flat, m, v, self._t_g, self.gen_lr, **bk)
         else:
             self._t_d += 1
-            E.adam_step(net.flat, net.grad_flat, m, v, self._t_d, self.dsc_lr)
+            E.adam_step(net.flat, net.grad_flat, m, v, self._t_d, self.dsc_lr, **bk)
 
     # -------------------------------------------------------------------------------------- how a step is launched
     def _graph_eligible(self):
@@ -1019,7 +1105,7 @@ class Trainer:
         # (likewise the augmentation's policy and seed, launch arguments of pg_diffaug_params)
         aug = self._aug_now() if train else None
         return (self._kind_key_base(x, y, u8, dims, train) + ((clip,) if clip != (None, None) else ())
-                + ((('diffaug',) + aug,) if aug is not None else ()))
+                + ((('diffaug',) + aug,) if aug is not None else ()) + (self._optim_key() if train else ()))
 
     def _kind_key_base(self, x, y, u8, dims, train):
         G, D = self.generator, self.discriminator
@@ -1169,7 +1255,8 @@ class Trainer:
         """The training step replayed from a captured hipGraph: ~220 launches become one hipGraphLaunch (host enqueue 1.9 ms -> well
         under 0.1 ms per step at cfg2; the step itself is unchanged -- same kernels, same arguments, bit-identical results).
         Captured on first use.  Per replay the host copies the inputs into the graph's input buffers, writes Adam's two
-        step-dependent scalars per network (lr / bc1, sqrt(bc2): pg_adam_step_dev reads them from device memory) and launches.
+        step-dependent scalars per network (lr / bc1, sqrt(bc2): pg_adam_step_dev reads them from device memory; with a weight decay
+        set a third, the decay multiplier of the step's learning rate: pg_adamw_step_dev) and launches.
         Returns None (after a warning) if this runtime cannot capture the step: the caller continues launch by launch."""
         self.flush()
         key = (key, bool(two))            # (a kind's one-stream and two-stream captures are different graphs)
@@ -1195,8 +1282,9 @@ class Trainer:
         host = st.host[st.slot]
         st.slot = (st.slot + 1) % len(st.host)
         h = host.numpy()
-        h[0:2] = E.adam_scalars(self._t_g, self.gen_lr)
-        h[2:4] = E.adam_scalars(self._t_d, self.dsc_lr)
+        k = st.scal.numel() // 2
+        h[0:k] = self._adam_scalars('g', k)
+        h[k:2 * k] = self._adam_scalars('d', k)
         st.scal.copy_(host, non_blocking=True)
         st.graph.replay()
         self._last_gen = st.gen
@@ -1216,10 +1304,12 @@ class Trainer:
         dev = x.device
         G, D = self.generator, self.discriminator
         st.x, st.y = torch.empty_like(x), torch.empty_like(y)
-        st.scal = torch.zeros(4, dtype=torch.float32, device=dev)
+        # (lr / bc1 and sqrt(bc2) per network; with a weight decay set for either, three floats per network: + the decay multiplier)
+        nscal = 6 if self._optim_now()[1] != (None, None) else 4
+        st.scal = torch.zeros(nscal, dtype=torch.float32, device=dev)
         # (a ring: the copy of slot i to the device may still be queued when the host prepares the next steps; _publish's ring of
         #  four loss slots keeps the host at most four steps ahead of the device)
-        st.host, st.slot = [torch.zeros(4, dtype=torch.float32).pin_memory() for _ in range(8)], 0
+        st.host, st.slot = [torch.zeros(nscal, dtype=torch.float32).pin_memory() for _ in range(8)], 0
         while len(self._graphs) >= self.MAX_GRAPHS:
             self._graphs.pop(next(iter(self._graphs)))
         G.ensure_grad_flat()
@@ -1298,6 +1388,11 @@ class Trainer:
         plateau = None
         if reduce_on_plateau:
             plateau = [_Plateau(gen_lr), _Plateau(dsc_lr)]
+            if self._resume_plateau is not None:
+                # a resumed run (save_optimizer): the schedule goes on from its saved learning rates, best values and patience counts
+                for pl, saved in zip(plateau, self._resume_plateau):
+                    pl.lr, pl.best, pl.bad = float(saved['lr']), float(saved['best']), int(saved['bad'])
+                self.gen_lr, self.dsc_lr = plateau[0].lr, plateau[1].lr
             if self.neptune_config is not None:
                 self.neptune_config['model/parameters/scheduler'] = 'ReduceLROnPlateau'
         elif lr_decay is not None and self.neptune_config is not None:
@@ -1305,12 +1400,14 @@ class Trainer:
             self.neptune_config['model/parameters/decay_freq'] = decay_freq
             self.neptune_config['model/parameters/lr_decay'] = lr_decay
 
+        self._plateau, self._resume_plateau = plateau, None
         history = {'gen': [], 'disc': []}
         try:
             return self._epochs(train_data, val_data, epochs, save_freq, lr_decay, decay_freq, plateau, history)
         finally:
             # also on an exception / KeyboardInterrupt inside the loop.  gc.unfreeze() is process-global: it also thaws what the host
             # application froze itself (which is why gc_freeze is opt-in)
+            self._plateau = None
             if self.gc_freeze:
                 _unsettle_gc()
 
@@ -1453,6 +1550,55 @@ class Trainer:
             ema_savefile = f'{self.savefolder}/generator_ema_ep_{epoch:03d}.pth'
             print(f"Saving to {ema_savefile}")
             torch.save(self.ema_generator.state_dict_contiguous(), ema_savefile)
+        if self.save_optimizer:
+            # Adam's moments and step counts and the trainer's own counters, for an exact resume; the name stays clear of the two globs
+            opt_savefile = f'{self.savefolder}/optimizer_ep_{epoch:03d}.pth'
+            print(f"Saving to {opt_savefile}")
+            torch.save(self.optimizer_state(epoch), opt_savefile)
+
+    def optimizer_state(self, epoch=None):
+        """What save() writes to optimizer_ep_%03d.pth with save_optimizer set: {'format': 1, 'gen', 'disc', 'trainer'}.  'gen' and
+        'disc' are state_dicts that torch.optim.Adam(list(net.parameters())) -- AdamW where weight_decay is set -- loads as they are
+        (optimizer_section); 'trainer' holds epoch, gen_lr, dsc_lr, t_g, t_d, step (the host step number the dropout seeds derive
+        from), diffaug_counter (the device word, read here; None without one) and plateau (the two schedules' lr / best / bad inside
+        train(reduce_on_plateau=True), else None).  CPU tensors.  Completes a discriminator update in flight."""
+        self.flush()
+        G, D = self.generator, self.discriminator
+        betas, wd = self._optim_now()
+        adam = self._adam
+        if adam is None:          # (nothing trained yet: zero moments at step 0, what a fresh optimizer starts from)
+            adam = (torch.zeros_like(G.flat), torch.zeros_like(G.flat), torch.zeros_like(D.flat), torch.zeros_like(D.flat))
+        plateau = self._plateau
+        return {
+            'format': 1,
+            'gen': optimizer_section(G, adam[0], adam[1], self._t_g, self.gen_lr, betas[0], wd[0]),
+            'disc': optimizer_section(D, adam[2], adam[3], self._t_d, self.dsc_lr, betas[1], wd[1]),
+            'trainer': {
+                'epoch': epoch, 'gen_lr': float(self.gen_lr), 'dsc_lr': float(self.dsc_lr), 't_g': int(self._t_g), 't_d': int(self._t_d),
+                'step': int(self._step),
+                'diffaug_counter': int(self._aug_counter.cpu()[0]) if self._aug_counter is not None else None,
+                'plateau': [dict(lr=float(pl.lr), best=float(pl.best), bad=int(pl.bad)) for pl in plateau] if plateau is not None else None,
+            },
+        }
+
+    def load_optimizer_state(self, path):
+        """Read an optimizer_ep_*.pth (or the dict optimizer_state() returns): its 'gen' / 'disc' sections may also come straight from
+        the state_dict() of a torch.optim.Adam / AdamW over the modules' parameters; 'trainer' may be missing.  RuntimeError for a wrong
+        parameter count or shape.  The state is PENDING: the next setup_optimizers() -- train() calls it, as does the first training
+        batch() of a trainer without optimizers -- takes it over instead of starting fresh."""
+        sd = torch.load(path, map_location='cpu') if not isinstance(path, dict) else path
+        if not isinstance(sd, dict) or 'gen' not in sd or 'disc' not in sd:
+            raise RuntimeError(f"{path if not isinstance(path, dict) else 'the given dict'}: not an optimizer state of this trainer (no 'gen' / 'disc' sections)")
+        if sd.get('format', 1) != 1:
+            raise RuntimeError(f"optimizer state of format {sd.get('format')!r}: this version reads format 1")
+        G, D = self.generator, self.discriminator
+        gm, gv, dm, dv = (torch.zeros(G.flat.numel()), torch.zeros(G.flat.numel()), torch.zeros(D.flat.numel()), torch.zeros(D.flat.numel()))
+        t_g = load_optimizer_section(G, sd['gen'], gm, gv, 'gen')
+        t_d = load_optimizer_section(D, sd['disc'], dm, dv, 'disc')
+        tr = sd.get('trainer')
+        if tr is not None:
+            t_g, t_d = int(tr.get('t_g', t_g)), int(tr.get('t_d', t_d))
+        self._resume = {'adam': (gm, gv, dm, dv), 't_g': t_g, 't_d': t_d, 'trainer': dict(tr) if tr is not None else None}
 
     def load_last_checkpoint(self):
         gen_ck = sorted(glob.glob(self.savefolder + "generator_ep*.pth"))
@@ -1466,6 +1612,13 @@ class Trainer:
             self.load(f"{self.savefolder}/generator_ep_{start:03d}.pth", f"{self.savefolder}/discriminator_ep_{start:03d}.pth",
                       ema_save if os.path.exists(ema_save) else None)
             self.start = start + 1
+            if self.save_optimizer:
+                opt_save = f"{self.savefolder}/optimizer_ep_{start:03d}.pth"
+                if os.path.exists(opt_save):
+                    self.load_optimizer_state(opt_save)
+                    print(f"Loaded the optimizer state from {os.path.basename(opt_save)}")
+                else:
+                    print(f"No {os.path.basename(opt_save)}: the optimizers start fresh")
             best = BestTracker.load(self.savefolder)      # (save_best: the resumed run competes with the best model already on disk)
             if best is not None:
                 self._best = best
@@ -1496,6 +1649,48 @@ class Trainer:
                     for k, _ in self._ema_net.named_parameters():
                         own[k].copy_(sd[k])
                 print(f"Loaded the weight average from {os.path.basename(ema_save)}")
+
+
+def optimizer_section(net, m, v, step, lr, betas=(0.9, 0.999), weight_decay=None):
+    """The state_dict of a torch.optim.Adam (AdamW with a weight_decay) over list(net.parameters()) that has taken `step` steps with
+    the flat moment buffers `m`, `v` of `net` (a UNet / Discriminator of this package): state[i] = {step: float32 scalar, exp_avg,
+    exp_avg_sq}, i in net.parameters() order, every tensor in the parameter's own shape, contiguous, on the CPU; one param_groups
+    entry.  The views are engine.torch_views of the moment buffers: the mechanism that makes the parameters views of net.flat."""
+    names = [k for k, _ in net.named_parameters()]
+    mv, vv = E.torch_views(m.detach(), net._layers), E.torch_views(v.detach(), net._layers)
+    state = {i: {'step': torch.tensor(float(step), dtype=torch.float32), 'exp_avg': mv[k].contiguous().cpu().clone(),
+                 'exp_avg_sq': vv[k].contiguous().cpu().clone()} for i, k in enumerate(names)}
+    group = {'lr': float(lr), 'betas': (float(betas[0]), float(betas[1])), 'eps': 1e-8, 'weight_decay': float(weight_decay or 0.0),
+             'amsgrad': False, 'params': list(range(len(names)))}
+    return {'state': state, 'param_groups': [group]}
+
+
+def load_optimizer_section(net, section, m, v, name='optimizer'):
+    """The reverse of optimizer_section: fill the flat moment buffers `m`, `v` (in net.flat's layout) from `section` -- one written by
+    optimizer_section or the state_dict() of a torch optimizer over list(net.parameters()) -- and return its step count.  A parameter
+    without a state entry (it never had a gradient) keeps zero moments.  RuntimeError for a wrong parameter count or shape."""
+    names = [k for k, _ in net.named_parameters()]
+    try:
+        state, groups = section['state'], section['param_groups']
+        ids = [i for g in groups for i in g['params']]
+    except (KeyError, TypeError):
+        raise RuntimeError(f"{name}: not an optimizer state_dict (state / param_groups)") from None
+    if len(ids) != len(names) or any(i not in ids for i in state):
+        raise RuntimeError(f"{name}: the optimizer state holds {len(ids)} parameters, the network has {len(names)}")
+    mv, vv = E.torch_views(m, net._layers), E.torch_views(v, net._layers)
+    step = 0
+    with torch.no_grad():
+        for i, k in zip(ids, names):
+            st = state.get(i)
+            if st is None:
+                continue
+            for key, views in (('exp_avg', mv), ('exp_avg_sq', vv)):
+                if tuple(st[key].shape) != tuple(views[k].shape):
+                    raise RuntimeError(f"{name}: {key} of parameter {i} ({k}) has shape {tuple(st[key].shape)}, the network's is {tuple(views[k].shape)}")
+            mv[k].copy_(st['exp_avg'])
+            vv[k].copy_(st['exp_avg_sq'])
+            step = max(step, int(float(st['step'])))
+    return step
 
 
 class _Plateau:
