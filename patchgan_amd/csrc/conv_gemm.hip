@@ -814,8 +814,9 @@ __global__ __launch_bounds__(256) void k_wgrad_tapn(const float* __restrict__ X,
 }
 
 // ================================================================================================
-// Fast variants (the hot path whenever channels are multiples of 4, buffers are 16-byte aligned and every
-// tensor is < 2 GiB): same tiling and MFMA loop as the generic kernels above, but
+// Fast variants (the hot path whenever channels are multiples of 4, buffers are 16-byte aligned, every tensor
+// they gather from spans < FAST_LIMIT = 1.5 GiB and the packed weights < FAST_P_LIMIT = 1 GiB; the table next to
+// FAST_LIMIT says which operand each planner path checks): same tiling and MFMA loop as the generic kernels above, but
 //   * operand gathers are raw buffer loads (hardware range check: an out-of-range offset returns 0), so the
 //     zero padding, ragged tiles and K tails cost one v_cndmask instead of a divergent branch per load,
 //   * all offsets are 32-bit element offsets from a per-row base computed once per tile; tap validity is a
@@ -3084,6 +3085,21 @@ inline long tensor_bytes(long pixels, int ld, int C, bool bf = false) { return (
 inline bool aligned_io(const void* p, bool bf) { return (reinterpret_cast<uintptr_t>(p) & (bf ? 7 : 15)) == 0; }
 constexpr long FAST_LIMIT = 0x60000000L;   // 1.5 GiB: keeps every 32-bit byte offset, incl. the +0x40000000 sentinel, < 2^32
 constexpr long FAST_P_LIMIT = 0x40000000L; // packed weights: the invalid-row sentinel (+1 GiB) must land beyond the block
+// Which view each planner path holds below FAST_LIMIT (tensor_bytes of the call's ld; a view beyond it takes the next path down):
+//   path                                             op     checked                   beyond the limit
+//   any path, bf16 tensors (PG_IO_*)                 0-2    every bf16 tensor         PG_EINVAL (plan_conv)
+//   Bf16x (k_conv_bf16x / k_conv_bf16r)              0, 1   input                     register-staged k_*_bf16, else PG_EINVAL
+//   Bf16xTapn (bf16 row GEMM + col2im)               1      small                     Bf16x
+//   Tapnf / TapnfBf (k_s2b_tapnf)                    1      small and big             row GEMM + col2im
+//   TapnRowGemm (+k_gather_big2small / +k_col2im..)  0 / 1  input (big / small)       Tapk(p) / Gemm
+//   Tapkp (k_b2s_tapkp)                              0      big and small             Tapk
+//   Gemm with p.fast (k_b2s_fast, k_s2b_fast,        0, 1   input; the packed         generic k_big2small / k_small2big
+//        k_*_bf16 on fp32 tensors)                          weights < FAST_P_LIMIT
+//   Gemm with p.fast (k_wgrad_fast, k_wgrad_bf16)    2      small and big             generic k_wgrad
+//   Bf16xWgrad (k_wgrad_bf16x)                       2      small and big             Gemm, else PG_EINVAL
+//   WgradTapnp (k_wgrad_tapnp)                       2      small and big             WgradTapn
+//   no limit, 64-bit addressing in the kernels: Direct, Ca1 (k_s2b_ca1 / _s1), Wino1, Wino2 (polyphase), WinoWgrad, Wino2Wgrad,
+//   Tapk (k_b2s_tapk), WgradTapn, the generic Gemm kernels, and the fp32 OUTPUT of every path that checks its input only
 inline bool force_generic() {
     static const bool v = pg_exp_env("PATCHGAN_GENERIC_KERNELS") != nullptr;   // debugging aid: disable the fast variants
     return v;
@@ -3891,6 +3907,13 @@ ConvPlan plan_conv(const pg_conv_geom* gg, int op, int algo_full, const Tune& tu
     const PlanCtx c{g, algo_full & PG_ALGO_MASK, algo_full & PG_IO_MASK, tune, ws_bytes, v,
                     v ? x->part != nullptr : (offer & OFFER_PART) != 0, v ? x->u_cache != nullptr : (offer & OFFER_U) != 0,
                     v ? (x->v_keep || x->v_pre) : (offer & OFFER_V) != 0, v ? x->mul_t != nullptr : (offer & OFFER_MUL) != 0};
+    // a bf16 tensor of FAST_LIMIT bytes or more has no kernel, as an input or as an OUTPUT (patchgan_hip.h, pg_conv_max_tensor_bytes):
+    // the paths below check the tensors they gather from, which let a bf16 output beyond the limit through
+    if (v && ((c.io & PG_IO_BIG_BF16 && tensor_bytes((long)g.N * g.Hb * g.Wb, v->ld_big, g.Cb, true) >= FAST_LIMIT) ||
+              (c.io & PG_IO_SMALL_BF16 && tensor_bytes((long)g.N * g.Hs * g.Ws, v->ld_small, g.Ca, true) >= FAST_LIMIT))) {
+        ConvPlan p;
+        return fail(p);
+    }
     return op == 0 ? plan_big2small(gg, c) : op == 1 ? plan_small2big(gg, c) : plan_wgrad_conv(gg, c);
 }
 
