@@ -613,6 +613,24 @@ int pg_adamw_step_dev(float* p, const float* g, float* m, float* v, float* ema, 
                       const float* scalars /* [0] lr / bc1, [1] sqrt(bc2), [2] decay_mul */, float ema_decay,
                       const pg_grad_stat* stat, void* stream);
 
+/* ---- gradient accumulation (beyond the reference, whose users sum .grad over a few backward() calls before optimizer.step(); the
+ * call site is patchgan_amd's Trainer._adam_step with Trainer.accumulate set) ----------------------------------------------------------
+ * One streaming pass over n contiguous floats of the accumulator `acc` and the flat gradient `g`, element by element:
+ *   PG_ACC_BEGIN       acc = g                     (g only read;   8 bytes per element)
+ *   PG_ACC_ADD         acc = acc + g               (g only read;  12 bytes per element)
+ *   PG_ACC_CLOSE       g = (acc + g) * scale       (acc only read; 12 bytes per element)
+ *   PG_ACC_CLOSE_ONLY  g = acc * scale             (acc only read;  8 bytes per element: a window closed short of its last gradient)
+ * ONE fp32 add and then ONE fp32 multiply, never fused (the library is built without contraction): numpy.float32 arithmetic in that
+ * order gives the same bits; NaN and inf propagate.  `scale` is 1 / (number of gradients in the window), formed by the caller in double
+ * and rounded once; the first two modes do not read it.  No atomics, nothing depends on the order of the workgroups.
+ * PG_EINVAL before any launch, nothing touched: a NULL acc or g, either not 16-byte aligned, n <= 0, an unknown mode, ranges
+ * [acc, acc + n) and [g, g + n) that intersect, and in the two closing modes a scale that is NaN or outside (0, 1]. */
+#define PG_ACC_BEGIN 0
+#define PG_ACC_ADD 1
+#define PG_ACC_CLOSE 2
+#define PG_ACC_CLOSE_ONLY 3
+int pg_grad_accum(float* acc, float* g, long n, int mode, float scale, void* stream);
+
 /* ---- spectral normalisation of conv weights (beyond the reference, whose users wrap each nn.Conv2d of the discriminator in
  * torch.nn.utils.spectral_norm; the call sites are patchgan_amd's Discriminator(spectral_norm=True) and Trainer._enqueue_step /
  * _adam_step) --------------------------------------------------------------------------------------------------------------------

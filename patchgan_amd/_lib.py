@@ -24,6 +24,7 @@ TUNE_S3_OFF = 0x40000        # the three Winograd GEMM families on the fp32 MFMA
 LOSS_TVERSKY, LOSS_WBCE, LOSS_MAE, LOSS_BCE = 0, 1, 2, 3
 OP_BIG2SMALL, OP_SMALL2BIG, OP_WGRAD = 0, 1, 2
 AUG_FLIP, AUG_TRANSLATION, AUG_CUTOUT = 1, 2, 4      # PG_AUG_*
+ACC_BEGIN, ACC_ADD, ACC_CLOSE, ACC_CLOSE_ONLY = 0, 1, 2, 3      # PG_ACC_*
 GAN_LSGAN, GAN_HINGE_D, GAN_HINGE_G, GAN_BCE_LOGITS = 0, 1, 2, 3      # PG_GAN_*
 
 _ERR = {-1: 'PG_EINVAL (bad shape / null or misaligned pointer)', -2: 'PG_EWORKSPACE (workspace too small)',
@@ -169,6 +170,7 @@ SIGNATURES = {
     'pg_adam_clip_step_dev': (_i, [_p, _p, _p, _p, _p, _l, _f, _f, _f, _p, _f, _p, _p]),
     'pg_adamw_step': (_i, [_p, _p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _f, _f, _f, _p, _p]),
     'pg_adamw_step_dev': (_i, [_p, _p, _p, _p, _p, _l, _f, _f, _f, _p, _f, _p, _p]),
+    'pg_grad_accum': (_i, [_p, _p, _l, _i, _f, _p]),
     'pg_spectral_workspace_bytes': (_l, [_i, ctypes.POINTER(SpectralItem)]),
     'pg_spectral_fwd': (_i, [_i, ctypes.POINTER(SpectralItem), _p, _p, _l, _p, _l, _p]),
     'pg_spectral_bwd': (_i, [_i, ctypes.POINTER(SpectralItem), _p, _l, _p, _l, _p]),

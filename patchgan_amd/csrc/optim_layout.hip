@@ -93,6 +93,40 @@ __global__ void k_adam(float* __restrict__ p, const float* __restrict__ g, float
     }
 }
 
+// ---- gradient accumulation (pg_grad_accum) ----------------------------------------------------------------------------------------------
+// One streaming pass over the accumulator and the flat gradient, MODE = PG_ACC_*: per element ONE fp32 add and then ONE fp32 multiply
+// where the mode has them (the library is built without fp contraction: never an fma), so a float32 replay on the host gives the same
+// bits, NaN and inf included.  The operand a mode only reads is const here and never stored.
+template <int MODE>
+__device__ __forceinline__ float acc_one(float a, float g, float scale) {
+    if constexpr (MODE == PG_ACC_BEGIN) return g;
+    if constexpr (MODE == PG_ACC_ADD) return a + g;
+    if constexpr (MODE == PG_ACC_CLOSE) return (a + g) * scale;
+    return a * scale;                                   // PG_ACC_CLOSE_ONLY
+}
+
+template <int MODE>
+__global__ void k_grad_accum(float* __restrict__ acc, float* __restrict__ g, long n, float scale) {
+    constexpr bool READ_A = MODE != PG_ACC_BEGIN, READ_G = MODE != PG_ACC_CLOSE_ONLY;
+    constexpr bool TO_ACC = MODE == PG_ACC_BEGIN || MODE == PG_ACC_ADD;
+    const long n4 = n >> 2;
+    const long stride = (long)gridDim.x * blockDim.x;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += stride) {
+        float4 aa = {0.f, 0.f, 0.f, 0.f}, gg = {0.f, 0.f, 0.f, 0.f}, r;
+        if constexpr (READ_A) aa = reinterpret_cast<const float4*>(acc)[i];
+        if constexpr (READ_G) gg = reinterpret_cast<const float4*>(g)[i];
+        r.x = acc_one<MODE>(aa.x, gg.x, scale);
+        r.y = acc_one<MODE>(aa.y, gg.y, scale);
+        r.z = acc_one<MODE>(aa.z, gg.z, scale);
+        r.w = acc_one<MODE>(aa.w, gg.w, scale);
+        reinterpret_cast<float4*>(TO_ACC ? acc : g)[i] = r;
+    }
+    for (long i = (n4 << 2) + blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += stride) {
+        const float a = READ_A ? acc[i] : 0.f, x = READ_G ? g[i] : 0.f;
+        (TO_ACC ? acc : g)[i] = acc_one<MODE>(a, x, scale);
+    }
+}
+
 // ---- global gradient norm (pg_grad_norm) ------------------------------------------------------------------------------------------------
 // The sum of squares of n floats in fp64, in an order that depends on n alone.  k_sumsq_part: workgroup b of B (norm_blocks(n)) takes the
 // 16-byte groups b * 256 + lane + k * B * 256, k = 0, 1, ... -- one fp64 accumulator per component, so four independent chains per lane
@@ -457,6 +491,25 @@ int pg_adamw_step_dev(float* p, const float* g, float* m, float* v, float* ema, 
     const uintptr_t al = (uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema | (uintptr_t)stat;
     if (al & 15) return PG_EINVAL;
     adamw_launch<true>(p, g, m, v, ema, n, 0.f, beta1, beta2, eps, 0.f, scalars, 1.f, ema_decay, stat, stream);
+    return pg_launch_status();
+}
+
+int pg_grad_accum(float* acc, float* g, long n, int mode, float scale, void* stream) {
+    if (!acc || !g || n <= 0) return PG_EINVAL;
+    if (((uintptr_t)acc | (uintptr_t)g) & 15) return PG_EINVAL;
+    const uintptr_t a0 = (uintptr_t)acc, g0 = (uintptr_t)g, bytes = (uintptr_t)n * sizeof(float);
+    if (a0 < g0 + bytes && g0 < a0 + bytes) return PG_EINVAL;
+    const bool closing = mode == PG_ACC_CLOSE || mode == PG_ACC_CLOSE_ONLY;
+    if (!closing && mode != PG_ACC_BEGIN && mode != PG_ACC_ADD) return PG_EINVAL;
+    if (closing && !(scale > 0.f && scale <= 1.f)) return PG_EINVAL;      // (a NaN fails both comparisons; inf the second)
+    const dim3 grid(blocks_for(n / 4 + 1)), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    switch (mode) {
+    case PG_ACC_BEGIN: hipLaunchKernelGGL(k_grad_accum<PG_ACC_BEGIN>, grid, block, 0, s, acc, g, n, scale); break;
+    case PG_ACC_ADD: hipLaunchKernelGGL(k_grad_accum<PG_ACC_ADD>, grid, block, 0, s, acc, g, n, scale); break;
+    case PG_ACC_CLOSE: hipLaunchKernelGGL(k_grad_accum<PG_ACC_CLOSE>, grid, block, 0, s, acc, g, n, scale); break;
+    default: hipLaunchKernelGGL(k_grad_accum<PG_ACC_CLOSE_ONLY>, grid, block, 0, s, acc, g, n, scale); break;
+    }
     return pg_launch_status();
 }
 

@@ -1122,6 +1122,36 @@ def adamw_step_dev(p, g, m, v, scalars, ema=None, ema_decay=None, stat=None, bet
                                        stat.data_ptr() if stat is not None else None, _stream()), 'pg_adamw_step_dev')
 
 
+def check_accumulate(value):
+    """Trainer.accumulate / train_params.accumulate as the window length: None (off: None or 1) or an int >= 2, or ValueError."""
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < 1:
+        raise ValueError(f"accumulate must be None or an int >= 1 (micro-batches per optimizer step), not {value!r}")
+    return int(value) if value >= 2 else None
+
+
+def accum_phase(done, k):
+    """The phase of the training call that follows `done` completed calls of a window of k >= 2: 'begin' | 'add' | 'close'."""
+    if not 0 <= done < k:
+        raise ValueError(f"window position {done} outside [0, {k})")
+    return 'begin' if done == 0 else ('close' if done + 1 == k else 'add')
+
+
+def accum_scale(count):
+    """1 / count as pg_grad_accum's closing modes take it: formed in double, rounded once."""
+    return np.float32(1.0 / count)
+
+
+ACC_MODES = {'begin': L.ACC_BEGIN, 'add': L.ACC_ADD, 'close': L.ACC_CLOSE, 'close_only': L.ACC_CLOSE_ONLY}
+
+
+def grad_accum(acc, g, mode, scale=1.0):
+    """One pass of pg_grad_accum over the flat fp32 accumulator `acc` and gradient `g` on the current stream.  mode 'begin': acc = g;
+    'add': acc += g; 'close': g = (acc + g) * scale; 'close_only': g = acc * scale (scale = accum_scale(count); the first two ignore it)."""
+    L.check(L.load().pg_grad_accum(acc.data_ptr(), g.data_ptr(), g.numel(), ACC_MODES[mode], float(scale), _stream()), 'pg_grad_accum')
+
+
 def seg_confusion(p, y, threshold, counts):
     """Add the confusion counts of prediction View p against target View y (fp32, the same shape) to `counts`: an int64 device tensor
     of K*K + 1 words, K = 2 for one channel (p >= threshold against y >= 0.5) and the channel count otherwise (first maximum against

@@ -94,6 +94,14 @@ def optimizer_of(betas=None, weight_decay=None, save_optimizer=None, lrs=None):
     return betas, weight_decay, (True if save_optimizer else None)
 
 
+def accumulate_of(value=None):
+    """Trainer.accumulate from the YAML's train_params.accumulate: an int >= 2 = that many micro-batches per optimizer step; absent,
+    null or 1 = off (None).  ValueError for anything else -- 0, a negative number, a float, true / false, a string --, before any
+    network is built."""
+    from . import engine as E
+    return E.check_accumulate(value)
+
+
 def _optimizer_of_params(tp):
     return optimizer_of(tp.get('betas', None), tp.get('weight_decay', None), tp.get('save_optimizer', None),
                         (tp.get('gen_learning_rate', 1e-3), tp.get('disc_learning_rate', 1e-3)))
@@ -151,7 +159,8 @@ def apply_train_params(trainer, train_params):
     may be null; a non-finite gradient then skips the step), diffaug / diffaug_seed (Trainer.diffaug: differentiable augmentation of
     the discriminator's inputs; diffaug_of), gan_mode / real_label (Trainer.gan_mode: the adversarial objective; gan_mode_of), betas /
     weight_decay / save_optimizer (Trainer.betas, Trainer.weight_decay: Adam's betas and AdamW's decoupled decay per network;
-    Trainer.save_optimizer: optimizer_ep_*.pth beside the checkpoints, for an exact resume; optimizer_of)."""
+    Trainer.save_optimizer: optimizer_ep_*.pth beside the checkpoints, for an exact resume; optimizer_of), accumulate
+    (Trainer.accumulate: micro-batches per optimizer step; accumulate_of)."""
     trainer.loss_type = train_params['loss_type']
     trainer.seg_alpha = train_params['seg_alpha']
     trainer.ema_decay = train_params.get('ema_decay', None)
@@ -165,6 +174,7 @@ def apply_train_params(trainer, train_params):
     trainer.gan_mode, trainer.real_label = gan_mode_of(train_params.get('gan_mode', None), train_params.get('real_label', None),
                                                        trainer.discriminator.final_act)
     trainer.betas, trainer.weight_decay, trainer.save_optimizer = _optimizer_of_params(train_params)
+    trainer.accumulate = accumulate_of(train_params.get('accumulate', None))
 
 
 def diffaug_of(policy=None, seed=None):
@@ -217,6 +227,7 @@ def patchgan_train(argv=None):
     # (the objective against the discriminator's head: a ValueError here, before any data set or network is built)
     gan_mode_of(config['train_params'].get('gan_mode'), config['train_params'].get('real_label'), disc_final_act_of(disc_cfg.get('final_act')))
     _optimizer_of_params(config['train_params'])      # (likewise the optimizer's settings)
+    accumulate_of(config['train_params'].get('accumulate'))      # (likewise the accumulation window)
 
     size = dataset_params.get('size', 256)
     augmentation = dataset_params.get('augmentation', 'randomcrop')

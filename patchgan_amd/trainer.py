@@ -244,6 +244,27 @@ class Trainer:
     weight_decay = None
     save_optimizer = None
 
+    # Gradient accumulation (opt-in, beyond the reference, whose users sum .grad over a few backward() calls before optimizer.step()):
+    # None or 1 = off -- no buffer, the same launches, the same kind key, the same bits.  An int k >= 2: every batch(x, y, train=True) is
+    # one MICRO-step of a window of k.  It runs the step as ever up to the point where a network's Adam update would launch and returns
+    # its own micro-batch's losses; there pg_grad_accum takes the network's flat gradient instead (_adam_step): calls 1 .. k-1 add it
+    # into a per-network accumulator (acc = g, then acc += g) and leave weights, moments, the weight average and the step counts alone;
+    # call k closes the window -- grad_flat = (acc + g) * fl(1 / k), the window's MEAN gradient -- and everything that sits in front of
+    # Adam runs once on that: the norm and skip of clip_grad_norm, AdamW's decay, the update, the weight average; _t_g / _t_d advance
+    # by one.  Under data parallelism each call's gradients are all-reduced as today and the REDUCED gradient is accumulated; a
+    # spectrally normalised discriminator's gradient is mapped back to the stored weights call by call (each call normalised with its
+    # own sigma) before it is added.  By construction: dropout seeds and diffaug draws advance per call; BatchNorm statistics are per
+    # micro-batch, as in torch; learning rate, betas and decay are those of the closing call; a NaN in any micro-batch reaches the
+    # closed gradient, so with clip_grad_norm set the whole window's update is skipped; where the loss is a mean over the batch (MAE,
+    # one-channel weighted BCE, every adversarial term) the window IS the large batch, while loss_type = 'tversky' gives the mean over
+    # the window of each micro-batch's own focal-Tversky loss (the power is applied per micro-batch: what accumulating with the
+    # reference's loss gives).  Evaluation steps do not touch the window.  step_accumulated() closes a window that is still open
+    # (train() does at the end of every epoch's training pass: checkpoints never straddle a window); setup_optimizers(), load(),
+    # load_last_checkpoint(), a change of `accumulate` and a training step that raised discard it.  Each phase of the window ('begin',
+    # 'add', 'close') is a kind of step of its own: its own launch decision, its own captured graph -- only the closing one holds Adam.
+    # Checked at the top of batch(): ValueError.
+    accumulate = None
+
     # Segmentation metrics of evaluation passes (opt-in, beyond the reference): None = off -- no launch, no buffer, no key, file or
     # printed line.  True: every batch(train=False) adds ONE launch beside its segmentation loss (engine.seg_confusion: the confusion
     # counts of G(x) against y, integers, accumulated in `seg_counts` on the device; reset_metrics() / read_metrics()), train() records
@@ -338,6 +359,14 @@ class Trainer:
         self.grad_history = []     # train() with clip_grad_norm: one read_grad_stats() dict per epoch
         self._aug_counter = None   # diffaug: the step count of the parameter stream, one int64 word on the device (persistent)
         self._aug_params = None    # diffaug: the last training step's parameter table (int32 [N, 8] on the device)
+        self._acc = None           # accumulate: the two accumulators (G's, D's), flat fp32 buffers like the gradients
+        self._acc_k = None         # ... the window length the open window was begun with
+        self._acc_done = 0         # ... training calls completed in the open window (0: none open); host state
+        self._acc_cur = None       # ... (phase, gradients in the window with this one) of the training call being enqueued
+        self._pending_d_acc = None # ... the place in its window of the call whose D gradient is still in a collective (_pending_d)
+        self._acc_run = None       # ... (the configuration, the first step, the last step) of the unbroken run of its training calls
+        self._acc_launches = 0     # ... pg_grad_accum launches enqueued so far (the out-of-memory retry of batch() looks at it)
+        self._acc_calls = self._acc_updates = 0      # ... training calls / closed windows (what train() prints per epoch)
         self._resume = None        # load_optimizer_state(): moments, step counts and trainer state the next setup_optimizers() takes over
         self._plateau = None       # train(reduce_on_plateau=True): the two _Plateau objects (optimizer_state() records them)
         self._resume_plateau = None      # their restored state, from setup_optimizers() to the train() that called it
@@ -349,6 +378,7 @@ class Trainer:
         augmentation count (the learning rates are this call's arguments) and the state is consumed."""
         self._optim_now((gen_lr, dsc_lr))      # (ValueError before anything changes)
         self.flush()              # an Adam(D) still running on the second stream reads and writes the OLD moments
+        self._acc_done = 0        # (accumulate: an open window is discarded -- its gradients belong to the old optimizer state)
         self.gen_lr, self.dsc_lr = gen_lr, dsc_lr
         g, d = self.generator.flat, self.discriminator.flat
         resume, self._resume, self._resume_plateau = self._resume, None, None
@@ -443,6 +473,57 @@ class Trainer:
             raise RuntimeError("reset_grad_stats(): Trainer.clip_grad_norm is None (gradient-norm clipping is off)")
         self.flush()
         self._clip[0].zero_()
+
+    # -------------------------------------------------------------------------------------- gradient accumulation
+    def _acc_now(self):
+        """The window length of the next training call: None (off: `accumulate` None or 1) or the validated int >= 2."""
+        if self.accumulate is None:
+            return None
+        return E.check_accumulate(self.accumulate)
+
+    def _acc_ensure(self):
+        """With accumulate set: one accumulator per network (created zeroed outside any capture, re-created when a network moved or
+        changed its size).  -> whether they exist."""
+        if self._acc_now() is None:
+            return self._acc is not None
+        flats = (self.generator.flat, self.discriminator.flat)
+        if self._acc is None or any(a.device != f.device or a.numel() != f.numel() for a, f in zip(self._acc, flats)):
+            self.flush()
+            self._acc = tuple(torch.zeros_like(f) for f in flats)
+            self._acc_done = 0    # (whatever an open window held went with the old buffers)
+        return True
+
+    def _acc_begin_call(self):
+        """At the top of a training call: (phase, gradients in the window once this call's is in) or None with accumulation off.  A
+        window begun with another length is discarded: this call begins a new one."""
+        k = self._acc_now()
+        if k != self._acc_k:
+            self._acc_k, self._acc_done = k, 0
+        if k is None:
+            return None
+        self._acc_ensure()        # (never allocated inside a capture)
+        return E.accum_phase(self._acc_done, k), self._acc_done + 1
+
+    def _acc_key(self):
+        # (the phase decides which launches the step holds -- the non-closing ones have no Adam --, k is the closing launch's scale:
+        #  every phase is a kind of step of its own.  Off: the key is the one without the feature)
+        cur = self._acc_cur
+        return (('accum', self._acc_k, cur[0]),) if cur is not None else ()
+
+    def step_accumulated(self):
+        """Close a window that is still open after c < k training calls: grad_flat = acc * fl(1 / c) for both networks (pg_grad_accum's
+        PG_ACC_CLOSE_ONLY), then what the closing call of a full window does -- clipping's norm and skip, the decay, Adam, the weight
+        average, one step count.  Launch by launch on the current stream, after flush().  -> whether there was a window to close."""
+        self.flush()
+        c = self._acc_done
+        if c == 0 or self._acc_now() is None or self._acc is None:
+            self._acc_done = 0
+            return False
+        self._acc_done = 0
+        for which in ('g', 'd'):
+            self._adam_step(which, acc=('close_only', c))
+        self._acc_updates += 1
+        return True
 
     # -------------------------------------------------------------------------------------- differentiable augmentation
     def _aug_now(self):
@@ -675,6 +756,7 @@ class Trainer:
         G, D = self.generator, self.discriminator
         self._gan_now()           # (ValueError before anything is launched)
         self._optim_now()         # (likewise)
+        self._acc_now()           # (likewise)
         if not train and self.metric_bins is not None:
             self._metric_bins()   # (an evaluation step: ValueError before anything is launched)
         x, y, u8, N, H, W, Cin, Cout = self._inputs(x, y)
@@ -687,6 +769,8 @@ class Trainer:
             self._clip_ensure()   # (set after setup_optimizers(), or the networks moved: never allocated inside a capture)
         if train and self.diffaug is not None:
             self._aug_ensure()    # (the step-count word: never allocated inside a capture)
+        # accumulate: this call's place in its window (None = off); evaluation steps neither read nor move it
+        acc = self._acc_cur = self._acc_begin_call() if train else None
         self._step += 1
         ex = self._exec
         if ex is None or ex.device != dev:
@@ -695,6 +779,12 @@ class Trainer:
         with ex:
             dims = (N, H, W, Cin, Cout)
             key = self._kind_key(x, y, u8, dims, train)
+            if acc is not None:
+                # (the run of calls of this configuration -- the key without the phase -- and the step it began with: _launch_mode)
+                if self._acc_run is None or self._acc_run[0] != key[:-1] or self._acc_run[2] != self._step - 1:
+                    self._acc_run = (key[:-1], self._step, self._step)
+                else:
+                    self._acc_run = self._acc_run[:2] + (self._step,)
             mode = self._launch_mode(key, train)
             losses = None
             try:
@@ -704,14 +794,15 @@ class Trainer:
                         mode = 'eager1'
                 if losses is None:
                     ex.enabled = mode == 'eager2'
-                    t_g0, t_d0 = self._t_g, self._t_d
+                    t_g0, t_d0, acc0 = self._t_g, self._t_d, self._acc_launches
                     try:
                         losses = self._enqueue_step(x, y, u8, N, H, W, Cin, Cout, train)
                     except torch.cuda.OutOfMemoryError:
                         # the two-stream step holds ~2x the one-stream step's memory (second workspace, the early discriminator forward
                         # beside the generator's saved activations): where it does not fit, this KIND of step runs on one stream from
-                        # now on.  Safe to run again only while nothing of this step was committed (no optimizer update enqueued).
-                        if mode != 'eager2' or _dist().on or (self._t_g, self._t_d) != (t_g0, t_d0):
+                        # now on.  Safe to run again only while nothing of this step was committed (no optimizer update enqueued, and
+                        # with `accumulate` no gradient added to its window).
+                        if mode != 'eager2' or _dist().on or (self._t_g, self._t_d, self._acc_launches) != (t_g0, t_d0, acc0):
                             raise
                         self._two_stream_oom(ex, key)
                         mode = 'eager1'
@@ -722,8 +813,17 @@ class Trainer:
                 kind = self._kinds.get(key)
                 if kind is not None:
                     kind['trial'] = None          # a step that raised must not score in a running tournament: it starts over
+                if acc is not None:
+                    self._acc_done = 0            # ... and what it may have added to an open window is discarded with the window
                 raise
+            finally:
+                self._acc_cur = None
             self.launch_mode = mode
+        if acc is not None:
+            # the window position advances once per completed training call
+            self._acc_done = 0 if acc[0] == 'close' else acc[1]
+            self._acc_calls += 1
+            self._acc_updates += acc[0] == 'close'
         if train and self.gc_freeze:
             _settle_gc(self._step)
         self.host_ms = (time.perf_counter() - t_host0) * 1e3       # host time to enqueue the whole step (bench.py reports it)
@@ -953,6 +1053,7 @@ class Trainer:
                     de.backward(dw, dflat, dc2, god, need_wgrad=True, need_dx=False, ucache=ucache)       # trainer.py:106
                     if g_reducer is not None:
                         self._pending_d = dist.all_reduce_side(dflat)      # (behind the pass on the second stream; Adam(D) in flush())
+                        self._pending_d_acc = self._acc_cur
                     else:
                         self._adam_step('d')                                                      # trainer.py:107
                     self._mark('side: D bwd done')
@@ -974,6 +1075,7 @@ class Trainer:
                     # D's weights -- after the NEXT step's generator forward, which does not read them (trainer.py:63-66); handed to
                     # the comm stream BEFORE the compute stream waits for G's buckets, so it is queued behind them without a gap
                     self._pending_d = dist.all_reduce_side(dflat)
+                    self._pending_d_acc = self._acc_cur
                     g_reducer.finish()                     # G's buckets have been in flight since the generator backward
                     self._adam_step('g')
                 else:
@@ -1016,10 +1118,18 @@ class Trainer:
         if wait is not None:
             self._pending_d = None
             wait()
-            self._adam_step('d')
+            # (accumulate: with the place in the window of the call that made this gradient, not of the call that completes it)
+            self._adam_step('d', acc=self._pending_d_acc)
 
-    def _adam_step(self, which):
+    _ACC_CUR = object()
+
+    def _adam_step(self, which, acc=_ACC_CUR):
+        """Network `which`'s optimizer update on its flat gradient, on the current stream.  With `accumulate` set this is where the
+        gradient joins its window instead: `acc` = (phase, gradients in the window with this one), by default the place of the training
+        call being enqueued; only a closing phase goes on to the update, on the window's mean gradient."""
         net, (m, v) = (self.generator, self._adam[0:2]) if which == 'g' else (self.discriminator, self._adam[2:4])
+        if acc is Trainer._ACC_CUR:
+            acc = self._acc_cur
         decay = self._ema_now() if which == 'g' else None
         max_norm = self._clip_now()[0 if which == 'g' else 1]
         betas, wds = self._optim_now()
@@ -1032,7 +1142,16 @@ class Trainer:
         if which == 'd' and net.engine.spectral:
             # the passes ran on W / sigma: the flat gradient (all-reduced already under data parallelism -- the map is linear in it, and
             # u, v, sigma agree on every rank) becomes the gradient of the stored weights, on this stream, ahead of the norm and Adam
-            net.spectral_grad_map(net.grad_flat)
+            # (accumulate: every call's gradient on its own, ahead of the sum -- call i ran on W / sigma_i; not once more for a window
+            #  closed by step_accumulated(), whose accumulator holds mapped gradients)
+            if acc is None or acc[0] != 'close_only':
+                net.spectral_grad_map(net.grad_flat)
+        if acc is not None:
+            phase, count = acc
+            E.grad_accum(self._acc[0 if which == 'g' else 1], net.grad_flat, phase, E.accum_scale(count))
+            self._acc_launches += 1       # (an enqueued accumulate launch is a commitment of the step, as an update is: batch())
+            if phase in ('begin', 'add'):
+                return            # weights, moments, the weight average and the step count stay as they are
         stat = None
         if max_norm is not None:
             # the norm of the whole flat gradient (two short launches) and Adam on g * coef, both behind the gradient on this stream;
@@ -1105,7 +1224,8 @@ class Trainer:
         # (likewise the augmentation's policy and seed, launch arguments of pg_diffaug_params)
         aug = self._aug_now() if train else None
         return (self._kind_key_base(x, y, u8, dims, train) + ((clip,) if clip != (None, None) else ())
-                + ((('diffaug',) + aug,) if aug is not None else ()) + (self._optim_key() if train else ()))
+                + ((('diffaug',) + aug,) if aug is not None else ()) + (self._optim_key() if train else ())
+                + (self._acc_key() if train else ()))
 
     def _kind_key_base(self, x, y, u8, dims, train):
         G, D = self.generator, self.discriminator
@@ -1163,15 +1283,23 @@ class Trainer:
             return 'eager1'                       # untimed: kernel plans, weight-cache plans, workspaces
         tr = k['trial']
         if tr is None or tr['cands'] != cands:    # (the settings changed under a running tournament, or a step raised: start over)
-            tr = k['trial'] = {'cands': cands, 'i': 0, 'starts': [], 'ms': {}, 'host': {}, 'step': -1}
+            tr = k['trial'] = {'cands': cands, 'i': 0, 'starts': [], 'at': [], 'ms': {}, 'host': {}, 'step': -1}
         ev = torch.cuda.Event(enable_timing=True)
         ev.record()                               # the start of this step on the compute stream
-        if tr['starts'] and tr['step'] != self._step - 1:
+        if self._acc_cur is None:
+            apart = tr['step'] != self._step - 1
+        else:
+            # accumulate: the phases of a window are kinds of their own that follow each other call by call and go through their
+            # candidates together, so a period from one 'begin' to the next is a window launched one way; it scores per call (the
+            # division below).  Only a step from outside the run of windows (_acc_run: since which step) breaks a period.
+            apart = self._acc_run is None or tr['step'] < self._acc_run[1]
+        if tr['starts'] and apart:
             # a step of ANOTHER kind ran since this kind's last one (validation batches, a ragged last batch, an evaluation pass): the
             # period would span it -- this candidate's trial starts over
-            tr['starts'] = []
+            tr['starts'], tr['at'] = [], []
         tr['step'] = self._step
         tr['starts'].append(ev)
+        tr['at'].append(self._step)
         if len(tr['starts']) <= 2 * self.TRIAL_STEPS + 1:
             return tr['cands'][tr['i']]
         # 2 x TRIAL_STEPS + 1 starts of this candidate and the start of the step that follows them: its periods are known once that last
@@ -1179,10 +1307,10 @@ class Trainer:
         # switch and the caching allocator's growth for the new launch pattern (a second stream allocates from a pool of its own:
         # device allocations synchronise -- seen at 2-3 x the settled step time for the first steps)
         ev.synchronize()
-        st = tr['starts']
-        tr['ms'][tr['cands'][tr['i']]] = min(st[j].elapsed_time(st[j + 1]) for j in range(self.TRIAL_STEPS, len(st) - 1))
+        st, at = tr['starts'], tr['at']
+        tr['ms'][tr['cands'][tr['i']]] = min(st[j].elapsed_time(st[j + 1]) / (at[j + 1] - at[j]) for j in range(self.TRIAL_STEPS, len(st) - 1))
         tr['i'] += 1
-        tr['starts'] = [ev]
+        tr['starts'], tr['at'] = [ev], [self._step]
         if tr['i'] < len(cands) and cands[tr['i']] == 'graph' and tr['ms']['eager1'] > self.GRAPH_TRIAL_RATIO * tr['host'].get('eager1', 0.0):
             # a replay removes host time only: where the one-stream step is well clear of being host-bound the capture (which would
             # hold a second copy of the step's activations, ~4 GB at cfg2) cannot win and is not tried
@@ -1277,15 +1405,17 @@ class Trainer:
             self._graphs[key] = self._graphs.pop(key)          # most recently used last
         st.x.copy_(x, non_blocking=True)
         st.y.copy_(y, non_blocking=True)
-        self._t_g += 1
-        self._t_d += 1
-        host = st.host[st.slot]
-        st.slot = (st.slot + 1) % len(st.host)
-        h = host.numpy()
-        k = st.scal.numel() // 2
-        h[0:k] = self._adam_scalars('g', k)
-        h[k:2 * k] = self._adam_scalars('d', k)
-        st.scal.copy_(host, non_blocking=True)
+        if self._acc_cur is None or self._acc_cur[0] == 'close':
+            # (accumulate: only the graph of a window's closing call holds Adam launches -- the others move no step count and read no scalars)
+            self._t_g += 1
+            self._t_d += 1
+            host = st.host[st.slot]
+            st.slot = (st.slot + 1) % len(st.host)
+            h = host.numpy()
+            k = st.scal.numel() // 2
+            h[0:k] = self._adam_scalars('g', k)
+            h[k:2 * k] = self._adam_scalars('d', k)
+            st.scal.copy_(host, non_blocking=True)
         st.graph.replay()
         self._last_gen = st.gen
         self._aug_params = st.aug_params
@@ -1295,7 +1425,8 @@ class Trainer:
         G, D = self.generator, self.discriminator
         ema = self._ema if self._ema_now() is not None else None
         clip = tuple(self._clip) if (self._clip is not None and self._clip_now() != (None, None)) else (None, None, None)
-        return tuple(t.data_ptr() if t is not None else 0 for t in (G.grad_flat, D.grad_flat) + tuple(self._adam) + clip + (ema,))
+        acc = tuple(self._acc) if (self._acc is not None and self._acc_cur is not None) else ()
+        return tuple(t.data_ptr() if t is not None else 0 for t in (G.grad_flat, D.grad_flat) + tuple(self._adam) + clip + (ema,) + acc)
 
     def _capture(self, key, x, y, u8, dims, two=False):
         class _StepGraph:
@@ -1310,7 +1441,9 @@ class Trainer:
         # (a ring: the copy of slot i to the device may still be queued when the host prepares the next steps; _publish's ring of
         #  four loss slots keeps the host at most four steps ahead of the device)
         st.host, st.slot = [torch.zeros(nscal, dtype=torch.float32).pin_memory() for _ in range(8)], 0
-        while len(self._graphs) >= self.MAX_GRAPHS:
+        # (accumulate: the phases of one window are graphs of their own and follow each other call by call -- room for all of them)
+        room = self.MAX_GRAPHS if self._acc_cur is None else max(self.MAX_GRAPHS, min(self._acc_k, 3))
+        while len(self._graphs) >= room:
             self._graphs.pop(next(iter(self._graphs)))
         G.ensure_grad_flat()
         D.ensure_grad_flat()
@@ -1341,7 +1474,8 @@ class Trainer:
                    + ([self._ema] if self._ema_now() is not None else [])
                    + (list(self._clip) if (self._clip is not None and self._clip_now() != (None, None)) else [])
                    + ([D.sn_bufs, D.sn_eff] + list(D.sn_ws) if D.engine.spectral else [])
-                   + ([self._aug_counter] if st.aug_params is not None else []))
+                   + ([self._aug_counter] if st.aug_params is not None else [])
+                   + (list(self._acc) if self._acc_cur is not None else []))
         st.ptrs = self._graph_ptrs()
         self._graphs[key] = st
         return st
@@ -1416,7 +1550,15 @@ class Trainer:
             if _dist().rank == 0:
                 print(f"Epoch {epoch} -- lr: {self.gen_lr:5.3e}, {self.dsc_lr:5.3e}")
                 print("-------------------------------------------------------")
+            calls0, updates0 = self._acc_calls, self._acc_updates
             train_mean = self._run_epoch(train_data, True, epoch, 'Training: ', dynamic_ncols=True)
+            if self._acc_now() is not None:
+                # a window the epoch's last batches left open is closed short (its mean over what it holds): validation, the schedule
+                # and the checkpoint below never see half a window
+                self.step_accumulated()
+                if _dist().rank == 0:
+                    print(f"Accumulation -- {self._acc_updates - updates0} optimizer steps from {self._acc_calls - calls0} "
+                          f"micro-batches (accumulate = {self._acc_now()})")
             for key in history:
                 history[key].append(train_mean[key])
             if self._clip_now() != (None, None):
@@ -1630,6 +1772,7 @@ class Trainer:
         """With ema_decay set, the weight average comes from `ema_save` (a generator_ema_ep_*.pth); without such a file it
         restarts from the generator weights just loaded."""
         self.flush()
+        self._acc_done = 0        # (accumulate: an open window's gradients belong to the weights that are replaced here)
         print(generator_save, discriminator_save)
         dev = self.generator.flat.device
         self.generator.load_state_dict(torch.load(generator_save, map_location=dev))
