@@ -818,6 +818,70 @@ long pg_gan_loss_single_max(void);    /* the largest n of the one-launch path */
 long pg_gan_loss_workspace_bytes(int nterms, const pg_gan_term* terms);      /* 0 for a bad list as well */
 int pg_gan_loss(int nterms, const pg_gan_term* terms, void* ws, long ws_bytes, void* stream);
 
+/* ---- segmentation objectives on the generator's output (beyond the reference, whose objectives are focal-Tversky, weighted BCE and
+ * MAE; the call sites are patchgan_amd's Trainer.loss_type = 'ce' | 'focal' | 'dice' and their '+'-joined sums) -------------------------
+ * p (the generator's output, probabilities of a softmax or sigmoid head) and y (the target) are fp32 NHWC channel slices as
+ * pg_loss_reduce takes them: element (n, i, c) at [(n * HW + i) * ld + c], 4-byte aligned only, any C >= 1 with ld >= C, any N, any HW,
+ * any N * C; every pixel offset is formed in 64 bits.  `terms` is an OR of PG_SEG_CE, PG_SEG_FOCAL, PG_SEG_DICE.  With
+ *   lp = max(log p, -100),  lq = max(log(1 - p), -100)   (logf(p), log1pf(-p): pg_loss_reduce's bce_elem),  q = 1 - p,
+ *   x^k = x^(k-1) * x from x^0 = 1 (repeated multiplication, no powf),  g = focal_gamma, an integer in 0 .. PG_SEG_FOCAL_GAMMA_MAX,
+ *   a1 = focal_alpha, a0 = 1 - focal_alpha, or a1 = a0 = 1 for focal_alpha == PG_SEG_FOCAL_ALPHA_NONE,
+ * the members are
+ *   PG_SEG_CE     e = -y lp                                                    de/dp = -y / max(p, 1e-12)
+ *                 value scale_ce * sum e, scale_ce = alpha / (Bglobal * HW): categorical cross-entropy on probabilities, a mean over
+ *                 pixels.  A pixel whose y is all zero has no listed label (the pixels pg_seg_confusion ignores): it adds nothing to
+ *                 value or gradient and still counts in the normaliser.  Needs C >= 2.  Not logit-space cross-entropy: the head stays
+ *                 pg_softmax_fwd / pg_softmax_bwd, so a softmax output that underflows to 0 at the labelled class gets lp = -100 and
+ *                 a gradient -y / 1e-12 which pg_softmax_bwd multiplies by p = 0.
+ *   PG_SEG_FOCAL  e = -(a1 y q^g lp + a0 (1 - y) p^g lq)                        (Lin et al. 2017, the binary form on every channel)
+ *                 de/dp = -a1 y (q^g / max(p, 1e-12) - g q^(g-1) lp) - a0 (1 - y) (g p^(g-1) lq - p^g / max(q, 1e-12));
+ *                 for g == 0 the two g * ... terms are absent (never 0 * x): with PG_SEG_FOCAL_ALPHA_NONE that is bce_elem.
+ *                 value scale_focal * sum e, scale_focal = alpha / (Bglobal * C * HW).
+ *   PG_SEG_DICE   per (n, c) over HW: I = sum p y, P = sum p, Y = sum y, D = (2 I + s) / (P + Y + s), s = dice_smooth > 0;
+ *                 value scale_dice * sum_{n,c} (1 - D), scale_dice = alpha / (Bglobal * C);
+ *                 gradient k0[n,c] * y + k1[n,c], k0 = fl32(-2 scale_dice / den), k1 = fl32(scale_dice (2 I + s) / den^2),
+ *                 den = P + Y + s, both formed in fp64 from the fp64 sums.
+ * The scales are formed by the caller in double (as pg_gan_term.scale): each value is this rank's partial of the global mean and the
+ * gradients are seeded for a SUM all-reduce (PG_LOSS_MAE's convention); the loss needs no collective.  Element arithmetic is fp32, in
+ * the order the expressions above are written from the left (-ffp-contract=off); sums and Dice coefficients are fp64.
+ * A NaN in p gives a NaN value and a NaN gradient at that element in every member (the clamps keep it, for any y); under PG_SEG_DICE
+ * the whole (n, c) plane's gradient is NaN.
+ *
+ * Two launches per evaluation:
+ *   pg_seg_loss_reduce      for each (sample n, slab z, channel c) the five sums {I, P, Y, sum e_ce, sum e_focal} over the slab's pixels
+ *                           into ws[((n * nslab + z) * C + c) * 5 + k]; sums the mask does not select are written as 0.
+ *                           nslab = pg_seg_loss_slabs(N, HW) = clamp(HW / 1024, 1, min(128, max(1, 1024 / N))): two slabs from
+ *                           HW = 2048 on.  Slab z holds the pixels z * 256 + t + 256 * nslab * j of the sample; lane t adds its
+ *                           pixels in index order, a wave of 64 lanes by a halving tree, the four waves in wave order.
+ *   pg_seg_loss_value_grad  adds the slabs of every sum in slab order, then
+ *                           *value = fl32(scale_ce * S_ce + scale_focal * S_focal + scale_dice * S_dice), the selected members in that
+ *                           order in fp64, S_x the sum of the member's per-(n, c) terms: lane i of 48 adds the pairs i, i + 48, ... of
+ *                           the (n, c) index n * C + c in index order, then one halving tree;
+ *                           g != NULL: g[(n * HW + i) * ld_g + c] for c < C and nothing else -- pad channels of a wider pixel and
+ *                           everything outside the view stay untouched -- = the selected members' gradients fl32(scale_ce) * de/dp,
+ *                           fl32(scale_focal) * de/dp, k0 y + k1, each rounded to fp32 and added in fp32 in that order.
+ *                           g == NULL (evaluation): the value only, with the same bits.
+ * No floating-point atomics, no workgroup reads what another wrote in the same launch, no last-arriving workgroup: the launch
+ * sequence and the result bits are functions of the arguments alone.  A workgroup of the gradient pass covers pixels of ONE sample and
+ * forms that sample's Dice coefficients from the slabs, four channels at a time: there is no table and no limit on N * C.
+ * `ws`: pg_seg_loss_workspace_bytes(N, HW, C) bytes, 8-byte aligned, written by the first call and read by the second.
+ * PG_EINVAL before any launch, nothing written: a NULL p, y, value or ws; ws misaligned or ws_bytes too small; N, HW or C <= 0; an ld
+ * < C (ld_g only where g is given); terms 0 or with an unknown bit; PG_SEG_CE with C < 2; focal_gamma outside
+ * 0 .. PG_SEG_FOCAL_GAMMA_MAX; focal_alpha neither in (0, 1) nor PG_SEG_FOCAL_ALPHA_NONE; dice_smooth not finite or <= 0 (the settings
+ * are checked whether or not the mask selects their member: pass the defaults 2, PG_SEG_FOCAL_ALPHA_NONE, 1). */
+#define PG_SEG_CE 1
+#define PG_SEG_FOCAL 2
+#define PG_SEG_DICE 4
+#define PG_SEG_FOCAL_GAMMA_MAX 8
+#define PG_SEG_FOCAL_ALPHA_NONE (-1.0f)
+long pg_seg_loss_workspace_bytes(int N, int HW, int C);      /* 0 for N, HW or C <= 0 */
+int pg_seg_loss_slabs(int N, int HW);                        /* nslab; 0 for N or HW <= 0 */
+int pg_seg_loss_reduce(const float* p, int ld_p, const float* y, int ld_y, int N, int HW, int C, int terms, int focal_gamma,
+                       float focal_alpha, void* ws, long ws_bytes, void* stream);
+int pg_seg_loss_value_grad(const void* ws, long ws_bytes, const float* p, int ld_p, const float* y, int ld_y, int N, int HW, int C,
+                           int terms, int focal_gamma, float focal_alpha, float dice_smooth, double scale_ce, double scale_focal,
+                           double scale_dice, float* g, int ld_g, float* value, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,8 @@ OP_BIG2SMALL, OP_SMALL2BIG, OP_WGRAD = 0, 1, 2
 AUG_FLIP, AUG_TRANSLATION, AUG_CUTOUT = 1, 2, 4      # PG_AUG_*
 ACC_BEGIN, ACC_ADD, ACC_CLOSE, ACC_CLOSE_ONLY = 0, 1, 2, 3      # PG_ACC_*
 GAN_LSGAN, GAN_HINGE_D, GAN_HINGE_G, GAN_BCE_LOGITS = 0, 1, 2, 3      # PG_GAN_*
+SEG_CE, SEG_FOCAL, SEG_DICE = 1, 2, 4      # PG_SEG_*
+SEG_FOCAL_GAMMA_MAX, SEG_FOCAL_ALPHA_NONE = 8, -1.0      # PG_SEG_FOCAL_GAMMA_MAX, PG_SEG_FOCAL_ALPHA_NONE
 
 _ERR = {-1: 'PG_EINVAL (bad shape / null or misaligned pointer)', -2: 'PG_EWORKSPACE (workspace too small)',
         -3: 'PG_ELAUNCH (HIP launch failed)'}
@@ -195,6 +197,10 @@ SIGNATURES = {
     'pg_gan_loss_single_max': (_l, []),
     'pg_gan_loss_workspace_bytes': (_l, [_i, ctypes.POINTER(GanTerm)]),
     'pg_gan_loss': (_i, [_i, ctypes.POINTER(GanTerm), _p, _l, _p]),
+    'pg_seg_loss_workspace_bytes': (_l, [_i, _i, _i]),
+    'pg_seg_loss_slabs': (_i, [_i, _i]),
+    'pg_seg_loss_reduce': (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _i, _f, _p, _l, _p]),
+    'pg_seg_loss_value_grad': (_i, [_p, _l, _p, _i, _p, _i, _i, _i, _i, _i, _i, _f, _f, _d, _d, _d, _p, _i, _p, _p]),
 }
 
 _lib = None

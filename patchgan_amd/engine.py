@@ -2343,6 +2343,115 @@ def loss_value_and_grad(p, y, tconst, mode, alpha, grad_out, loss_out, loss_slot
     return loss_finish(h, mode, alpha, grad_out, loss_out, loss_slot, bglobal, gamma)
 
 
+REFERENCE_LOSSES = ('tversky', 'weighted_bce', 'MAE')      # the reference's objectives: pg_loss_reduce_parts / pg_loss_value_grad
+SEG_OBJECTIVES = ('ce', 'focal', 'dice')                   # Trainer.loss_type beyond them, alone or '+'-joined: segloss.hip
+_SEG_BITS = {'ce': L.SEG_CE, 'focal': L.SEG_FOCAL, 'dice': L.SEG_DICE}
+
+
+class SegLossSpec(tuple):
+    """check_seg_loss's result for a new objective: (terms, focal_gamma, focal_alpha, dice_smooth) -- the PG_SEG_* mask and the settings
+    as the entry points take them (focal_alpha None -> PG_SEG_FOCAL_ALPHA_NONE).  Hashable: it is part of the step's kind key."""
+    __slots__ = ()
+    terms = property(lambda s: s[0])
+    focal_gamma = property(lambda s: s[1])
+    focal_alpha = property(lambda s: s[2])
+    dice_smooth = property(lambda s: s[3])
+
+
+def check_seg_loss(loss_type, final_act, C, focal_gamma=2, focal_alpha=None, dice_smooth=1.0):
+    """Trainer.loss_type and its settings against the generator's head (final_act) and channel count C, validated.  None for one of the
+    reference's three names ("not ours": the existing kernels, whatever the settings hold); a SegLossSpec for 'ce', 'focal', 'dice' or
+    a '+'-joined sum of them.  ValueError for an unknown name, a repeated or mixed sum, a head that does not give probabilities in
+    [0, 1] (ce: softmax only, on at least two channels) and a bad setting."""
+    names = ' | '.join(REFERENCE_LOSSES + SEG_OBJECTIVES)
+    if not isinstance(loss_type, str):
+        raise ValueError(f"loss_type must be one of {names} (the last three also '+'-joined, e.g. 'ce+dice'), not {loss_type!r}")
+    if loss_type in REFERENCE_LOSSES:
+        return None
+    members = loss_type.split('+')
+    for m in members:
+        if m in REFERENCE_LOSSES:
+            raise ValueError(f"loss_type = {loss_type!r}: {m!r} does not combine with other objectives (sums are made of "
+                             f"{' | '.join(SEG_OBJECTIVES)} only)")
+        if m not in SEG_OBJECTIVES:
+            raise ValueError(f"loss_type must be one of {names} (the last three also '+'-joined, e.g. 'ce+dice'), not {loss_type!r}")
+    if len(set(members)) != len(members):
+        raise ValueError(f"loss_type = {loss_type!r}: each objective may be used once in a sum")
+    if isinstance(focal_gamma, bool) or not isinstance(focal_gamma, int) or not 0 <= focal_gamma <= L.SEG_FOCAL_GAMMA_MAX:
+        raise ValueError(f"focal_gamma must be an integer in 0 .. {L.SEG_FOCAL_GAMMA_MAX} (the powers are repeated multiplications), "
+                         f"not {focal_gamma!r}")
+    if focal_alpha is not None and (isinstance(focal_alpha, bool) or not isinstance(focal_alpha, (int, float))
+                                    or not 0.0 < float(focal_alpha) < 1.0):
+        raise ValueError(f"focal_alpha must be None or a number in (0, 1), not {focal_alpha!r}")
+    if (isinstance(dice_smooth, bool) or not isinstance(dice_smooth, (int, float)) or not math.isfinite(float(dice_smooth))
+            or not float(dice_smooth) > 0.0):
+        raise ValueError(f"dice_smooth must be a finite number > 0, not {dice_smooth!r}")
+    if focal_alpha is not None and not 0.0 < _f32(focal_alpha) < 1.0:
+        raise ValueError(f"focal_alpha = {focal_alpha!r} is not inside (0, 1) as an fp32 number")
+    if not (0.0 < _f32(dice_smooth) < math.inf):
+        raise ValueError(f"dice_smooth = {dice_smooth!r} is not a finite fp32 number > 0")
+    if 'ce' in members and final_act != 'softmax':
+        raise ValueError(f"loss_type = {loss_type!r}: 'ce' is categorical cross-entropy and needs a generator with final_act='softmax', "
+                         f"not {final_act!r}")
+    if 'ce' in members and int(C) < 2:
+        raise ValueError(f"loss_type = {loss_type!r}: 'ce' needs at least two output channels, not {C}")
+    if final_act not in ('softmax', 'sigmoid'):
+        raise ValueError(f"loss_type = {loss_type!r} needs probabilities in [0, 1]: a generator with final_act='sigmoid' or 'softmax', "
+                         f"not {final_act!r}")
+    terms = 0
+    for m in members:
+        terms |= _SEG_BITS[m]
+    return SegLossSpec((terms, int(focal_gamma), float(focal_alpha) if focal_alpha is not None else None, float(dice_smooth)))
+
+
+def _f32(x):
+    """x as the fp32 number a launch argument carries."""
+    with np.errstate(over='ignore'):
+        return float(np.float32(x))
+
+
+class SegLossBuffers:
+    """Scratch for one evaluation of the new objectives: ws, the partial slabs pg_seg_loss_reduce writes and pg_seg_loss_value_grad
+    adds.  Kept alive by the caller until both launches are enqueued; nothing reads it afterwards."""
+
+    def __init__(self, N, HW, C, device):
+        self.nbytes = int(L.load().pg_seg_loss_workspace_bytes(N, HW, C))
+        self.ws = torch.empty(self.nbytes // 8, dtype=torch.float64, device=device)
+
+
+class PendingSegLoss:
+    """An evaluation of the new objectives between its two launches."""
+    __slots__ = ('buf', 'args')
+
+
+def seg_loss_begin(p, y, spec):
+    """Phase 1 of Trainer.loss_type = 'ce' | 'focal' | 'dice' | a sum, over prediction View p against target View y: ONE launch
+    (pg_seg_loss_reduce), the counterpart of loss_begin.  spec: check_seg_loss's result.  Nothing is exchanged under data parallelism:
+    the objectives are means over samples."""
+    assert not p.bf and not y.bf and (y.N, y.HW, y.C) == (p.N, p.HW, p.C)
+    h = PendingSegLoss()
+    h.buf, h.args = SegLossBuffers(p.N, p.HW, p.C, p.t.device), (p, y, spec)
+    alpha = spec.focal_alpha if spec.focal_alpha is not None else L.SEG_FOCAL_ALPHA_NONE
+    L.check(L.load().pg_seg_loss_reduce(p.ptr(), p.ld, y.ptr(), y.ld, p.N, p.HW, p.C, spec.terms, spec.focal_gamma, alpha,
+                                        h.buf.ws.data_ptr(), h.buf.nbytes, _stream()), 'pg_seg_loss_reduce')
+    return h
+
+
+def seg_loss_finish(h, alpha, grad_out, loss_out, loss_slot, bglobal):
+    """Phase 2: ONE launch (pg_seg_loss_value_grad) writes the value -- this rank's partial of the global mean, seg_alpha times the sum
+    of the members -- into loss_out[loss_slot] and, if grad_out is not None, the gradient wrt p into View grad_out, seeded for the SUM
+    all-reduce.  Returns the scratch buffers (not a result), as loss_finish does."""
+    p, y, spec = h.args
+    assert grad_out is None or (not grad_out.bf and (grad_out.N, grad_out.HW, grad_out.C) == (p.N, p.HW, p.C))
+    a, b, hw, c = float(alpha), float(bglobal), float(p.HW), float(p.C)
+    fa = spec.focal_alpha if spec.focal_alpha is not None else L.SEG_FOCAL_ALPHA_NONE
+    gp, gl = _pl(grad_out)
+    L.check(L.load().pg_seg_loss_value_grad(h.buf.ws.data_ptr(), h.buf.nbytes, p.ptr(), p.ld, y.ptr(), y.ld, p.N, p.HW, p.C, spec.terms,
+                                            spec.focal_gamma, fa, spec.dice_smooth, a / (b * hw), a / (b * c * hw), a / (b * c),
+                                            gp, gl, L.ptr(loss_out, loss_slot), _stream()), 'pg_seg_loss_value_grad')
+    return h.buf
+
+
 GAN_MODES = ('vanilla', 'lsgan', 'hinge')
 
 

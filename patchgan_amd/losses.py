@@ -46,3 +46,44 @@ def hinge_d_loss(d_real, d_fake):
 def hinge_g_loss(d_fake):
     """The generator's side of the hinge objective: -mean d_fake."""
     return -torch.mean(d_fake)
+
+
+# Segmentation objectives on a generator output y_pred (probabilities, NCHW) against y_true (Trainer.loss_type = 'ce' | 'focal' | 'dice';
+# inside Trainer.batch they run as two HIP kernels, pg_seg_loss_reduce / pg_seg_loss_value_grad).  Means over the batch, without seg_alpha.
+def _clamped_log(x):
+    return torch.clamp(torch.log(x), min=-100.)
+
+
+def _ipow(x, k):
+    """x^k by repeated multiplication (k a small non-negative integer; x^0 = 1 also at x = 0)."""
+    out = torch.ones_like(x)
+    for _ in range(k):
+        out = out * x
+    return out
+
+
+def ce_loss(y_true, y_pred):
+    """Categorical cross-entropy on probabilities: the mean over pixels of -sum_c y log p, the log clamped at -100.  A pixel whose
+    y_true is all zero (no listed label) adds nothing and still counts in the mean."""
+    n, _, h, w = y_pred.shape
+    return torch.sum(-y_true * _clamped_log(y_pred)) / (n * h * w)
+
+
+def focal_loss(y_true, y_pred, gamma=2, alpha=None):
+    """Focal loss (Lin et al. 2017), the binary form on every channel: mean -(a1 y (1-p)^gamma log p + a0 (1-y) p^gamma log(1-p)),
+    gamma an integer in 0..8, a1 = alpha and a0 = 1 - alpha, or both 1 for alpha = None; gamma = 0 without alpha is
+    F.binary_cross_entropy."""
+    if isinstance(gamma, bool) or not isinstance(gamma, int) or not 0 <= gamma <= 8:
+        raise ValueError(f"gamma must be an integer in 0 .. 8, not {gamma!r}")
+    a1, a0 = (1., 1.) if alpha is None else (float(alpha), 1. - float(alpha))
+    p, q = y_pred, 1. - y_pred
+    lq = torch.clamp(torch.log1p(-p), min=-100.)
+    e = -(a1 * y_true * _ipow(q, gamma) * _clamped_log(p) + a0 * (1. - y_true) * _ipow(p, gamma) * lq)
+    return torch.mean(e)
+
+
+def dice_loss(y_true, y_pred, smooth=1.0):
+    """Soft Dice per sample and channel: the mean over (n, c) of 1 - (2 sum p y + smooth) / (sum p + sum y + smooth)."""
+    i = torch.sum(y_true * y_pred, dim=(2, 3))
+    d = (2. * i + smooth) / (torch.sum(y_pred, dim=(2, 3)) + torch.sum(y_true, dim=(2, 3)) + smooth)
+    return torch.mean(1. - d)

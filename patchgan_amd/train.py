@@ -160,7 +160,10 @@ def apply_train_params(trainer, train_params):
     the discriminator's inputs; diffaug_of), gan_mode / real_label (Trainer.gan_mode: the adversarial objective; gan_mode_of), betas /
     weight_decay / save_optimizer (Trainer.betas, Trainer.weight_decay: Adam's betas and AdamW's decoupled decay per network;
     Trainer.save_optimizer: optimizer_ep_*.pth beside the checkpoints, for an exact resume; optimizer_of), accumulate
-    (Trainer.accumulate: micro-batches per optimizer step; accumulate_of)."""
+    (Trainer.accumulate: micro-batches per optimizer step; accumulate_of), focal_gamma / focal_alpha / dice_smooth (the settings of
+    loss_type = 'ce' | 'focal' | 'dice' and their '+'-joined sums; seg_loss_of)."""
+    ge = trainer.generator.engine
+    trainer.focal_gamma, trainer.focal_alpha, trainer.dice_smooth = seg_loss_of(train_params, ge.final_act, ge.output_nc)
     trainer.loss_type = train_params['loss_type']
     trainer.seg_alpha = train_params['seg_alpha']
     trainer.ema_decay = train_params.get('ema_decay', None)
@@ -175,6 +178,21 @@ def apply_train_params(trainer, train_params):
                                                        trainer.discriminator.final_act)
     trainer.betas, trainer.weight_decay, trainer.save_optimizer = _optimizer_of_params(train_params)
     trainer.accumulate = accumulate_of(train_params.get('accumulate', None))
+
+
+def seg_loss_of(train_params, final_act, out_channels):
+    """(Trainer.focal_gamma, Trainer.focal_alpha, Trainer.dice_smooth) from the YAML's train_params.focal_gamma (an integer in 0..8;
+    absent = 2), focal_alpha (a number in (0, 1); absent or null = none) and dice_smooth (a finite number > 0; absent = 1), checked
+    together with train_params.loss_type against the generator's head and channel count as Trainer.batch checks them
+    (engine.check_seg_loss): ValueError.  With one of the reference's three loss types the settings are inert and not checked."""
+    from . import engine as E
+    from .trainer import Trainer
+    gamma = train_params.get('focal_gamma', None)
+    smooth = train_params.get('dice_smooth', None)
+    out = (Trainer.focal_gamma if gamma is None else gamma, train_params.get('focal_alpha', None),
+           Trainer.dice_smooth if smooth is None else smooth)
+    E.check_seg_loss(train_params['loss_type'], final_act, out_channels, *out)
+    return out
 
 
 def diffaug_of(policy=None, seed=None):
@@ -228,6 +246,9 @@ def patchgan_train(argv=None):
     gan_mode_of(config['train_params'].get('gan_mode'), config['train_params'].get('real_label'), disc_final_act_of(disc_cfg.get('final_act')))
     _optimizer_of_params(config['train_params'])      # (likewise the optimizer's settings)
     accumulate_of(config['train_params'].get('accumulate'))      # (likewise the accumulation window)
+    # (likewise the segmentation objective, against the generator's head and the mask's channel count)
+    seg_loss_of(config['train_params'], gen_cfg.get('final_activation', 'sigmoid'),
+                len(dataset_params.get('labels', [1])) if dataset_params['type'] == 'COCOStuff' else dataset_params.get('out_channels', 1))
 
     size = dataset_params.get('size', 256)
     augmentation = dataset_params.get('augmentation', 'randomcrop')

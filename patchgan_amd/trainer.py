@@ -26,6 +26,8 @@ Per-step schedule (reference trainer.py:50-115):
    With Trainer.gan_mode / real_label set, or a Discriminator(final_act='none'), the three BCE terms above become the terms of the chosen
    objective (least squares, hinge, BCE with logits), evaluated by pg_gan_loss: one launch for the generator step's term, one for the
    discriminator step's two.
+   With Trainer.loss_type = 'ce' | 'focal' | 'dice' or a sum of them, the segmentation loss's two launches -- one in front of D
+   fwd(fake), one behind it -- are pg_seg_loss_reduce and pg_seg_loss_value_grad instead of the reference objectives' pair.
 
 Data parallelism: one process per GPU (torch.distributed, backend "nccl" = RCCL).  InstanceNorm is per sample,
 so the only exchanges are the SUM all-reduce of the flat gradient buffers and of two loss-normalisation terms
@@ -223,6 +225,25 @@ class Trainer:
     # then the discriminator step's two terms together) in place of two launches per term.  Checked at the top of batch(): ValueError.
     gan_mode = 'vanilla'
     real_label = 1.0
+
+    # Segmentation objectives beyond the reference's three (opt-in): loss_type = 'tversky' | 'weighted_bce' | 'MAE' = off -- the same
+    # launches with the same arguments, the same kind key, the same bits, whatever the three settings below hold.  loss_type = 'ce' |
+    # 'focal' | 'dice', or a '+'-joined sum of them ('ce+dice', 'focal+dice', ...; each once, none of the reference's three): with p the
+    # generator's output, y the target, lp = max(log p, -100), lq = max(log(1 - p), -100), means over the GLOBAL batch B,
+    #   'ce'     seg_alpha / (B HW) sum -y lp: categorical cross-entropy on the softmax output (final_act='softmax', >= 2 channels).  A
+    #            pixel whose y is all zero has no listed label: it adds nothing and still counts in the normaliser.
+    #   'focal'  seg_alpha / (B C HW) sum -(a1 y (1-p)^g lp + a0 (1-y) p^g lq), g = focal_gamma an INTEGER in 0..8 (powers by repeated
+    #            multiplication), a1 = focal_alpha, a0 = 1 - focal_alpha, or a1 = a0 = 1 for focal_alpha = None; g = 0 without alpha is
+    #            F.binary_cross_entropy.  Sigmoid or softmax head.
+    #   'dice'   seg_alpha / (B C) sum_{n,c} (1 - (2 I + s) / (P + Y + s)), I = sum p y, P = sum p, Y = sum y over the pixels of sample n
+    #            and channel c, s = dice_smooth > 0: per sample, not per batch.  Sigmoid or softmax head.
+    # A sum's value and gradient are the sums of its members' under the one seg_alpha.  Two launches in place of the reference pair
+    # (engine.seg_loss_begin / seg_loss_finish -> pg_seg_loss_reduce, pg_seg_loss_value_grad), nothing exchanged under data
+    # parallelism, and a window of `accumulate` micro-batches IS the large batch (the objectives are means over samples).  batch() keeps
+    # its six keys: the members of a sum are not reported separately.  Checked at the top of batch(): ValueError.
+    focal_gamma = 2
+    focal_alpha = None
+    dice_smooth = 1.0
 
     # The optimizer's settings (opt-in, beyond the reference, whose optimizers are optim.Adam(lr, betas=(0.9, 0.999))): None = off -- the
     # same launches with the same arguments, the same kind key, the same files.
@@ -568,6 +589,25 @@ class Trainer:
         fa = self.discriminator.final_act
         return E.check_gan_mode(self.gan_mode, self.real_label, fa) + (fa,)
 
+    # -------------------------------------------------------------------------------------- the segmentation objective
+    def _seg_now(self):
+        """None while loss_type is one of the reference's three, else the validated engine.SegLossSpec of the next step (ValueError)."""
+        ge = self.generator.engine
+        return E.check_seg_loss(self.loss_type, ge.final_act, ge.output_nc, self.focal_gamma, self.focal_alpha, self.dice_smooth)
+
+    def _seg_begin(self, spec, gen, yv, allred):
+        """Phase 1 of the segmentation loss: the reference pair's, or the new objectives' (spec = _seg_now())."""
+        if spec is None:
+            return E.loss_begin(gen, yv, 0.0, self.tversky_beta, allred)
+        return E.seg_loss_begin(gen, yv, spec)
+
+    def _seg_finish(self, spec, pending, grad_out, loss_out, bglobal):
+        """Phase 2: the value into loss_out[0] and, with grad_out, the gradient wrt the generator's output."""
+        if spec is None:
+            return E.loss_finish(pending, _LOSS_MODES[self.loss_type], float(self.seg_alpha), grad_out, loss_out, 0, bglobal,
+                                 self.tversky_gamma)
+        return E.seg_loss_finish(pending, float(self.seg_alpha), grad_out, loss_out, 0, bglobal)
+
     # -------------------------------------------------------------------------------------- the generator's weight average
     @property
     def ema_generator(self):
@@ -673,6 +713,7 @@ class Trainer:
         ge, dev = net.engine, G.flat.device
         if (ge.input_nc, ge.output_nc) != (G.engine.input_nc, G.engine.output_nc) or net.flat.device != dev:
             raise RuntimeError("evaluate(): the generator must have the live generator's channels and device")
+        seg_spec = self._seg_now()      # (ValueError before anything is launched)
         self.flush()
         dist = _dist()
         counts = SegCounts(ge.output_nc, dev)
@@ -693,12 +734,11 @@ class Trainer:
                     xin, yv, gen = fake.channels(0, Cin), real.channels(Cin, Cout), fake.channels(Cin, Cout)
                     loss = torch.empty(1, dtype=torch.float32, device=dev)
                     ge.forward(net.flat, xin, gen, False, 0, sample0=dist.rank * N, bn=net.bn_run())
-                    pending = E.loss_begin(gen, yv, 0.0, self.tversky_beta, allred)
+                    pending = self._seg_begin(seg_spec, gen, yv, allred)
                     E.seg_confusion(gen, yv, self.metric_threshold, counts.t)
                     if hist is not None:
                         E.seg_hist(gen, yv, bins, hist.t)
-                    E.loss_finish(pending, _LOSS_MODES[self.loss_type], float(self.seg_alpha), None, loss, 0, N * dist.world,
-                                  self.tversky_gamma)
+                    self._seg_finish(seg_spec, pending, None, loss, N * dist.world)
                     total += loss
                     nbatches += 1
         finally:
@@ -755,6 +795,7 @@ class Trainer:
         t_host0 = time.perf_counter()
         G, D = self.generator, self.discriminator
         self._gan_now()           # (ValueError before anything is launched)
+        self._seg_now()           # (likewise)
         self._optim_now()         # (likewise)
         self._acc_now()           # (likewise)
         if not train and self.metric_bins is not None:
@@ -921,7 +962,8 @@ class Trainer:
         dw = D.spectral_normalize() if de.spectral else D.flat
         # seg loss, phase 1 (per-sample reductions); under data parallelism its two batch-global terms are summed across
         # ranks on the comm stream while the discriminator's forward pass over the fake batch runs
-        seg_pending = E.loss_begin(gen, yv, 0.0, self.tversky_beta, allred)
+        seg_spec = self._seg_now()
+        seg_pending = self._seg_begin(seg_spec, gen, yv, allred)
         if self.metrics and not train:
             # evaluation step: the confusion counts of G(x) against y, one more pass over the bytes the loss reduction just read (on this
             # stream in every launch mode; never in a training step, so a captured step does not hold it)
@@ -967,8 +1009,7 @@ class Trainer:
         else:
             dc = de.forward(dw, fake_d, ucache=ucache, bn=D.bn_run(0, 1))                     # trainer.py:66
         gseg = E.View.alloc(N, H, W, Cout, dev) if train else None
-        E.loss_finish(seg_pending, _LOSS_MODES[self.loss_type], float(self.seg_alpha), gseg, losses, 0, Bglobal,
-                      self.tversky_gamma)                                                     # trainer.py:71-82
+        self._seg_finish(seg_spec, seg_pending, gseg, losses, Bglobal)                        # trainer.py:71-82
         o = dc.out
         gd = E.View.alloc(o.N, o.H, o.W, 1, dev) if train else None
         if kind_g is None:
@@ -1237,7 +1278,13 @@ class Trainer:
                 # (an evaluation step with the metrics launch is another kind of step than one without: never timed against each other)
                 # (likewise one with the histogram launch of metric_bins)
                 ((float(self.metric_threshold), self.metric_bins) if self.metric_bins is not None else float(self.metric_threshold))
-                if (self.metrics and not train) else None) + self._gan_key()
+                if (self.metrics and not train) else None) + self._gan_key() + self._seg_key()
+
+    def _seg_key(self):
+        # (the term mask and the three settings are launch arguments of the new objectives' kernels: a captured step holds what it was
+        #  captured with.  One of the reference's three: the key is the one without the feature, whatever the settings hold)
+        spec = self._seg_now()
+        return (('seg',) + tuple(spec),) if spec is not None else ()
 
     def _gan_key(self):
         # (the objective's kinds, targets and scales are launch arguments: a captured step holds what it was captured with.  The
