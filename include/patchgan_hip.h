@@ -881,6 +881,36 @@ int pg_seg_loss_reduce(const float* p, int ld_p, const float* y, int ld_y, int N
 int pg_seg_loss_value_grad(const void* ws, long ws_bytes, const float* p, int ld_p, const float* y, int ld_y, int N, int HW, int C,
                            int terms, int focal_gamma, float focal_alpha, float dice_smooth, double scale_ce, double scale_focal,
                            double scale_dice, float* g, int ld_g, float* value, void* stream);
+/* Per-class weights (patchgan_amd's Trainer.class_weights).  Every member's value is linear in the per-(n, c) sums pg_seg_loss_reduce
+ * writes, so the weights enter in phase 2 only: pg_seg_loss_reduce and its workspace are used unchanged, and
+ * pg_seg_loss_value_grad_w is pg_seg_loss_value_grad (the same kernel body, arguments, address forms and summation orders) with
+ * w_c = cw[c], C floats in DEVICE memory, 4-byte aligned, read once per (n, c) pair for the value and once per group of four
+ * channels for the gradient:
+ *   value     each pair's term times (double)w_c before it enters the pair accumulators: w_c S_ce[n,c], w_c S_focal[n,c],
+ *             w_c (1 - D[n,c]); order, scales and the single rounding to float as above.
+ *   gradient  fl32(scale_ce * w_c) and fl32(scale_focal * w_c) (one rounding from double each) in place of fl32(scale_ce) /
+ *             fl32(scale_focal); k0 = fl32(-2 scale_dice w_c / den), k1 = fl32(scale_dice w_c (2 I + s) / den^2), w_c entering in
+ *             fp64.  The element expressions and the order in which a sum's members are added are unchanged.
+ * With every w_c == 1 the value and every gradient element are those of pg_seg_loss_value_grad, bit for bit.  A channel with
+ * w_c == 0 gets a gradient of +-0 wherever p is not NaN; a NaN in p still comes out as NaN in the value and at that element (under
+ * PG_SEG_DICE in the whole (n, c) plane), whatever the weight.
+ * The denominators stay B HW, B C HW and B C: 'ce' is F.cross_entropy(logits, labels, weight=w, reduction='sum') / (B HW), NOT torch's
+ * reduction='mean', which divides by the sum of the weights of the batch's labelled pixels -- a batch-dependent denominator would need
+ * a collective under data parallelism and a window of accumulated micro-batches would no longer be the large batch.
+ * The kernel cannot read the weights before it launches: the caller keeps them finite and >= 0 (engine.check_seg_loss does).
+ * PG_EINVAL before any launch, nothing written: a NULL cw and everything pg_seg_loss_value_grad refuses. */
+int pg_seg_loss_value_grad_w(const void* ws, long ws_bytes, const float* p, int ld_p, const float* y, int ld_y, int N, int HW, int C,
+                             int terms, int focal_gamma, float focal_alpha, float dice_smooth, double scale_ce, double scale_focal,
+                             double scale_dice, const float* cw, float* g, int ld_g, float* value, void* stream);
+/* Per-class pixel counts of a target (what 'balanced' class weights are made of; Trainer.estimate_class_weights): one pass over y
+ * alone, y an fp32 NHWC channel slice as above (any C >= 1 -- not limited to pg_seg_confusion_max_c() --, any ld_y >= C, 4-byte
+ * aligned, 64-bit offsets).  `counts` holds C + 2 64-bit words on the device and the call ADDS to them (the caller zeroes them):
+ *   counts[c]     += pixels with y_c >= 0.5f          (a NaN is not >= 0.5; a soft or multi-hot pixel counts in every such channel)
+ *   counts[C]     += pixels with no channel >= 0.5f   (unlabelled)
+ *   counts[C + 1] += N * HW
+ * Integer sums only (64-bit per-workgroup counters, one integer atomicAdd per non-zero counter): exactly NumPy's counts, in any order.
+ * PG_EINVAL before any launch: NULL y or counts; N, HW or C <= 0; ld_y < C. */
+int pg_seg_label_count(const float* y, int ld_y, int N, int HW, int C, unsigned long long* counts, void* stream);
 
 #ifdef __cplusplus
 }

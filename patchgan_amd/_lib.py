@@ -201,6 +201,8 @@ SIGNATURES = {
     'pg_seg_loss_slabs': (_i, [_i, _i]),
     'pg_seg_loss_reduce': (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _i, _f, _p, _l, _p]),
     'pg_seg_loss_value_grad': (_i, [_p, _l, _p, _i, _p, _i, _i, _i, _i, _i, _i, _f, _f, _d, _d, _d, _p, _i, _p, _p]),
+    'pg_seg_loss_value_grad_w': (_i, [_p, _l, _p, _i, _p, _i, _i, _i, _i, _i, _i, _f, _f, _d, _d, _d, _p, _p, _i, _p, _p]),
+    'pg_seg_label_count': (_i, [_p, _i, _i, _i, _i, _p, _p]),
 }
 
 _lib = None

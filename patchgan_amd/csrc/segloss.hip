@@ -4,6 +4,8 @@
 //
 //   pg_seg_loss_reduce      per (sample, slab, channel) the sums over the slab's pixels of {p y, p, y, e_ce, e_focal}
 //   pg_seg_loss_value_grad  adds the slabs in slab order; workgroup 0 writes the value, the others the gradient of one sample's pixels
+//   pg_seg_loss_value_grad_w  the same kernel body with a per-class weight w_c on every (sample, channel) term (template flag W)
+//   pg_seg_label_count      per-class pixel counts of the target (what 'balanced' class weights are made of): integers only
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <stdint.h>
@@ -45,6 +47,7 @@ struct SegArgs {
     float* g;
     float* value;
     double* ws;
+    const float* cw;                        // per-class weights, C floats (the weighted entry point only)
     double scale_ce, scale_focal, scale_dice;
     long ld_p, ld_y, ld_g;
     int N, HW, C, terms, gamma, nslab, nchunk;
@@ -203,6 +206,9 @@ __global__ __launch_bounds__(SEG_THREADS) void k_seg_loss_reduce(SegArgs a) {
 
 // Phase 2.  Workgroup 0: the value.  Workgroup 1 + n * nchunk + j: the gradient of the pixels j * 256 + tid, + 256 * nchunk, ... of
 // sample n, four channels at a time, the Dice coefficients of those channels formed from the slabs in front of each group.
+// W: every (n, c) term of the value, the two fp32 scales and the Dice coefficients of channel c carry w_c = cw[c], entering in fp64;
+// the weights are read once per pair (value) and once per channel group (gradient), never per pixel.  !W is the code without them.
+template <bool W>
 __global__ __launch_bounds__(SEG_THREADS) void k_seg_loss_value_grad(SegArgs a) {
     __shared__ double sums[SEG_VALUE_TILE * SEG_SUMS];
     __shared__ float coef[8];
@@ -228,9 +234,16 @@ __global__ __launch_bounds__(SEG_THREADS) void k_seg_loss_value_grad(SegArgs a) 
             __syncthreads();
             if (tid < cnt) {
                 const double* q = sums + tid * SEG_SUMS;
-                if (ce) acc_ce += q[3];
-                if (focal) acc_focal += q[4];
-                if (dice) acc_dice += 1.0 - (2.0 * q[0] + s) / (q[1] + q[2] + s);
+                if (W) {
+                    const double w = (double)a.cw[(i0 + tid) % a.C];
+                    if (ce) acc_ce += w * q[3];
+                    if (focal) acc_focal += w * q[4];
+                    if (dice) acc_dice += w * (1.0 - (2.0 * q[0] + s) / (q[1] + q[2] + s));
+                } else {
+                    if (ce) acc_ce += q[3];
+                    if (focal) acc_focal += q[4];
+                    if (dice) acc_dice += 1.0 - (2.0 * q[0] + s) / (q[1] + q[2] + s);
+                }
             }
         }
         if (tid < 64) {
@@ -253,6 +266,18 @@ __global__ __launch_bounds__(SEG_THREADS) void k_seg_loss_value_grad(SegArgs a) 
     const float sf_ce = (float)a.scale_ce, sf_focal = (float)a.scale_focal;
     for (int c0 = 0; c0 < a.C; c0 += 4) {
         const int nc = a.C - c0 < 4 ? a.C - c0 : 4;
+        float sc_ce[4], sc_focal[4];          // the group's fp32 scales: one rounding from double each
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            if (W) {
+                const double w = c < nc ? (double)a.cw[c0 + c] : 0.0;      // (a uniform load per channel of the group)
+                sc_ce[c] = (float)(a.scale_ce * w);
+                sc_focal[c] = (float)(a.scale_focal * w);
+            } else {
+                sc_ce[c] = sf_ce;
+                sc_focal[c] = sf_focal;
+            }
+        }
         if (dice) {
             __syncthreads();      // (the previous group's reads of coef are over)
             if (tid < nc * 3) {
@@ -262,8 +287,9 @@ __global__ __launch_bounds__(SEG_THREADS) void k_seg_loss_value_grad(SegArgs a) 
             __syncthreads();
             if (tid < nc) {
                 const double I = sums[tid * 3], den = sums[tid * 3 + 1] + sums[tid * 3 + 2] + s;
-                coef[tid * 2 + 0] = (float)(-2.0 * a.scale_dice / den);
-                coef[tid * 2 + 1] = (float)(a.scale_dice * (2.0 * I + s) / (den * den));
+                const double sd = W ? a.scale_dice * (double)a.cw[c0 + tid] : a.scale_dice;
+                coef[tid * 2 + 0] = (float)(-2.0 * sd / den);
+                coef[tid * 2 + 1] = (float)(sd * (2.0 * I + s) / (den * den));
             }
             __syncthreads();
         }
@@ -278,11 +304,11 @@ __global__ __launch_bounds__(SEG_THREADS) void k_seg_loss_value_grad(SegArgs a) 
                     float gsum = 0.f;
                     bool first = true;
                     if (ce) {
-                        gsum = sf_ce * seg_ce_grad(p, y);
+                        gsum = sc_ce[c] * seg_ce_grad(p, y);
                         first = false;
                     }
                     if (focal) {
-                        const float gf = sf_focal * seg_focal_grad(p, y, seg_logp(p), seg_logq(p), a.gamma, a.a1, a.a0);
+                        const float gf = sc_focal[c] * seg_focal_grad(p, y, seg_logp(p), seg_logq(p), a.gamma, a.a1, a.a0);
                         gsum = first ? gf : gsum + gf;
                         first = false;
                     }
@@ -330,6 +356,107 @@ SegArgs seg_args(const float* p, int ld_p, const float* y, int ld_y, int N, int 
     return a;
 }
 
+// both phase-2 entry points: the checks, then the kernel without (W = false, cw unused) or with the per-class weights
+template <bool W>
+int seg_value_grad(const void* ws, long ws_bytes, const float* p, int ld_p, const float* y, int ld_y, int N, int HW, int C, int terms,
+                   int focal_gamma, float focal_alpha, float dice_smooth, double scale_ce, double scale_focal, double scale_dice,
+                   const float* cw, float* g, int ld_g, float* value, void* stream) {
+    if (!p || !y || !value || seg_check(N, HW, C, terms, focal_gamma, focal_alpha) != PG_OK || ld_p < C || ld_y < C) return PG_EINVAL;
+    if (!(dice_smooth > 0.f) || !std::isfinite(dice_smooth)) return PG_EINVAL;
+    if (g && ld_g < C) return PG_EINVAL;
+    if (!seg_ws_ok(ws, ws_bytes, N, HW, C)) return PG_EINVAL;
+    SegArgs a = seg_args(p, ld_p, y, ld_y, N, HW, C, terms, focal_gamma, focal_alpha, const_cast<void*>(ws));
+    a.g = g, a.ld_g = ld_g, a.value = value, a.smooth = dice_smooth, a.cw = cw;
+    a.scale_ce = scale_ce, a.scale_focal = scale_focal, a.scale_dice = scale_dice;
+    const long blocks = g ? 1 + (long)N * a.nchunk : 1;
+    if (blocks > 0x7fffffffL) return PG_EINVAL;
+    hipLaunchKernelGGL(k_seg_loss_value_grad<W>, dim3((unsigned)blocks), dim3(SEG_THREADS), 0, (hipStream_t)stream, a);
+    return pg_launch_status();
+}
+
+// ---- per-class pixel counts of the target (pg_seg_label_count) ----------------------------------------------------------------------
+// One pass over y alone: thread t of workgroup b takes the pixels b * 512 + t, + 512 * gridDim, ..., four of them per trip (their loads
+// issued together), four channels at a time.  A wave counts a channel's hits (y_c >= 0.5f: false for a NaN) with one ballot per pixel
+// and ONE lane adds the four popcounts to the workgroup's table of 64-bit counters in LDS (a 64-bit local cannot wrap, whatever N * HW
+// is); the table goes to the 64-bit global words with one integer atomicAdd per non-zero counter when the workgroup is done.  At most
+// 256 workgroups of 512 threads: every workgroup's adds land on the same few words and serialise there.  (Measured on cfg4's target,
+// 8 x 512^2 x 4 in 8-float pixels, and cfg2's, 16 x 256^2 x 1 in 4-float pixels: 21.5 and 12.8 us; the first version -- up to 1024
+// workgroups of 256 threads, one pixel per trip -- took 36.3 and 30.5 us; pg_seg_confusion on the same views 27.7 and 12.2 us.
+// EXPERIMENTS.md.)  The table holds 1024 channels: a wider target is counted table by table, and the pass over the first table looks
+// through the channels behind it only until it finds the pixel's label (the unlabelled count needs every channel).
+// Integer sums only: the result does not depend on the order of arrival.
+constexpr int SEG_COUNT_THREADS = 512;
+constexpr int SEG_COUNT_BLOCKS = 256;
+constexpr int SEG_COUNT_TABLE = 1024;
+constexpr int SEG_COUNT_UNROLL = 4;
+
+__global__ __launch_bounds__(SEG_COUNT_THREADS) void k_seg_label_count(const float* __restrict__ y, long ld_y, long npix, int C,
+                                                                       unsigned long long* __restrict__ counts) {
+    __shared__ unsigned long long tab[SEG_COUNT_TABLE + 1];
+    constexpr int U = SEG_COUNT_UNROLL;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const long stride = (long)gridDim.x * SEG_COUNT_THREADS;
+    const long trips = (npix + stride - 1) / stride;      // the same for every thread: the ballots below see whole waves
+    for (int k0 = 0; k0 < C; k0 += SEG_COUNT_TABLE) {
+        const int kc = C - k0 < SEG_COUNT_TABLE ? C - k0 : SEG_COUNT_TABLE;
+        for (int i = tid; i <= kc; i += SEG_COUNT_THREADS) tab[i] = 0ull;
+        __syncthreads();
+        for (long trip = 0; trip < trips; trip += U) {
+            const float* yp[U];                           // (read only where valid)
+            bool valid[U], any[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const long pix = (trip + u) * stride + (long)blockIdx.x * SEG_COUNT_THREADS + tid;
+                valid[u] = pix < npix;                    // (a trip past the last one lies past npix as well)
+                yp[u] = y + pix * ld_y;
+                any[u] = false;
+            }
+            for (int c0 = 0; c0 < kc; c0 += 4) {
+                const int nc = kc - c0 < 4 ? kc - c0 : 4;
+                f4 v[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    v[u] = f4{0.f, 0.f, 0.f, 0.f};
+                    if (valid[u]) v[u] = seg_load(yp[u] + k0 + c0, nc);
+                }
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    if (c < nc) {
+                        unsigned int hits = 0;
+#pragma unroll
+                        for (int u = 0; u < U; ++u) {
+                            const bool hit = v[u][c] >= 0.5f;
+                            any[u] |= hit;
+                            hits += (unsigned int)__popcll(__ballot(hit));
+                        }
+                        if (lane == 0 && hits) atomicAdd(&tab[c0 + c], (unsigned long long)hits);
+                    }
+                }
+            }
+            if (k0 == 0) {
+                unsigned int none = 0;
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    if (valid[u])
+                        for (int c = kc; c < C && !any[u]; ++c) any[u] = yp[u][c] >= 0.5f;
+                    none += (unsigned int)__popcll(__ballot(valid[u] && !any[u]));
+                }
+                if (lane == 0 && none) atomicAdd(&tab[kc], (unsigned long long)none);
+            }
+        }
+        __syncthreads();
+        for (int i = tid; i < kc; i += SEG_COUNT_THREADS) {
+            const unsigned long long v = tab[i];
+            if (v) atomicAdd(&counts[k0 + i], v);
+        }
+        if (k0 == 0 && tid == 0) {
+            if (tab[kc]) atomicAdd(&counts[C], tab[kc]);
+            if (blockIdx.x == 0) atomicAdd(&counts[(long)C + 1], (unsigned long long)npix);
+        }
+        __syncthreads();
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -354,16 +481,26 @@ int pg_seg_loss_reduce(const float* p, int ld_p, const float* y, int ld_y, int N
 int pg_seg_loss_value_grad(const void* ws, long ws_bytes, const float* p, int ld_p, const float* y, int ld_y, int N, int HW, int C,
                            int terms, int focal_gamma, float focal_alpha, float dice_smooth, double scale_ce, double scale_focal,
                            double scale_dice, float* g, int ld_g, float* value, void* stream) {
-    if (!p || !y || !value || seg_check(N, HW, C, terms, focal_gamma, focal_alpha) != PG_OK || ld_p < C || ld_y < C) return PG_EINVAL;
-    if (!(dice_smooth > 0.f) || !std::isfinite(dice_smooth)) return PG_EINVAL;
-    if (g && ld_g < C) return PG_EINVAL;
-    if (!seg_ws_ok(ws, ws_bytes, N, HW, C)) return PG_EINVAL;
-    SegArgs a = seg_args(p, ld_p, y, ld_y, N, HW, C, terms, focal_gamma, focal_alpha, const_cast<void*>(ws));
-    a.g = g, a.ld_g = ld_g, a.value = value, a.smooth = dice_smooth;
-    a.scale_ce = scale_ce, a.scale_focal = scale_focal, a.scale_dice = scale_dice;
-    const long blocks = g ? 1 + (long)N * a.nchunk : 1;
-    if (blocks > 0x7fffffffL) return PG_EINVAL;
-    hipLaunchKernelGGL(k_seg_loss_value_grad, dim3((unsigned)blocks), dim3(SEG_THREADS), 0, (hipStream_t)stream, a);
+    return seg_value_grad<false>(ws, ws_bytes, p, ld_p, y, ld_y, N, HW, C, terms, focal_gamma, focal_alpha, dice_smooth, scale_ce,
+                                 scale_focal, scale_dice, nullptr, g, ld_g, value, stream);
+}
+
+int pg_seg_loss_value_grad_w(const void* ws, long ws_bytes, const float* p, int ld_p, const float* y, int ld_y, int N, int HW, int C,
+                             int terms, int focal_gamma, float focal_alpha, float dice_smooth, double scale_ce, double scale_focal,
+                             double scale_dice, const float* cw, float* g, int ld_g, float* value, void* stream) {
+    if (!cw) return PG_EINVAL;
+    return seg_value_grad<true>(ws, ws_bytes, p, ld_p, y, ld_y, N, HW, C, terms, focal_gamma, focal_alpha, dice_smooth, scale_ce,
+                                scale_focal, scale_dice, cw, g, ld_g, value, stream);
+}
+
+int pg_seg_label_count(const float* y, int ld_y, int N, int HW, int C, unsigned long long* counts, void* stream) {
+    if (!y || !counts || N <= 0 || HW <= 0 || C <= 0 || ld_y < C) return PG_EINVAL;
+    const long npix = (long)N * HW;
+    const long per = (long)SEG_COUNT_THREADS * SEG_COUNT_UNROLL;
+    long b = (npix + per - 1) / per;
+    if (b > SEG_COUNT_BLOCKS) b = SEG_COUNT_BLOCKS;
+    hipLaunchKernelGGL(k_seg_label_count, dim3((unsigned)b), dim3(SEG_COUNT_THREADS), 0, (hipStream_t)stream, y, (long)ld_y, npix, C,
+                       counts);
     return pg_launch_status();
 }
 

@@ -2350,23 +2350,109 @@ _SEG_BITS = {'ce': L.SEG_CE, 'focal': L.SEG_FOCAL, 'dice': L.SEG_DICE}
 
 class SegLossSpec(tuple):
     """check_seg_loss's result for a new objective: (terms, focal_gamma, focal_alpha, dice_smooth) -- the PG_SEG_* mask and the settings
-    as the entry points take them (focal_alpha None -> PG_SEG_FOCAL_ALPHA_NONE).  Hashable: it is part of the step's kind key."""
-    __slots__ = ()
+    as the entry points take them (focal_alpha None -> PG_SEG_FOCAL_ALPHA_NONE) -- and, with per-class weights set, a fifth member: the
+    weights as a tuple of fp32-rounded floats (without weights the tuple is the four-member one).  Hashable: it is part of the step's
+    kind key.  `cw` is the weights' device buffer (None without weights, or where check_seg_loss was given no device): an attribute,
+    not part of the value."""
+    cw = None
     terms = property(lambda s: s[0])
     focal_gamma = property(lambda s: s[1])
     focal_alpha = property(lambda s: s[2])
     dice_smooth = property(lambda s: s[3])
+    class_weights = property(lambda s: s[4] if len(s) > 4 else None)
 
 
-def check_seg_loss(loss_type, final_act, C, focal_gamma=2, focal_alpha=None, dice_smooth=1.0):
+CLASS_WEIGHT_SCHEMES = ('balanced', 'balanced_sqrt')
+
+
+def check_class_weights(class_weights, C):
+    """Per-class weights validated: None, or a sequence of C numbers, each finite and >= 0 as an fp32 number, at least one > 0 ->
+    None or the tuple of fp32-rounded floats.  ValueError otherwise -- also for a scheme name ('balanced' | 'balanced_sqrt'), which
+    stands for weights that have not been estimated yet (Trainer.estimate_class_weights)."""
+    if class_weights is None:
+        return None
+    if isinstance(class_weights, str):
+        if class_weights in CLASS_WEIGHT_SCHEMES:
+            raise ValueError(f"class_weights = {class_weights!r} has not been resolved yet: call estimate_class_weights(data) (train() "
+                             f"does before its first epoch)")
+        raise ValueError(f"class_weights must be None, a sequence of {C} numbers or one of {' | '.join(CLASS_WEIGHT_SCHEMES)}, "
+                         f"not {class_weights!r}")
+    try:
+        ws = list(class_weights)
+    except TypeError:
+        raise ValueError(f"class_weights must be None or a sequence of {C} numbers, not {class_weights!r}") from None
+    if len(ws) != int(C):
+        raise ValueError(f"class_weights has {len(ws)} entries for {C} output channels")
+    out = []
+    for w in ws:
+        if isinstance(w, (bool, np.bool_)) or not isinstance(w, (int, float, np.integer, np.floating)):
+            raise ValueError(f"class_weights must be numbers, not {w!r}")
+        f = _f32(w)
+        if not math.isfinite(f) or not f >= 0.0:
+            raise ValueError(f"class_weights: {w!r} is not a finite fp32 number >= 0")
+        out.append(f)
+    if not any(f > 0.0 for f in out):
+        raise ValueError("class_weights: at least one weight must be > 0 as an fp32 number")
+    return tuple(out)
+
+
+def class_weights_from_counts(counts, scheme='balanced'):
+    """Weights from per-class pixel counts n_c (the first C words of pg_seg_label_count's result), in float64, rounded to fp32 at the
+    end: f_c = n_c / sum_k n_k; r_c = 1 / f_c ('balanced') or 1 / sqrt(f_c) ('balanced_sqrt'); a class that does not occur takes the
+    largest r among those that do; w = r * C / sum r (the mean weight is 1).  -> a list of C floats.  ValueError for C == 1, for counts
+    that are all zero, a negative count or an unknown scheme."""
+    if scheme not in CLASS_WEIGHT_SCHEMES:
+        raise ValueError(f"scheme must be one of {' | '.join(CLASS_WEIGHT_SCHEMES)}, not {scheme!r}")
+    n = np.asarray(counts, dtype=np.float64).reshape(-1)
+    C = n.size
+    if C < 2:
+        raise ValueError("class weights need at least two classes (one channel has nothing to be balanced against)")
+    if not np.all(np.isfinite(n)) or np.any(n < 0):
+        raise ValueError(f"counts must be finite and >= 0, not {list(counts)!r}")
+    total = n.sum()
+    if not total > 0:
+        raise ValueError("class weights from counts that are all zero")
+    seen = n > 0
+    f = n[seen] / total
+    r = np.empty(C, dtype=np.float64)
+    r[seen] = 1.0 / f if scheme == 'balanced' else 1.0 / np.sqrt(f)
+    r[~seen] = r[seen].max()
+    w = r * C / r.sum()
+    return [float(x) for x in w.astype(np.float32)]
+
+
+_SEG_WEIGHT_BUFFERS = {}      # (weights, device) -> the weights' device buffer, most recently used last
+_SEG_WEIGHT_BUFFERS_MAX = 16
+
+
+def seg_weight_buffer(weights, device):
+    """The device buffer (C floats) of a weights tuple, made on first use -- the one host-to-device copy; a step that has checked its
+    settings up front (Trainer.batch does, ahead of any capture) finds it here.  A captured step keeps its buffer alive itself."""
+    key = (weights, str(torch.device(device)))
+    t = _SEG_WEIGHT_BUFFERS.pop(key, None)
+    if t is None:
+        t = torch.tensor(weights, dtype=torch.float32).to(device)
+    _SEG_WEIGHT_BUFFERS[key] = t
+    while len(_SEG_WEIGHT_BUFFERS) > _SEG_WEIGHT_BUFFERS_MAX:
+        _SEG_WEIGHT_BUFFERS.pop(next(iter(_SEG_WEIGHT_BUFFERS)))
+    return t
+
+
+def check_seg_loss(loss_type, final_act, C, focal_gamma=2, focal_alpha=None, dice_smooth=1.0, class_weights=None, device=None):
     """Trainer.loss_type and its settings against the generator's head (final_act) and channel count C, validated.  None for one of the
     reference's three names ("not ours": the existing kernels, whatever the settings hold); a SegLossSpec for 'ce', 'focal', 'dice' or
     a '+'-joined sum of them.  ValueError for an unknown name, a repeated or mixed sum, a head that does not give probabilities in
-    [0, 1] (ce: softmax only, on at least two channels) and a bad setting."""
+    [0, 1] (ce: softmax only, on at least two channels) and a bad setting.
+    class_weights: None, or C numbers, finite and >= 0 as fp32 numbers with at least one > 0 (check_class_weights); with one of the
+    reference's three names anything but None is a ValueError (they have no per-class weights: the setting would be silently inert).
+    With `device` the spec carries the weights' device buffer (spec.cw)."""
     names = ' | '.join(REFERENCE_LOSSES + SEG_OBJECTIVES)
     if not isinstance(loss_type, str):
         raise ValueError(f"loss_type must be one of {names} (the last three also '+'-joined, e.g. 'ce+dice'), not {loss_type!r}")
     if loss_type in REFERENCE_LOSSES:
+        if class_weights is not None:
+            raise ValueError(f"class_weights needs loss_type = {' | '.join(SEG_OBJECTIVES)} or a sum of them; loss_type = {loss_type!r} "
+                             f"has no per-class weights")
         return None
     members = loss_type.split('+')
     for m in members:
@@ -2401,7 +2487,14 @@ def check_seg_loss(loss_type, final_act, C, focal_gamma=2, focal_alpha=None, dic
     terms = 0
     for m in members:
         terms |= _SEG_BITS[m]
-    return SegLossSpec((terms, int(focal_gamma), float(focal_alpha) if focal_alpha is not None else None, float(dice_smooth)))
+    base = (terms, int(focal_gamma), float(focal_alpha) if focal_alpha is not None else None, float(dice_smooth))
+    weights = check_class_weights(class_weights, C)
+    if weights is None:
+        return SegLossSpec(base)
+    spec = SegLossSpec(base + (weights,))
+    if device is not None:
+        spec.cw = seg_weight_buffer(weights, device)
+    return spec
 
 
 def _f32(x):
@@ -2446,10 +2539,27 @@ def seg_loss_finish(h, alpha, grad_out, loss_out, loss_slot, bglobal):
     a, b, hw, c = float(alpha), float(bglobal), float(p.HW), float(p.C)
     fa = spec.focal_alpha if spec.focal_alpha is not None else L.SEG_FOCAL_ALPHA_NONE
     gp, gl = _pl(grad_out)
+    if spec.class_weights is not None:
+        # per-class weights: the same launch with the weights' device buffer (made with the spec: no copy in here)
+        cw = spec.cw if spec.cw is not None else seg_weight_buffer(spec.class_weights, p.t.device)
+        assert cw.device == p.t.device and cw.numel() == p.C
+        L.check(L.load().pg_seg_loss_value_grad_w(h.buf.ws.data_ptr(), h.buf.nbytes, p.ptr(), p.ld, y.ptr(), y.ld, p.N, p.HW, p.C,
+                                                  spec.terms, spec.focal_gamma, fa, spec.dice_smooth, a / (b * hw), a / (b * c * hw),
+                                                  a / (b * c), cw.data_ptr(), gp, gl, L.ptr(loss_out, loss_slot), _stream()),
+                'pg_seg_loss_value_grad_w')
+        h.buf.cw = cw      # (alive until the launch has run, with the scratch)
+        return h.buf
     L.check(L.load().pg_seg_loss_value_grad(h.buf.ws.data_ptr(), h.buf.nbytes, p.ptr(), p.ld, y.ptr(), y.ld, p.N, p.HW, p.C, spec.terms,
                                             spec.focal_gamma, fa, spec.dice_smooth, a / (b * hw), a / (b * c * hw), a / (b * c),
                                             gp, gl, L.ptr(loss_out, loss_slot), _stream()), 'pg_seg_loss_value_grad')
     return h.buf
+
+
+def seg_label_count(y, counts):
+    """Add the per-class pixel counts of target View y to `counts` (int64 [C + 2] on the device: C classes, unlabelled, pixels): ONE
+    launch (pg_seg_label_count), nothing read back."""
+    assert not y.bf and counts.dtype == torch.int64 and counts.numel() == y.C + 2 and counts.is_contiguous()
+    L.check(L.load().pg_seg_label_count(y.ptr(), y.ld, y.N, y.HW, y.C, counts.data_ptr(), _stream()), 'pg_seg_label_count')
 
 
 GAN_MODES = ('vanilla', 'lsgan', 'hinge')

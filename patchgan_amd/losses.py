@@ -62,28 +62,52 @@ def _ipow(x, k):
     return out
 
 
-def ce_loss(y_true, y_pred):
+def _per_class(class_weights, like):
+    """class_weights (None or C numbers) as a [1, C, 1, 1] tensor beside `like` (NCHW), or None."""
+    if class_weights is None:
+        return None
+    w = torch.as_tensor(class_weights, dtype=like.dtype, device=like.device).reshape(-1)
+    if w.numel() != like.shape[1]:
+        raise ValueError(f"class_weights has {w.numel()} entries for {like.shape[1]} channels")
+    return w.view(1, -1, 1, 1)
+
+
+def ce_loss(y_true, y_pred, class_weights=None):
     """Categorical cross-entropy on probabilities: the mean over pixels of -sum_c y log p, the log clamped at -100.  A pixel whose
-    y_true is all zero (no listed label) adds nothing and still counts in the mean."""
+    y_true is all zero (no listed label) adds nothing and still counts in the mean.
+    class_weights (C numbers w_c): -sum_c w_c y log p, still divided by the number of pixels -- F.cross_entropy(logits, labels,
+    weight=w, reduction='sum') / (N H W), not its weighted 'mean'."""
     n, _, h, w = y_pred.shape
-    return torch.sum(-y_true * _clamped_log(y_pred)) / (n * h * w)
+    e = -y_true * _clamped_log(y_pred)
+    cw = _per_class(class_weights, y_pred)
+    if cw is not None:
+        e = cw * e
+    return torch.sum(e) / (n * h * w)
 
 
-def focal_loss(y_true, y_pred, gamma=2, alpha=None):
+def focal_loss(y_true, y_pred, gamma=2, alpha=None, class_weights=None):
     """Focal loss (Lin et al. 2017), the binary form on every channel: mean -(a1 y (1-p)^gamma log p + a0 (1-y) p^gamma log(1-p)),
     gamma an integer in 0..8, a1 = alpha and a0 = 1 - alpha, or both 1 for alpha = None; gamma = 0 without alpha is
-    F.binary_cross_entropy."""
+    F.binary_cross_entropy.  class_weights (C numbers w_c): channel c's elements times w_c, the mean still over all N C H W elements."""
     if isinstance(gamma, bool) or not isinstance(gamma, int) or not 0 <= gamma <= 8:
         raise ValueError(f"gamma must be an integer in 0 .. 8, not {gamma!r}")
     a1, a0 = (1., 1.) if alpha is None else (float(alpha), 1. - float(alpha))
     p, q = y_pred, 1. - y_pred
     lq = torch.clamp(torch.log1p(-p), min=-100.)
     e = -(a1 * y_true * _ipow(q, gamma) * _clamped_log(p) + a0 * (1. - y_true) * _ipow(p, gamma) * lq)
+    cw = _per_class(class_weights, y_pred)
+    if cw is not None:
+        e = cw * e
     return torch.mean(e)
 
 
-def dice_loss(y_true, y_pred, smooth=1.0):
-    """Soft Dice per sample and channel: the mean over (n, c) of 1 - (2 sum p y + smooth) / (sum p + sum y + smooth)."""
+def dice_loss(y_true, y_pred, smooth=1.0, class_weights=None):
+    """Soft Dice per sample and channel: the mean over (n, c) of 1 - (2 sum p y + smooth) / (sum p + sum y + smooth).
+    class_weights (C numbers w_c): the mean over (n, c) of w_c (1 - D[n, c]), still over all N C pairs."""
     i = torch.sum(y_true * y_pred, dim=(2, 3))
     d = (2. * i + smooth) / (torch.sum(y_pred, dim=(2, 3)) + torch.sum(y_true, dim=(2, 3)) + smooth)
-    return torch.mean(1. - d)
+    t = 1. - d
+    cw = _per_class(class_weights, y_pred)
+    if cw is not None:
+        t = cw.view(1, -1) * t
+    return torch.mean(t)

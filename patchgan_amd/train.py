@@ -161,9 +161,11 @@ def apply_train_params(trainer, train_params):
     weight_decay / save_optimizer (Trainer.betas, Trainer.weight_decay: Adam's betas and AdamW's decoupled decay per network;
     Trainer.save_optimizer: optimizer_ep_*.pth beside the checkpoints, for an exact resume; optimizer_of), accumulate
     (Trainer.accumulate: micro-batches per optimizer step; accumulate_of), focal_gamma / focal_alpha / dice_smooth (the settings of
-    loss_type = 'ce' | 'focal' | 'dice' and their '+'-joined sums; seg_loss_of)."""
+    loss_type = 'ce' | 'focal' | 'dice' and their '+'-joined sums; seg_loss_of), class_weights / class_weight_batches
+    (Trainer.class_weights: per-class weights of those objectives, a list or 'balanced' | 'balanced_sqrt'; class_weights_of)."""
     ge = trainer.generator.engine
     trainer.focal_gamma, trainer.focal_alpha, trainer.dice_smooth = seg_loss_of(train_params, ge.final_act, ge.output_nc)
+    trainer.class_weights, trainer.class_weight_batches = class_weights_of(train_params, ge.final_act, ge.output_nc)
     trainer.loss_type = train_params['loss_type']
     trainer.seg_alpha = train_params['seg_alpha']
     trainer.ema_decay = train_params.get('ema_decay', None)
@@ -193,6 +195,41 @@ def seg_loss_of(train_params, final_act, out_channels):
            Trainer.dice_smooth if smooth is None else smooth)
     E.check_seg_loss(train_params['loss_type'], final_act, out_channels, *out)
     return out
+
+
+def class_weights_of(train_params, final_act, out_channels):
+    """(Trainer.class_weights, Trainer.class_weight_batches) from the YAML's train_params.class_weights -- a list of one number per
+    output channel (finite, >= 0, at least one > 0) or 'balanced' | 'balanced_sqrt' (estimated from the training masks before the first
+    epoch); absent or null = off -- and train_params.class_weight_batches (how many training batches the estimate counts: an integer
+    >= 1; absent or null = all).  Checked with the objective as Trainer.batch checks them (engine.check_seg_loss): ValueError, also
+    for weights beside one of the reference's three loss types, which have none."""
+    from . import engine as E
+    from .trainer import Trainer
+    cw = train_params.get('class_weights', None)
+    nb = train_params.get('class_weight_batches', None)
+    if nb is not None and (isinstance(nb, bool) or not isinstance(nb, int) or nb < 1):
+        raise ValueError(f"class_weight_batches must be an integer >= 1, not {nb!r}")
+    if cw is None:
+        if nb is not None:
+            raise ValueError("class_weight_batches needs class_weights = 'balanced' | 'balanced_sqrt'")
+        return None, None
+    gamma, smooth = train_params.get('focal_gamma', None), train_params.get('dice_smooth', None)
+    settings = (Trainer.focal_gamma if gamma is None else gamma, train_params.get('focal_alpha', None),
+                Trainer.dice_smooth if smooth is None else smooth)
+    if isinstance(cw, str) and cw in E.CLASS_WEIGHT_SCHEMES:
+        # (a scheme: the objective must be one that takes weights, on at least two channels; the values come from the data)
+        if E.check_seg_loss(train_params['loss_type'], final_act, out_channels, *settings) is None:
+            raise ValueError(f"class_weights = {cw!r} needs loss_type = {' | '.join(E.SEG_OBJECTIVES)} or a sum of them; loss_type = "
+                             f"{train_params['loss_type']!r} has no per-class weights")
+        if int(out_channels) < 2:
+            raise ValueError(f"class_weights = {cw!r}: one output channel has nothing to be balanced against")
+        return cw, nb
+    if nb is not None:
+        raise ValueError("class_weight_batches needs class_weights = 'balanced' | 'balanced_sqrt'")
+    if isinstance(cw, tuple):
+        cw = list(cw)
+    E.check_seg_loss(train_params['loss_type'], final_act, out_channels, *settings, cw)
+    return cw, None
 
 
 def diffaug_of(policy=None, seed=None):
@@ -249,6 +286,9 @@ def patchgan_train(argv=None):
     # (likewise the segmentation objective, against the generator's head and the mask's channel count)
     seg_loss_of(config['train_params'], gen_cfg.get('final_activation', 'sigmoid'),
                 len(dataset_params.get('labels', [1])) if dataset_params['type'] == 'COCOStuff' else dataset_params.get('out_channels', 1))
+    # (likewise its per-class weights)
+    class_weights_of(config['train_params'], gen_cfg.get('final_activation', 'sigmoid'),
+                     len(dataset_params.get('labels', [1])) if dataset_params['type'] == 'COCOStuff' else dataset_params.get('out_channels', 1))
 
     size = dataset_params.get('size', 256)
     augmentation = dataset_params.get('augmentation', 'randomcrop')

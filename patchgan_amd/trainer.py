@@ -245,6 +245,27 @@ class Trainer:
     focal_alpha = None
     dice_smooth = 1.0
 
+    # Per-class weights of 'ce' | 'focal' | 'dice' and their sums (opt-in): None = off -- the same launches with the same arguments, the
+    # same kind key, the same bits.  A sequence of C numbers w_c (C the generator's output channels; each finite and >= 0 as an fp32
+    # number, at least one > 0): every (sample, channel) term of every member is multiplied by w_c,
+    #   'ce'     seg_alpha / (B HW) sum_c w_c sum -y_c lp_c    'focal'  seg_alpha / (B C HW) sum_c w_c sum e_c
+    #   'dice'   seg_alpha / (B C) sum_{n,c} w_c (1 - D[n,c])
+    # in training steps and in evaluate().  The denominators do NOT change with the weights: 'ce' is F.cross_entropy(logits, labels,
+    # weight=w, reduction='sum') / (B HW), not torch's reduction='mean', which divides by the sum of the weights of the batch's labelled
+    # pixels -- a batch-dependent denominator would need a collective under data parallelism, and a window of `accumulate`
+    # micro-batches would stop being the large batch.  The weights enter in the second launch only (pg_seg_loss_value_grad_w in place of
+    # pg_seg_loss_value_grad; the reduction pass is unchanged) and live in a device buffer made when the setting is first checked: no
+    # copy inside a step.  Changed weights are another kind of step, as a changed focal_gamma is.
+    # 'balanced' | 'balanced_sqrt': weights still to be estimated from the data -- estimate_class_weights(data) counts the targets'
+    # pixels per class on the device (pg_seg_label_count) and sets w_c proportional to 1 / f_c (1 / sqrt(f_c)), f_c the class's share of
+    # the labelled pixels, with mean 1 (engine.class_weights_from_counts); train() does so on its training data before the first epoch,
+    # at most class_weight_batches batches of it (None = all), and class_weights.json in the save folder keeps the result for a
+    # resumed run (load_last_checkpoint()).
+    # With one of the reference's three loss types anything but None is a ValueError (not silently inert), as is a wrong length, a bad
+    # value or a scheme name that has not been resolved: checked at the top of batch() / evaluate().
+    class_weights = None
+    class_weight_batches = None
+
     # The optimizer's settings (opt-in, beyond the reference, whose optimizers are optim.Adam(lr, betas=(0.9, 0.999))): None = off -- the
     # same launches with the same arguments, the same kind key, the same files.
     #   betas         (beta1, beta2) for both networks, or ((gen_beta1, gen_beta2), (disc_beta1, disc_beta2)); each in [0, 1).  They are
@@ -391,6 +412,7 @@ class Trainer:
         self._resume = None        # load_optimizer_state(): moments, step counts and trainer state the next setup_optimizers() takes over
         self._plateau = None       # train(reduce_on_plateau=True): the two _Plateau objects (optimizer_state() records them)
         self._resume_plateau = None      # their restored state, from setup_optimizers() to the train() that called it
+        self.class_weight_info = None    # estimate_class_weights(): {'scheme', 'counts', 'unlabelled', 'pixels', 'weights'} of the last estimate
 
     # -------------------------------------------------------------------------------------- optimizers
     def setup_optimizers(self, gen_lr=1e-3, dsc_lr=1e-3):
@@ -593,7 +615,73 @@ class Trainer:
     def _seg_now(self):
         """None while loss_type is one of the reference's three, else the validated engine.SegLossSpec of the next step (ValueError)."""
         ge = self.generator.engine
-        return E.check_seg_loss(self.loss_type, ge.final_act, ge.output_nc, self.focal_gamma, self.focal_alpha, self.dice_smooth)
+        if self.class_weights is None:
+            return E.check_seg_loss(self.loss_type, ge.final_act, ge.output_nc, self.focal_gamma, self.focal_alpha, self.dice_smooth)
+        # (the weights' device buffer is made here, by the check at the top of batch() / evaluate(): later checks of the step find it)
+        return E.check_seg_loss(self.loss_type, ge.final_act, ge.output_nc, self.focal_gamma, self.focal_alpha, self.dice_smooth,
+                                self.class_weights, self.generator.flat.device)
+
+    # -------------------------------------------------------------------------------------- per-class weights from the data
+    CLASS_WEIGHTS_FILE = 'class_weights.json'
+
+    def estimate_class_weights(self, data, scheme='balanced', max_batches=None):
+        """Per-class weights from the targets of `data` (an iterable of (x, y) batches as batch() takes them): every target is uploaded
+        as a step uploads it and counted on the device (one pg_seg_label_count launch per batch into one table; the counts are read
+        once, at the end), under a process group every rank counts its shard and the tables are summed by one int64 all-reduce (a
+        COLLECTIVE outside any step: every rank calls it).  -> the weights engine.class_weights_from_counts(counts, scheme) gives, also
+        set as Trainer.class_weights; `class_weight_info` keeps scheme, counts and weights, and rank 0 writes them to
+        class_weights.json in the save folder.  max_batches: count at most that many batches (None = all)."""
+        if scheme not in E.CLASS_WEIGHT_SCHEMES:
+            raise ValueError(f"scheme must be one of {' | '.join(E.CLASS_WEIGHT_SCHEMES)}, not {scheme!r}")
+        if max_batches is not None and (isinstance(max_batches, bool) or not isinstance(max_batches, int) or max_batches < 1):
+            raise ValueError(f"max_batches must be None or an integer >= 1, not {max_batches!r}")
+        G = self.generator
+        C, dev = G.engine.output_nc, G.flat.device
+        if C < 2:
+            raise ValueError("estimate_class_weights(): one output channel has nothing to be balanced against")
+        self.flush()
+        dist = _dist()
+        counts = torch.zeros(C + 2, dtype=torch.int64, device=dev)
+        for i, (x, y) in enumerate(data):
+            if max_batches is not None and i >= max_batches:
+                break
+            x, y, u8, N, H, W, Cin, Cout = self._inputs(x, y)
+            yv = E.View.alloc(N, H, W, Cout, dev)
+            if u8:
+                yv.from_labels(y, self.label_values)
+            else:
+                yv.from_nchw(y)
+            E.seg_label_count(yv, counts)
+        if dist.on:
+            if dist.backend != 'nccl':
+                counts = counts.cpu()
+            dist.dist.all_reduce(counts, op=dist.dist.ReduceOp.SUM)
+        a = [int(v) for v in counts.cpu().numpy()]
+        weights = E.class_weights_from_counts(a[:C], scheme)
+        self.class_weight_info = {'scheme': scheme, 'counts': a[:C], 'unlabelled': a[C], 'pixels': a[C + 1], 'weights': weights}
+        self.class_weights = list(weights)
+        if dist.rank == 0:
+            import json
+            with open(self.savefolder + self.CLASS_WEIGHTS_FILE, 'w') as f:
+                json.dump(self.class_weight_info, f, indent=1)
+        return list(weights)
+
+    def _class_weights_restore(self):
+        """class_weights.json of the save folder, where the setting is the scheme name it was estimated with: the weights of the earlier
+        run (a resumed run does not re-draw the estimate from randomly cropped data).  -> whether they were taken."""
+        path = self.savefolder + self.CLASS_WEIGHTS_FILE
+        if not isinstance(self.class_weights, str) or not os.path.exists(path):
+            return False
+        import json
+        with open(path) as f:
+            info = json.load(f)
+        C = self.generator.engine.output_nc
+        if info.get('scheme') != self.class_weights or len(info.get('weights', ())) != C:
+            return False
+        self.class_weights = list(E.check_class_weights(info['weights'], C))
+        self.class_weight_info = info
+        print(f"Loaded the class weights from {self.CLASS_WEIGHTS_FILE}: {self.class_weights}")
+        return True
 
     def _seg_begin(self, spec, gen, yv, allred):
         """Phase 1 of the segmentation loss: the reference pair's, or the new objectives' (spec = _seg_now())."""
@@ -1523,6 +1611,9 @@ class Trainer:
                    + ([D.sn_bufs, D.sn_eff] + list(D.sn_ws) if D.engine.spectral else [])
                    + ([self._aug_counter] if st.aug_params is not None else [])
                    + (list(self._acc) if self._acc_cur is not None else []))
+        seg_spec = self._seg_now()
+        if seg_spec is not None and seg_spec.cw is not None:
+            st.hold.append(seg_spec.cw)      # (class_weights: the buffer the captured loss launch reads)
         st.ptrs = self._graph_ptrs()
         self._graphs[key] = st
         return st
@@ -1553,6 +1644,17 @@ class Trainer:
             if self._best is None or self._best.metric != self.save_best:
                 self._best = BestTracker(self.save_best)      # (a resumed run keeps what load_last_checkpoint() read back)
         self._metric_bins()      # (ValueError for a bin count pg_seg_hist does not take, or one without `metrics`)
+        if isinstance(self.class_weights, str):
+            # a scheme name that nothing has resolved yet: the estimate, on the training data, before the first epoch
+            scheme = self.class_weights
+            ge = self.generator.engine
+            if E.check_seg_loss(self.loss_type, ge.final_act, ge.output_nc, self.focal_gamma, self.focal_alpha, self.dice_smooth) is None:
+                self._seg_now()      # (one of the reference's three objectives has no per-class weights: ValueError before any pass over the data)
+            self.estimate_class_weights(train_data, scheme, self.class_weight_batches)
+            if _dist().rank == 0:
+                info = self.class_weight_info
+                print(f"Class weights ({scheme}) -- counts: {info['counts']}  unlabelled: {info['unlabelled']} of {info['pixels']} "
+                      f"pixels  weights: {[round(w, 4) for w in info['weights']]}")
         if (lr_decay is not None) and not reduce_on_plateau:
             gen_lr = gen_learning_rate * (lr_decay) ** ((self.start - 1) / (decay_freq))
             dsc_lr = dsc_learning_rate * (lr_decay) ** ((self.start - 1) / (decay_freq))
@@ -1795,6 +1897,7 @@ class Trainer:
         gen_epochs = set(int(os.path.basename(c).replace('generator_ep_', '')[:-4]) for c in gen_ck)
         dsc_epochs = set(int(os.path.basename(c).replace('discriminator_ep_', '')[:-4]) for c in dsc_ck)
         try:
+            self._class_weights_restore()      # (class_weights = a scheme name: the estimate an earlier run left in the folder)
             assert len(gen_epochs) > 0, "No checkpoints found!"
             start = max(gen_epochs.union(dsc_epochs))
             ema_save = f"{self.savefolder}/generator_ema_ep_{start:03d}.pth"
