@@ -46,10 +46,10 @@ __device__ __forceinline__ float decay_one(float p, float decay_mul) {
     return p;
 }
 
-template <bool DEV, bool EMA, bool CLIP = false, bool WD = false>
+template <bool DEV, bool EMA, bool CLIP, bool WD>
 __global__ void k_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                        long n, float lr_over_bc1, float beta1, float beta2, float eps, float sqrt_bc2, const float* __restrict__ scal,
-                       float* __restrict__ ema, float ema_decay, const pg_grad_stat* __restrict__ stat = nullptr, float decay_mul = 1.f) {
+                       float* __restrict__ ema, float ema_decay, const pg_grad_stat* __restrict__ stat, float decay_mul) {
     float coef = 1.f;
     if constexpr (CLIP) {
         if (stat->apply == 0u) return;
@@ -364,24 +364,40 @@ bool adamw_args_ok(float beta1, float beta2, float decay_mul, const float* ema, 
     return !ema || (ema_decay >= 0.f && ema_decay < 1.f);
 }
 
-template <bool DEV>
-void adamw_launch(float* p, const float* g, float* m, float* v, float* ema, long n, float lr_over_bc1, float beta1, float beta2,
-                         float eps, float sqrt_bc2, const float* scalars, float decay_mul, float ema_decay, const pg_grad_stat* stat,
-                         void* stream) {
-    const dim3 grid(blocks_for(n / 4 + 1)), block(256);
-    hipStream_t s = (hipStream_t)stream;
-    if (ema && stat)
-        hipLaunchKernelGGL((k_adam<DEV, true, true, true>), grid, block, 0, s, p, g, m, v, n, lr_over_bc1, beta1, beta2, eps, sqrt_bc2, scalars,
-                           ema, ema_decay, stat, decay_mul);
-    else if (ema)
-        hipLaunchKernelGGL((k_adam<DEV, true, false, true>), grid, block, 0, s, p, g, m, v, n, lr_over_bc1, beta1, beta2, eps, sqrt_bc2, scalars,
-                           ema, ema_decay, (const pg_grad_stat*)nullptr, decay_mul);
-    else if (stat)
-        hipLaunchKernelGGL((k_adam<DEV, false, true, true>), grid, block, 0, s, p, g, m, v, n, lr_over_bc1, beta1, beta2, eps, sqrt_bc2, scalars,
-                           (float*)nullptr, 0.f, stat, decay_mul);
-    else
-        hipLaunchKernelGGL((k_adam<DEV, false, false, true>), grid, block, 0, s, p, g, m, v, n, lr_over_bc1, beta1, beta2, eps, sqrt_bc2, scalars,
-                           (float*)nullptr, 0.f, (const pg_grad_stat*)nullptr, decay_mul);
+// (a null pointer counts as aligned: the entry point has decided already whether it may be null)
+template <class... P>
+bool aligned16(const P*... ptrs) {
+    return (((uintptr_t)ptrs | ...) & 15) == 0;
+}
+
+// The one launch site of k_adam, behind the validation of all eight pg_adam* entry points.  dev and wd are the entry point's (pg_adamw_*
+// is WD also with a multiplier of 1), EMA and CLIP follow the pointers.  Every launch passes every argument; the fillers of the forms
+// without a feature -- scalars null, lr_over_bc1 = sqrt_bc2 = 0 (dev), decay_mul = 1 -- are the callers', ema_decay = 0 without an
+// average is set here.  (The forms stand in the order the code object has always held them -- template kernels are emitted in the
+// order the file first names them --, so the device assembly of two revisions compares file against file.)
+int adam_launch(bool dev, bool wd, float* p, const float* g, float* m, float* v, float* ema, long n, float lr_over_bc1, float beta1, float beta2,
+                float eps, float sqrt_bc2, const float* scalars, float decay_mul, float ema_decay, const pg_grad_stat* stat, void* stream) {
+    auto* kernel = k_adam<false, false, false, false>;
+    switch (dev << 3 | (ema != nullptr) << 2 | (stat != nullptr) << 1 | (int)wd) {          // DEV EMA CLIP WD
+    case 0b1000: kernel = k_adam<true, false, false, false>; break;
+    case 0b0100: kernel = k_adam<false, true, false, false>; break;
+    case 0b1100: kernel = k_adam<true, true, false, false>; break;
+    case 0b0110: kernel = k_adam<false, true, true, false>; break;
+    case 0b0010: kernel = k_adam<false, false, true, false>; break;
+    case 0b1110: kernel = k_adam<true, true, true, false>; break;
+    case 0b1010: kernel = k_adam<true, false, true, false>; break;
+    case 0b0111: kernel = k_adam<false, true, true, true>; break;
+    case 0b0101: kernel = k_adam<false, true, false, true>; break;
+    case 0b0011: kernel = k_adam<false, false, true, true>; break;
+    case 0b0001: kernel = k_adam<false, false, false, true>; break;
+    case 0b1111: kernel = k_adam<true, true, true, true>; break;
+    case 0b1101: kernel = k_adam<true, true, false, true>; break;
+    case 0b1011: kernel = k_adam<true, false, true, true>; break;
+    case 0b1001: kernel = k_adam<true, false, false, true>; break;
+    }
+    hipLaunchKernelGGL(kernel, dim3(blocks_for(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr_over_bc1, beta1, beta2, eps,
+                       sqrt_bc2, scalars, ema, ema ? ema_decay : 0.f, stat, decay_mul);
+    return pg_launch_status();
 }
 
 }  // namespace
@@ -393,43 +409,31 @@ int pg_version(void) { return 2; }
 int pg_adam_step(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,
                  float bc1, float sqrt_bc2, void* stream) {
     if (!p || !g || !m || !v || n <= 0 || bc1 <= 0.f || sqrt_bc2 <= 0.f) return PG_EINVAL;
-    const uintptr_t al = (uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v;
-    if (al & 15) return PG_EINVAL;
-    hipLaunchKernelGGL((k_adam<false, false>), dim3(blocks_for(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr / bc1,
-                       beta1, beta2, eps, sqrt_bc2, (const float*)nullptr, (float*)nullptr, 0.f);
-    return pg_launch_status();
+    if (!aligned16(p, g, m, v)) return PG_EINVAL;
+    return adam_launch(false, false, p, g, m, v, nullptr, n, lr / bc1, beta1, beta2, eps, sqrt_bc2, nullptr, 1.f, 0.f, nullptr, stream);
 }
 
 int pg_adam_step_dev(float* p, const float* g, float* m, float* v, long n, float beta1, float beta2, float eps, const float* scalars,
                      void* stream) {
     if (!p || !g || !m || !v || !scalars || n <= 0) return PG_EINVAL;
-    const uintptr_t al = (uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v;
-    if (al & 15) return PG_EINVAL;
-    hipLaunchKernelGGL((k_adam<true, false>), dim3(blocks_for(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, 0.f, beta1, beta2, eps,
-                       0.f, scalars, (float*)nullptr, 0.f);
-    return pg_launch_status();
+    if (!aligned16(p, g, m, v)) return PG_EINVAL;
+    return adam_launch(true, false, p, g, m, v, nullptr, n, 0.f, beta1, beta2, eps, 0.f, scalars, 1.f, 0.f, nullptr, stream);
 }
 
 int pg_adam_ema_step(float* p, const float* g, float* m, float* v, float* ema, long n, float lr, float beta1, float beta2, float eps,
                      float bc1, float sqrt_bc2, float ema_decay, void* stream) {
     if (!p || !g || !m || !v || !ema || n <= 0 || bc1 <= 0.f || sqrt_bc2 <= 0.f) return PG_EINVAL;
     if (!(ema_decay >= 0.f && ema_decay < 1.f)) return PG_EINVAL;      // (a NaN fails both comparisons)
-    const uintptr_t al = (uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema;
-    if (al & 15) return PG_EINVAL;
-    hipLaunchKernelGGL((k_adam<false, true>), dim3(blocks_for(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr / bc1,
-                       beta1, beta2, eps, sqrt_bc2, (const float*)nullptr, ema, ema_decay);
-    return pg_launch_status();
+    if (!aligned16(p, g, m, v, ema)) return PG_EINVAL;
+    return adam_launch(false, false, p, g, m, v, ema, n, lr / bc1, beta1, beta2, eps, sqrt_bc2, nullptr, 1.f, ema_decay, nullptr, stream);
 }
 
 int pg_adam_ema_step_dev(float* p, const float* g, float* m, float* v, float* ema, long n, float beta1, float beta2, float eps,
                          const float* scalars, float ema_decay, void* stream) {
     if (!p || !g || !m || !v || !ema || !scalars || n <= 0) return PG_EINVAL;
     if (!(ema_decay >= 0.f && ema_decay < 1.f)) return PG_EINVAL;
-    const uintptr_t al = (uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema;
-    if (al & 15) return PG_EINVAL;
-    hipLaunchKernelGGL((k_adam<true, true>), dim3(blocks_for(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, 0.f, beta1, beta2,
-                       eps, 0.f, scalars, ema, ema_decay);
-    return pg_launch_status();
+    if (!aligned16(p, g, m, v, ema)) return PG_EINVAL;
+    return adam_launch(true, false, p, g, m, v, ema, n, 0.f, beta1, beta2, eps, 0.f, scalars, 1.f, ema_decay, nullptr, stream);
 }
 
 long pg_grad_norm_workspace_bytes(long n) { return n > 0 ? (long)norm_blocks(n) * (long)sizeof(double) : 0; }
@@ -448,50 +452,32 @@ int pg_adam_clip_step(float* p, const float* g, float* m, float* v, float* ema, 
                       float bc1, float sqrt_bc2, float ema_decay, const pg_grad_stat* stat, void* stream) {
     if (!p || !g || !m || !v || !stat || n <= 0 || bc1 <= 0.f || sqrt_bc2 <= 0.f) return PG_EINVAL;
     if (ema && !(ema_decay >= 0.f && ema_decay < 1.f)) return PG_EINVAL;
-    const uintptr_t al = (uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema | (uintptr_t)stat;
-    if (al & 15) return PG_EINVAL;
-    if (ema)
-        hipLaunchKernelGGL((k_adam<false, true, true>), dim3(blocks_for(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr / bc1,
-                           beta1, beta2, eps, sqrt_bc2, (const float*)nullptr, ema, ema_decay, stat);
-    else
-        hipLaunchKernelGGL((k_adam<false, false, true>), dim3(blocks_for(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr / bc1,
-                           beta1, beta2, eps, sqrt_bc2, (const float*)nullptr, (float*)nullptr, 0.f, stat);
-    return pg_launch_status();
+    if (!aligned16(p, g, m, v, ema, stat)) return PG_EINVAL;
+    return adam_launch(false, false, p, g, m, v, ema, n, lr / bc1, beta1, beta2, eps, sqrt_bc2, nullptr, 1.f, ema_decay, stat, stream);
 }
 
 int pg_adam_clip_step_dev(float* p, const float* g, float* m, float* v, float* ema, long n, float beta1, float beta2, float eps,
                           const float* scalars, float ema_decay, const pg_grad_stat* stat, void* stream) {
     if (!p || !g || !m || !v || !scalars || !stat || n <= 0) return PG_EINVAL;
     if (ema && !(ema_decay >= 0.f && ema_decay < 1.f)) return PG_EINVAL;
-    const uintptr_t al = (uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema | (uintptr_t)stat;
-    if (al & 15) return PG_EINVAL;
-    if (ema)
-        hipLaunchKernelGGL((k_adam<true, true, true>), dim3(blocks_for(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, 0.f, beta1,
-                           beta2, eps, 0.f, scalars, ema, ema_decay, stat);
-    else
-        hipLaunchKernelGGL((k_adam<true, false, true>), dim3(blocks_for(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, 0.f, beta1,
-                           beta2, eps, 0.f, scalars, (float*)nullptr, 0.f, stat);
-    return pg_launch_status();
+    if (!aligned16(p, g, m, v, ema, stat)) return PG_EINVAL;
+    return adam_launch(true, false, p, g, m, v, ema, n, 0.f, beta1, beta2, eps, 0.f, scalars, 1.f, ema_decay, stat, stream);
 }
 
 int pg_adamw_step(float* p, const float* g, float* m, float* v, float* ema, long n, float lr, float beta1, float beta2, float eps,
                   float bc1, float sqrt_bc2, float decay_mul, float ema_decay, const pg_grad_stat* stat, void* stream) {
     if (!p || !g || !m || !v || n <= 0 || !(bc1 > 0.f) || !(sqrt_bc2 > 0.f)) return PG_EINVAL;
     if (!adamw_args_ok(beta1, beta2, decay_mul, ema, ema_decay)) return PG_EINVAL;
-    const uintptr_t al = (uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema | (uintptr_t)stat;
-    if (al & 15) return PG_EINVAL;
-    adamw_launch<false>(p, g, m, v, ema, n, lr / bc1, beta1, beta2, eps, sqrt_bc2, nullptr, decay_mul, ema_decay, stat, stream);
-    return pg_launch_status();
+    if (!aligned16(p, g, m, v, ema, stat)) return PG_EINVAL;
+    return adam_launch(false, true, p, g, m, v, ema, n, lr / bc1, beta1, beta2, eps, sqrt_bc2, nullptr, decay_mul, ema_decay, stat, stream);
 }
 
 int pg_adamw_step_dev(float* p, const float* g, float* m, float* v, float* ema, long n, float beta1, float beta2, float eps,
                       const float* scalars, float ema_decay, const pg_grad_stat* stat, void* stream) {
     if (!p || !g || !m || !v || !scalars || n <= 0) return PG_EINVAL;
     if (!adamw_args_ok(beta1, beta2, 1.f, ema, ema_decay)) return PG_EINVAL;      // (decay_mul lives on the device: scalars[2])
-    const uintptr_t al = (uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema | (uintptr_t)stat;
-    if (al & 15) return PG_EINVAL;
-    adamw_launch<true>(p, g, m, v, ema, n, 0.f, beta1, beta2, eps, 0.f, scalars, 1.f, ema_decay, stat, stream);
-    return pg_launch_status();
+    if (!aligned16(p, g, m, v, ema, stat)) return PG_EINVAL;
+    return adam_launch(true, true, p, g, m, v, ema, n, 0.f, beta1, beta2, eps, 0.f, scalars, 1.f, ema_decay, stat, stream);
 }
 
 int pg_grad_accum(float* acc, float* g, long n, int mode, float scale, void* stream) {

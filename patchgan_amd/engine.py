@@ -950,14 +950,6 @@ def softmax_bwd(g1, g2, out, dy):
             'pg_softmax_bwd')
 
 
-def adam_step(p, g, m, v, step, lr, beta1=0.9, beta2=0.999, eps=1e-8):
-    """torch.optim.Adam defaults (reference trainer.py:169-172); bias corrections in Python doubles like torch."""
-    bc1 = 1.0 - beta1 ** step
-    bc2 = 1.0 - beta2 ** step
-    L.check(L.load().pg_adam_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), lr, beta1, beta2,
-                                  eps, bc1, math.sqrt(bc2), _stream()), 'pg_adam_step')
-
-
 def adam_scalars(step, lr, beta1=0.9, beta2=0.999, weight_decay=None):
     """(lr / bc1, sqrt(bc2)) as the float32 values pg_adam_step forms from its arguments: what pg_adam_step_dev reads from device memory.
     With a weight_decay also decay_mul(lr, weight_decay), the third float pg_adamw_step_dev reads."""
@@ -966,15 +958,26 @@ def adam_scalars(step, lr, beta1=0.9, beta2=0.999, weight_decay=None):
     return sc if weight_decay is None else sc + (np.float32(decay_mul(lr, weight_decay)),)
 
 
-def adam_step_dev(p, g, m, v, scalars, beta1=0.9, beta2=0.999, eps=1e-8):
-    """adam_step with lr / bc1 and sqrt(bc2) taken from the device tensor `scalars` (2 floats): a launch without step-dependent arguments."""
-    L.check(L.load().pg_adam_step_dev(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), beta1, beta2, eps,
-                                      scalars.data_ptr(), _stream()), 'pg_adam_step_dev')
+def _is_number(x):
+    return not isinstance(x, bool) and isinstance(x, (int, float, np.floating, np.integer))
+
+
+def _one_or_pair(value, one, msg):
+    """A per-network setting as (gen, disc): None -> (None, None), one number -> one(number) for both, a pair whose members may be
+    None -> one(member) of each; ValueError(msg) for a sequence of another length."""
+    if value is None:
+        return None, None
+    if isinstance(value, (tuple, list)):
+        if len(value) != 2:
+            raise ValueError(msg)
+        return tuple(None if x is None else one(x) for x in value)
+    x = one(value)
+    return x, x
 
 
 def check_ema_decay(decay):
     """The decay of the generator's weight average as a float in [0, 1), or ValueError (what pg_adam_ema_step accepts)."""
-    if isinstance(decay, bool) or not isinstance(decay, (int, float, np.floating, np.integer)):
+    if not _is_number(decay):
         raise ValueError(f"ema_decay must be None or a float in [0, 1), not {decay!r}")
     d = float(decay)
     if not (0.0 <= d < 1.0) or not (float(np.float32(d)) < 1.0):        # (the kernel takes it as a float32)
@@ -982,38 +985,16 @@ def check_ema_decay(decay):
     return d
 
 
-def adam_ema_step(p, g, m, v, ema, step, lr, ema_decay, beta1=0.9, beta2=0.999, eps=1e-8):
-    """adam_step, and in the same pass ema += (p_new - ema) * (1 - ema_decay): the weights' exponential moving average."""
-    bc1 = 1.0 - beta1 ** step
-    bc2 = 1.0 - beta2 ** step
-    L.check(L.load().pg_adam_ema_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ema.data_ptr(), p.numel(), lr, beta1,
-                                      beta2, eps, bc1, math.sqrt(bc2), ema_decay, _stream()), 'pg_adam_ema_step')
-
-
-def adam_ema_step_dev(p, g, m, v, ema, scalars, ema_decay, beta1=0.9, beta2=0.999, eps=1e-8):
-    """adam_ema_step with lr / bc1 and sqrt(bc2) taken from the device tensor `scalars` (adam_step_dev); the decay stays a launch argument."""
-    L.check(L.load().pg_adam_ema_step_dev(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ema.data_ptr(), p.numel(), beta1,
-                                          beta2, eps, scalars.data_ptr(), ema_decay, _stream()), 'pg_adam_ema_step_dev')
-
-
 def check_clip_norm(value):
     """Trainer.clip_grad_norm as (gen_max_norm, disc_max_norm), each None or a float > 0 (inf allowed: monitor only), or ValueError.
     `value`: None, one positive number for both networks, or a pair whose members may be None (what pg_grad_norm accepts)."""
+    msg = f"clip_grad_norm must be None, a positive float or a pair of them (members may be None), not {value!r}"
+
     def one(x):
-        if isinstance(x, bool) or not isinstance(x, (int, float, np.floating, np.integer)):
-            raise ValueError(f"clip_grad_norm must be None, a positive float or a pair of them (members may be None), not {value!r}")
-        x = float(x)
-        if not x > 0.0:          # (a NaN fails the comparison)
-            raise ValueError(f"clip_grad_norm must be None, a positive float or a pair of them (members may be None), not {value!r}")
-        return x
-    if value is None:
-        return None, None
-    if isinstance(value, (tuple, list)):
-        if len(value) != 2:
-            raise ValueError(f"clip_grad_norm must be None, a positive float or a pair of them (members may be None), not {value!r}")
-        return tuple(None if x is None else one(x) for x in value)
-    x = one(value)
-    return x, x
+        if not _is_number(x) or not float(x) > 0.0:          # (a NaN fails the comparison)
+            raise ValueError(msg)
+        return float(x)
+    return _one_or_pair(value, one, msg)
 
 
 # struct pg_grad_stat (include/patchgan_hip.h): one 64-byte status block per network, read on the host as one record
@@ -1034,28 +1015,8 @@ def grad_norm(g, max_norm, ws, stat):
                                   _stream()), 'pg_grad_norm')
 
 
-def adam_clip_step(p, g, m, v, ema, step, lr, stat, ema_decay=None, beta1=0.9, beta2=0.999, eps=1e-8):
-    """adam_step (ema None) / adam_ema_step on g * coef, coef and the skip flag read from the status block grad_norm wrote."""
-    bc1 = 1.0 - beta1 ** step
-    bc2 = 1.0 - beta2 ** step
-    L.check(L.load().pg_adam_clip_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ema.data_ptr() if ema is not None else None,
-                                       p.numel(), lr, beta1, beta2, eps, bc1, math.sqrt(bc2), ema_decay if ema is not None else 0.0,
-                                       stat.data_ptr(), _stream()), 'pg_adam_clip_step')
-
-
-def adam_clip_step_dev(p, g, m, v, ema, scalars, stat, ema_decay=None, beta1=0.9, beta2=0.999, eps=1e-8):
-    """adam_clip_step with lr / bc1 and sqrt(bc2) taken from the device tensor `scalars` (adam_step_dev)."""
-    L.check(L.load().pg_adam_clip_step_dev(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ema.data_ptr() if ema is not None else None,
-                                           p.numel(), beta1, beta2, eps, scalars.data_ptr(), ema_decay if ema is not None else 0.0,
-                                           stat.data_ptr(), _stream()), 'pg_adam_clip_step_dev')
-
-
 _BETAS_MSG = "betas must be None, a pair (beta1, beta2) of floats in [0, 1) or a pair of such pairs (generator, discriminator), not {!r}"
 _WD_MSG = "weight_decay must be None, a finite number >= 0 or a pair of them (generator, discriminator; members may be None), not {!r}"
-
-
-def _is_number(x):
-    return not isinstance(x, bool) and isinstance(x, (int, float, np.floating, np.integer))
 
 
 def check_betas(value):
@@ -1084,14 +1045,7 @@ def check_weight_decay(value):
         if not _is_number(x) or not (0.0 <= float(x) < float('inf')):          # (a NaN fails the comparison)
             raise ValueError(_WD_MSG.format(value))
         return float(x) or None
-    if value is None:
-        return None, None
-    if isinstance(value, (tuple, list)):
-        if len(value) != 2:
-            raise ValueError(_WD_MSG.format(value))
-        return tuple(None if x is None else one(x) for x in value)
-    x = one(value)
-    return x, x
+    return _one_or_pair(value, one, _WD_MSG.format(value))
 
 
 def decay_mul(lr, weight_decay):
@@ -1103,23 +1057,41 @@ def decay_mul(lr, weight_decay):
     return dm
 
 
-def adamw_step(p, g, m, v, step, lr, weight_decay, ema=None, ema_decay=None, stat=None, beta1=0.9, beta2=0.999, eps=1e-8):
-    """adam_step on p * (1 - lr * weight_decay): torch.optim.AdamW's decoupled decay, one more multiply in the same pass.  ema / stat
-    as adam_ema_step / adam_clip_step take them, each optional."""
-    bc1 = 1.0 - beta1 ** step
-    bc2 = 1.0 - beta2 ** step
-    L.check(L.load().pg_adamw_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ema.data_ptr() if ema is not None else None,
-                                   p.numel(), lr, beta1, beta2, eps, bc1, math.sqrt(bc2), decay_mul(lr, weight_decay),
-                                   ema_decay if ema is not None else 0.0, stat.data_ptr() if stat is not None else None, _stream()),
-            'pg_adamw_step')
+def adam_entry(ema, stat, weight_decay, dev):
+    """The library entry point of an Adam update from four booleans: is there a weight average, a clipping status block, a decoupled
+    weight decay, and do the step-dependent scalars come from device memory (a step being captured)."""
+    name = 'pg_adamw_step' if weight_decay else 'pg_adam_clip_step' if stat else 'pg_adam_ema_step' if ema else 'pg_adam_step'
+    return name + '_dev' if dev else name
 
 
-def adamw_step_dev(p, g, m, v, scalars, ema=None, ema_decay=None, stat=None, beta1=0.9, beta2=0.999, eps=1e-8):
-    """adamw_step with lr / bc1, sqrt(bc2) and the decay multiplier taken from the device tensor `scalars` (3 floats: adam_scalars with a
-    weight_decay)."""
-    L.check(L.load().pg_adamw_step_dev(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ema.data_ptr() if ema is not None else None,
-                                       p.numel(), beta1, beta2, eps, scalars.data_ptr(), ema_decay if ema is not None else 0.0,
-                                       stat.data_ptr() if stat is not None else None, _stream()), 'pg_adamw_step_dev')
+def adam_update(p, g, m, v, *, step=None, lr=None, scalars=None, ema=None, ema_decay=None, stat=None, weight_decay=None, beta1=0.9,
+                beta2=0.999, eps=1e-8):
+    """One fused Adam pass over the flat fp32 buffers p, g, m, v on the current stream: torch.optim.Adam (reference trainer.py:169-172),
+    bias corrections in Python doubles like torch.  Either `step` and `lr`, or `scalars`: a device tensor holding adam_scalars(...) -- a
+    launch without step-dependent arguments, what a captured step replays.  Options, each None for off, all in the same pass:
+    `ema` (+ `ema_decay`): ema += (p_new - ema) * (1 - ema_decay), the weights' exponential moving average; `stat`: the update runs on
+    g * coef, coef and the skip flag read from the status block grad_norm wrote; `weight_decay`: on p * decay_mul(lr, weight_decay),
+    torch.optim.AdamW's decoupled decay (with `scalars` the multiplier is their third float).  adam_entry names the entry point."""
+    dev = scalars is not None
+    if (step is None) != (lr is None) or dev == (step is not None):
+        raise ValueError("adam_update takes either step and lr or scalars")
+    name = adam_entry(ema is not None, stat is not None, weight_decay is not None, dev)
+    plain = name.startswith('pg_adam_step')
+    args = [p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr()]
+    if not plain:
+        args.append(ema.data_ptr() if ema is not None else None)
+    args.append(p.numel())
+    if dev:
+        args += [beta1, beta2, eps, scalars.data_ptr()]
+    else:
+        args += [lr, beta1, beta2, eps, 1.0 - beta1 ** step, math.sqrt(1.0 - beta2 ** step)]
+        if weight_decay is not None:
+            args.append(decay_mul(lr, weight_decay))
+    if not plain:
+        args.append(ema_decay if ema is not None else 0.0)
+    if stat is not None or weight_decay is not None:
+        args.append(stat.data_ptr() if stat is not None else None)
+    L.check(getattr(L.load(), name)(*args, _stream()), name)
 
 
 def check_accumulate(value):

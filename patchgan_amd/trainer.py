@@ -37,7 +37,7 @@ by the GLOBAL batch so the summed gradient equals the single-process large-batch
 import glob
 import os
 import time
-from collections import defaultdict
+from collections import defaultdict, namedtuple
 
 import numpy as np
 import torch
@@ -62,6 +62,10 @@ DEFER_D_BWD_DP = E._exp_env('PATCHGAN_DEFER_D_BWD_DP') != '0'
 # planner says the halves compute what the whole computes (halves_ok); off = the reference's three passes (A/B switch, tests)
 SHARE_D_FAKE = E._exp_env('PATCHGAN_SHARE_D_FAKE') != '0'
 DEFER_D_BWD = E._exp_env('PATCHGAN_DEFER_D_BWD') != '0'      # two-stream step: the discriminator's backward pass + Adam(D) under the NEXT step's generator forward (A/B switch)
+
+# One network's side of the optimizer (Trainer._opt): i = 0 (generator) | 1 (discriminator) indexes the per-network pairs, t is the
+# Adam step count, scal the network's slice of a captured step's device scalars
+_Opt = namedtuple('_Opt', 'i net m v t lr betas weight_decay max_norm ema ema_decay acc scal')
 
 
 _GC_FREEZES = 0
@@ -463,11 +467,35 @@ class Trainer:
             return ()
         return (('optim',) + self._optim_now(),)
 
+    def _opt(self, which):
+        """Everything per-network of the optimizer for network `which` ('g' | 'd'), as it stands now: the one place that tells the two
+        apart.  Settings are validated (ValueError); m, v, acc and scal are None where the trainer has none (no optimizer yet,
+        accumulation off, no step being captured); ema / ema_decay are the generator's alone and None while the average is off."""
+        i = 0 if which == 'g' else 1
+        decay = self._ema_now() if i == 0 else None
+        max_norm = self._clip_now()[i]
+        betas, wd = self._optim_now()
+        m, v = self._adam[2 * i:2 * i + 2] if self._adam is not None else (None, None)
+        scal = self._adam_dev
+        if scal is not None:
+            k = scal.numel() // 2         # floats per network: 2, or 3 with a decay set (_capture)
+            scal = scal[i * k:(i + 1) * k]
+        return _Opt(i, (self.generator, self.discriminator)[i], m, v, (self._t_g, self._t_d)[i], (self.gen_lr, self.dsc_lr)[i], betas[i], wd[i],
+                    max_norm, self._ema if decay is not None else None, decay, self._acc[i] if self._acc is not None else None, scal)
+
+    def _opt_buffers(self):
+        """The optimizer's device buffers in use now: the moments, the weight average while it is on, clipping's status blocks and
+        workspaces while either network clips (else three Nones: the places stay), the accumulators inside a window.  What a captured
+        step keeps alive besides the gradients, and by whose addresses it is recognised as stale."""
+        ema = self._ema if self._ema_now() is not None else None
+        clip = tuple(self._clip) if (self._clip is not None and self._clip_now() != (None, None)) else (None, None, None)
+        acc = tuple(self._acc) if (self._acc is not None and self._acc_cur is not None) else ()
+        return tuple(self._adam) + clip + (ema,) + acc
+
     def _adam_scalars(self, which, k):
         """The `k` floats (2, or 3 with a decay set for either network) a captured step's Adam launch of network `which` reads."""
-        betas, wd = self._optim_now()
-        i = 0 if which == 'g' else 1
-        sc = E.adam_scalars(self._t_g if i == 0 else self._t_d, self.gen_lr if i == 0 else self.dsc_lr, betas[i][0], betas[i][1], wd[i])
+        o = self._opt(which)
+        sc = E.adam_scalars(o.t, o.lr, o.betas[0], o.betas[1], o.weight_decay)
         return sc + (np.float32(1.0),) * (k - len(sc))
 
     # -------------------------------------------------------------------------------------- gradient-norm clipping
@@ -1256,18 +1284,10 @@ class Trainer:
         """Network `which`'s optimizer update on its flat gradient, on the current stream.  With `accumulate` set this is where the
         gradient joins its window instead: `acc` = (phase, gradients in the window with this one), by default the place of the training
         call being enqueued; only a closing phase goes on to the update, on the window's mean gradient."""
-        net, (m, v) = (self.generator, self._adam[0:2]) if which == 'g' else (self.discriminator, self._adam[2:4])
+        o = self._opt(which)
+        net = o.net
         if acc is Trainer._ACC_CUR:
             acc = self._acc_cur
-        decay = self._ema_now() if which == 'g' else None
-        max_norm = self._clip_now()[0 if which == 'g' else 1]
-        betas, wds = self._optim_now()
-        (b1, b2), wd = (betas[0], wds[0]) if which == 'g' else (betas[1], wds[1])
-        bk = dict(beta1=b1, beta2=b2) if self.betas is not None else {}      # (off: the calls of before, argument for argument)
-        dev = self._adam_dev
-        if dev is not None:
-            k = dev.numel() // 2          # floats per network: 2, or 3 with a decay set (_capture)
-            dev = dev[0:k] if which == 'g' else dev[k:2 * k]
         if which == 'd' and net.engine.spectral:
             # the passes ran on W / sigma: the flat gradient (all-reduced already under data parallelism -- the map is linear in it, and
             # u, v, sigma agree on every rank) becomes the gradient of the stored weights, on this stream, ahead of the norm and Adam
@@ -1277,54 +1297,28 @@ class Trainer:
                 net.spectral_grad_map(net.grad_flat)
         if acc is not None:
             phase, count = acc
-            E.grad_accum(self._acc[0 if which == 'g' else 1], net.grad_flat, phase, E.accum_scale(count))
+            E.grad_accum(o.acc, net.grad_flat, phase, E.accum_scale(count))
             self._acc_launches += 1       # (an enqueued accumulate launch is a commitment of the step, as an update is: batch())
             if phase in ('begin', 'add'):
                 return            # weights, moments, the weight average and the step count stay as they are
         stat = None
-        if max_norm is not None:
+        if o.max_norm is not None:
             # the norm of the whole flat gradient (two short launches) and Adam on g * coef, both behind the gradient on this stream;
             # a non-finite norm skips the update on the device -- the host's step count advances regardless
             self._clip_ensure()
             stat = self._clip_stat(which)
-            E.grad_norm(net.grad_flat, max_norm, self._clip[1 if which == 'g' else 2], stat)
-        if wd is not None:
-            # decoupled weight decay: p * (1 - lr * wd) rides in the same kernel, with the average and the clipping where they are set
-            ema = self._ema if decay is not None else None
-            if dev is not None:
-                E.adamw_step_dev(net.flat, net.grad_flat, m, v, dev, ema, decay, stat, **bk)
-            elif which == 'g':
-                self._t_g += 1
-                E.adamw_step(net.flat, net.grad_flat, m, v, self._t_g, self.gen_lr, wd, ema, decay, stat, **bk)
-            else:
-                self._t_d += 1
-                E.adamw_step(net.flat, net.grad_flat, m, v, self._t_d, self.dsc_lr, wd, ema, decay, stat, **bk)
-        elif stat is not None:
-            ema = self._ema if decay is not None else None
-            if dev is not None:
-                E.adam_clip_step_dev(net.flat, net.grad_flat, m, v, ema, dev, stat, decay, **bk)
-            elif which == 'g':
-                self._t_g += 1
-                E.adam_clip_step(net.flat, net.grad_flat, m, v, ema, self._t_g, self.gen_lr, stat, decay, **bk)
-            else:
-                self._t_d += 1
-                E.adam_clip_step(net.flat, net.grad_flat, m, v, ema, self._t_d, self.dsc_lr, stat, decay, **bk)
-        elif decay is not None:
-            # the generator's weight average rides in the same kernel (5 reads + 4 writes per element instead of 4 + 3 and a second pass)
-            if dev is not None:
-                E.adam_ema_step_dev(net.flat, net.grad_flat, m, v, self._ema, dev, decay, **bk)
-            else:
-                self._t_g += 1
-                E.adam_ema_step(net.flat, net.grad_flat, m, v, self._ema, self._t_g, self.gen_lr, decay, **bk)
-        elif dev is not None:
-            # a step being captured: lr / bc1 and sqrt(bc2) come from device memory (written before every replay, _batch_graph)
-            E.adam_step_dev(net.flat, net.grad_flat, m, v, dev, **bk)
-        elif which == 'g':
-            self._t_g += 1
-            E.adam_step(net.flat, net.grad_flat, m, v, self._t_g, self.gen_lr, **bk)
+            E.grad_norm(net.grad_flat, o.max_norm, self._clip[1 + o.i], stat)
+        # One fused pass (engine.adam_update picks the entry point): the decoupled decay, the clipping coefficient and the generator's
+        # weight average ride in the Adam kernel where they are set.  A step being captured reads lr / bc1, sqrt(bc2) and the decay
+        # multiplier from device memory (written before every replay, _replay, which also advances the step counts); otherwise this
+        # launch is step o.t + 1 and the count advances here.
+        if o.scal is not None:
+            when = dict(scalars=o.scal)
         else:
-            self._t_d += 1
-            E.adam_step(net.flat, net.grad_flat, m, v, self._t_d, self.dsc_lr, **bk)
+            when = dict(step=o.t + 1, lr=o.lr)
+            self._t_g, self._t_d = self._t_g + (1 - o.i), self._t_d + o.i
+        E.adam_update(net.flat, net.grad_flat, o.m, o.v, ema=o.ema, ema_decay=o.ema_decay, stat=stat, weight_decay=o.weight_decay,
+                      beta1=o.betas[0], beta2=o.betas[1], **when)
 
     # -------------------------------------------------------------------------------------- how a step is launched
     def _graph_eligible(self):
@@ -1548,8 +1542,8 @@ class Trainer:
             st.slot = (st.slot + 1) % len(st.host)
             h = host.numpy()
             k = st.scal.numel() // 2
-            h[0:k] = self._adam_scalars('g', k)
-            h[k:2 * k] = self._adam_scalars('d', k)
+            for i, which in enumerate('gd'):
+                h[i * k:(i + 1) * k] = self._adam_scalars(which, k)
             st.scal.copy_(host, non_blocking=True)
         st.graph.replay()
         self._last_gen = st.gen
@@ -1558,10 +1552,7 @@ class Trainer:
 
     def _graph_ptrs(self):
         G, D = self.generator, self.discriminator
-        ema = self._ema if self._ema_now() is not None else None
-        clip = tuple(self._clip) if (self._clip is not None and self._clip_now() != (None, None)) else (None, None, None)
-        acc = tuple(self._acc) if (self._acc is not None and self._acc_cur is not None) else ()
-        return tuple(t.data_ptr() if t is not None else 0 for t in (G.grad_flat, D.grad_flat) + tuple(self._adam) + clip + (ema,) + acc)
+        return tuple(t.data_ptr() if t is not None else 0 for t in (G.grad_flat, D.grad_flat) + self._opt_buffers())
 
     def _capture(self, key, x, y, u8, dims, two=False):
         class _StepGraph:
@@ -1605,12 +1596,10 @@ class Trainer:
         # one, so a replay never writes into memory the allocator has handed to someone else -- and it is captured again if the
         # buffers whose CONTENT matters outside the graph (gradients, moments) were replaced (_graph_ptrs).
         st.hold = (E.cur_exec(dev).buffers() + list(G.engine.__dict__.get('_upool', {}).values())
-                   + list(D.engine.__dict__.get('_upool', {}).values()) + [G.grad_flat, D.grad_flat] + list(self._adam)
-                   + ([self._ema] if self._ema_now() is not None else [])
-                   + (list(self._clip) if (self._clip is not None and self._clip_now() != (None, None)) else [])
+                   + list(D.engine.__dict__.get('_upool', {}).values()) + [G.grad_flat, D.grad_flat]
+                   + [t for t in self._opt_buffers() if t is not None]
                    + ([D.sn_bufs, D.sn_eff] + list(D.sn_ws) if D.engine.spectral else [])
-                   + ([self._aug_counter] if st.aug_params is not None else [])
-                   + (list(self._acc) if self._acc_cur is not None else []))
+                   + ([self._aug_counter] if st.aug_params is not None else []))
         seg_spec = self._seg_now()
         if seg_spec is not None and seg_spec.cw is not None:
             st.hold.append(seg_spec.cw)      # (class_weights: the buffer the captured loss launch reads)
@@ -1854,16 +1843,15 @@ class Trainer:
         from), diffaug_counter (the device word, read here; None without one) and plateau (the two schedules' lr / best / bad inside
         train(reduce_on_plateau=True), else None).  CPU tensors.  Completes a discriminator update in flight."""
         self.flush()
-        G, D = self.generator, self.discriminator
-        betas, wd = self._optim_now()
-        adam = self._adam
-        if adam is None:          # (nothing trained yet: zero moments at step 0, what a fresh optimizer starts from)
-            adam = (torch.zeros_like(G.flat), torch.zeros_like(G.flat), torch.zeros_like(D.flat), torch.zeros_like(D.flat))
+        def section(o):
+            # (nothing trained yet: zero moments at step 0, what a fresh optimizer starts from)
+            m, v = (o.m, o.v) if o.m is not None else (torch.zeros_like(o.net.flat), torch.zeros_like(o.net.flat))
+            return optimizer_section(o.net, m, v, o.t, o.lr, o.betas, o.weight_decay)
         plateau = self._plateau
         return {
             'format': 1,
-            'gen': optimizer_section(G, adam[0], adam[1], self._t_g, self.gen_lr, betas[0], wd[0]),
-            'disc': optimizer_section(D, adam[2], adam[3], self._t_d, self.dsc_lr, betas[1], wd[1]),
+            'gen': section(self._opt('g')),
+            'disc': section(self._opt('d')),
             'trainer': {
                 'epoch': epoch, 'gen_lr': float(self.gen_lr), 'dsc_lr': float(self.dsc_lr), 't_g': int(self._t_g), 't_d': int(self._t_d),
                 'step': int(self._step),

@@ -10,6 +10,7 @@ import torch
 import yaml
 
 from tests import accum_util as A
+from tests import adam_spy as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAN, INF = float('nan'), float('inf')
@@ -160,11 +161,7 @@ def test_the_command_line_validates_before_it_builds_anything():
 
 # ---------------------------------------------------------------------------------------------- 5. the trainer's dispatch
 def _spied(monkeypatch):
-    from patchgan_amd import engine as E
-    calls = []
-    for name in ('adam_step', 'adam_step_dev', 'adam_ema_step', 'adam_clip_step', 'adamw_step', 'grad_norm', 'grad_accum'):
-        monkeypatch.setattr(E, name, lambda *a, _n=name, **k: calls.append((_n, a, k)))
-    return calls
+    return S.spy(monkeypatch)
 
 
 def _call(t):
@@ -199,7 +196,7 @@ def test_dispatch_per_phase(tmp_path, monkeypatch):
     del calls[:]
     assert _call(t) == ('close', 3)
     assert [c[0] for c in calls] == ['grad_accum', 'adam_step', 'grad_accum', 'adam_step']
-    assert calls[0][1][2:] == ('close', A.scale_of(3)) and calls[1][1][4:] == (1, 1e-3) and calls[3][1][4:] == (1, 2e-3)
+    assert calls[0][1][2:] == ('close', A.scale_of(3)) and S.step_lr(calls[1]) == (1, 1e-3) and S.step_lr(calls[3]) == (1, 2e-3)
     assert (t._t_g, t._t_d) == (1, 1) and t._acc_done == 0
     del calls[:]
     # clipping, the weight average and a decay run once per window, on the closed gradient

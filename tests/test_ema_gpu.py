@@ -41,10 +41,10 @@ def test_kernel_against_adam_step_and_float64(n, decay):
     for t in range(1, 6):
         grad = (torch.randn(n, generator=g) * (10.0 ** (t - 3))).to(DEV)          # the gradient scales of test_adam_matches_torch
         e_before = ema[3].clone()
-        E.adam_step(plain[0], grad, plain[1], plain[2], t, 1e-3)
-        E.adam_ema_step(ema[0], grad, ema[1], ema[2], ema[3], t, 1e-3, decay)
+        E.adam_update(plain[0], grad, plain[1], plain[2], step=t, lr=1e-3)
+        E.adam_update(ema[0], grad, ema[1], ema[2], step=t, lr=1e-3, ema=ema[3], ema_decay=decay)
         scal = torch.tensor([float(s) for s in E.adam_scalars(t, 1e-3)], dtype=torch.float32, device=DEV)
-        E.adam_ema_step_dev(dev[0], grad, dev[1], dev[2], dev[3], scal, decay)
+        E.adam_update(dev[0], grad, dev[1], dev[2], scalars=scal, ema=dev[3], ema_decay=decay)
         torch.cuda.synchronize()
         for a, b, name in zip(plain, ema, 'pmv'):
             assert torch.equal(a, b), (t, name)

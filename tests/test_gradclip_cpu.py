@@ -9,6 +9,7 @@ import pytest
 import torch
 import yaml
 
+from tests import adam_spy as S
 from tests import gradclip_util as U
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -128,28 +129,14 @@ def test_bad_setting_raises_value_error(tmp_path, bad):
         t2._kind_key(x, x[:, :1], False, (2, 256, 256, 3, 1), True)
 
 
-class _Spy:
-    """Stands in for patchgan_amd.engine inside the trainer module: records the entry points _adam_step reaches, launches nothing."""
-    LAUNCHERS = ('adam_step', 'adam_step_dev', 'adam_ema_step', 'adam_ema_step_dev', 'grad_norm', 'adam_clip_step', 'adam_clip_step_dev')
-
-    def __init__(self, real):
-        self._real, self.calls = real, []
-
-    def __getattr__(self, name):
-        if name in self.LAUNCHERS:
-            return lambda *a, **k: self.calls.append((name, a, k))
-        return getattr(self._real, name)
-
-
 def _dispatch(monkeypatch, t, dev):
-    from patchgan_amd import trainer as T
-    spy = _Spy(T.E)
-    monkeypatch.setattr(T, 'E', spy)
+    """The entry points _adam_step reaches for both networks (adam_spy: recorded at engine.adam_update, nothing is launched)."""
+    calls = S.spy(monkeypatch)
     t._adam_dev = torch.zeros(4) if dev else None
     t._adam_step('g')
     t._adam_step('d')
     t._adam_dev = None
-    return spy.calls
+    return calls
 
 
 @pytest.mark.parametrize('dev', [False, True], ids=['args', 'dev_scalars'])
@@ -201,9 +188,9 @@ def test_a_value_puts_the_norm_in_front_of_the_clipped_adam(tmp_path, monkeypatc
         assert norm[1][0] is net.grad_flat and norm[1][1] == mx and norm[1][2] is ws
         assert norm[1][3].data_ptr() == t._clip_stat(which).data_ptr()
         assert step[1][0] is net.flat and step[1][1] is net.grad_flat
-        assert (step[1][4] is t._ema) if ema else (step[1][4] is None)          # the average rides along for G only
-        assert step[1][-1] == (decay if ema else None)
-        assert any(getattr(x, 'data_ptr', lambda: None)() == t._clip_stat(which).data_ptr() for x in step[1][5:])
+        assert (step[2]['ema'] is t._ema) if ema else (step[2]['ema'] is None)          # the average rides along for G only
+        assert step[2]['ema_decay'] == (decay if ema else None)
+        assert step[2]['stat'].data_ptr() == t._clip_stat(which).data_ptr()
     assert [c[0] for c in calls] == want
     # the host's step counts advance as without the feature (a captured step's are advanced by the replay)
     assert (t._t_g, t._t_d) == ((t0[0], t0[1]) if dev else (t0[0] + 1, t0[1] + 1))

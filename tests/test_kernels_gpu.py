@@ -463,7 +463,7 @@ def test_adam_matches_torch():
         grad = torch.randn(n, generator=g) * (10.0 ** (t - 3))
         ref.grad = grad.clone()
         opt.step()
-        E.adam_step(p, grad.to(DEV), m, v, t, 1e-3)
+        E.adam_update(p, grad.to(DEV), m, v, step=t, lr=1e-3)
     torch.cuda.synchronize()
     assert (p.cpu() - ref.detach()).abs().max().item() < 1e-6
 

@@ -11,6 +11,7 @@ import torch
 import yaml
 from torch import nn
 
+from tests import adam_spy as S
 from tests import optim_util as U
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -192,31 +193,32 @@ def test_apply_train_params_and_trainer_checks(tmp_path):
 
 
 def test_dispatch_and_kind_key(tmp_path, monkeypatch):
-    """Which engine call _adam_step makes, with which betas: a default trainer makes the calls of before with (0.9, 0.999); a network
-    with a decay takes adamw_step with ema / stat as the other settings say."""
+    """Which entry point _adam_step reaches (adam_spy: recorded at engine.adam_update), with which betas: a default trainer makes the
+    calls of before with (0.9, 0.999); a network with a decay takes adamw_step with ema / stat as the other settings say."""
     from patchgan_amd import engine as E
-    calls = []
-    for name in ('adam_step', 'adam_step_dev', 'adam_ema_step', 'adam_ema_step_dev', 'adam_clip_step', 'adam_clip_step_dev', 'adamw_step',
-                 'adamw_step_dev', 'grad_norm'):
-        monkeypatch.setattr(E, name, lambda *a, _n=name, **k: calls.append((_n, a, k)))
+    calls = S.spy(monkeypatch)
     t = _trainer(tmp_path)
     t.setup_optimizers(1e-3, 2e-3)
     t.generator.ensure_grad_flat(), t.discriminator.ensure_grad_flat()
     t._adam_step('g'), t._adam_step('d')
     assert [c[0] for c in calls] == ['adam_step', 'adam_step']
-    assert calls[0][1][4:] == (1, 1e-3) and calls[1][1][4:] == (1, 2e-3) and not calls[0][2] and not calls[1][2]      # the calls of before
+    assert S.step_lr(calls[0]) == (1, 1e-3) and S.step_lr(calls[1]) == (1, 2e-3)
+    assert S.betas(calls[0]) == (0.9, 0.999) and S.betas(calls[1]) == (0.9, 0.999)      # the calls of before: torch.optim.Adam's betas
+    assert all(c[2][k] is None for c in calls for k in ('scalars', 'ema', 'ema_decay', 'stat', 'weight_decay')) and calls[0][2]['eps'] == 1e-8
     del calls[:]
     t.betas = ((0.5, 0.999), (0.0, 0.9))
     t._adam_step('g'), t._adam_step('d')
     assert [c[0] for c in calls] == ['adam_step', 'adam_step']
-    assert calls[0][1][4:] == (2, 1e-3) and calls[0][2] == dict(beta1=0.5, beta2=0.999)
-    assert calls[1][1][4:] == (2, 2e-3) and calls[1][2] == dict(beta1=0.0, beta2=0.9)
+    assert S.step_lr(calls[0]) == (2, 1e-3) and S.betas(calls[0]) == (0.5, 0.999)
+    assert S.step_lr(calls[1]) == (2, 2e-3) and S.betas(calls[1]) == (0.0, 0.9)
     assert t._optim_key() == (('optim', ((0.5, 0.999), (0.0, 0.9)), (None, None)),)
     del calls[:]
     t.weight_decay = (1e-2, None)
     t._adam_step('g'), t._adam_step('d')
     assert [c[0] for c in calls] == ['adamw_step', 'adam_step']
-    assert calls[0][1][4:] == (3, 1e-3, 1e-2, None, None, None) and calls[0][2] == dict(beta1=0.5, beta2=0.999)
+    k = calls[0][2]
+    assert S.step_lr(calls[0]) == (3, 1e-3) and (k['weight_decay'], k['ema'], k['ema_decay'], k['stat']) == (1e-2, None, None, None)
+    assert S.betas(calls[0]) == (0.5, 0.999)
     del calls[:]
     t.gen_lr = 5e-4          # the multiplier follows the step's learning rate
     t.ema_decay, t.clip_grad_norm = 0.99, (1.0, None)
@@ -224,14 +226,15 @@ def test_dispatch_and_kind_key(tmp_path, monkeypatch):
     t._clip = (None, None, None)
     t._adam_step('g')
     assert [c[0] for c in calls] == ['grad_norm', 'adamw_step']
-    a = calls[1][1]
-    assert a[4:7] == (4, 5e-4, 1e-2) and a[7] is t._ema and a[8:] == (0.99, 'STAT') and calls[1][2] == dict(beta1=0.5, beta2=0.999)
+    k = calls[1][2]
+    assert S.step_lr(calls[1]) + (k['weight_decay'],) == (4, 5e-4, 1e-2) and k['ema'] is t._ema and (k['ema_decay'], k['stat']) == (0.99, 'STAT')
+    assert S.betas(calls[1]) == (0.5, 0.999)
     del calls[:]
     # a step being captured: three floats per network, the network without a decay reads the first two of its three
     t._adam_dev = torch.arange(6.0)
     t._adam_step('g'), t._adam_step('d')
     assert [c[0] for c in calls] == ['grad_norm', 'adamw_step_dev', 'adam_step_dev']
-    assert calls[1][1][4].tolist() == [0.0, 1.0, 2.0] and calls[2][1][4].tolist() == [3.0, 4.0, 5.0]
+    assert calls[1][2]['scalars'].tolist() == [0.0, 1.0, 2.0] and calls[2][2]['scalars'].tolist() == [3.0, 4.0, 5.0]
     t._t_g, t._t_d = 7, 9
     assert [float(x) for x in t._adam_scalars('g', 3)] == [float(x) for x in E.adam_scalars(7, 5e-4, 0.5, 0.999, 1e-2)]
     assert [float(x) for x in t._adam_scalars('d', 3)] == [float(x) for x in E.adam_scalars(9, 2e-3, 0.0, 0.9)] + [1.0]

@@ -96,11 +96,11 @@ def accum(mode):
     return events(lambda: E.grad_accum(acc, g, mode, E.accum_scale(K)))
 
 
-kern = {'parameters': n, 'adam_ms': events(lambda: E.adam_step(p, g, m, v, 100, 1e-3))}
+kern = {'parameters': n, 'adam_ms': events(lambda: E.adam_update(p, g, m, v, step=100, lr=1e-3))}
 bytes_per = {'begin': 8, 'add': 12, 'close': 12, 'close_only': 8}
 for mode in bytes_per:
     kern[mode + '_ms'] = accum(mode)
-kern['adam_again_ms'] = events(lambda: E.adam_step(p, g, m, v, 100, 1e-3))
+kern['adam_again_ms'] = events(lambda: E.adam_update(p, g, m, v, step=100, lr=1e-3))
 kern['tb_per_s'] = dict({mode: round(b * n / (kern[mode + '_ms'][0] * 1e-3) / 1e12, 3) for mode, b in bytes_per.items()},
                         adam=round(28.0 * n / (min(kern['adam_ms'][0], kern['adam_again_ms'][0]) * 1e-3) / 1e12, 3))
 med = {k: statistics.median(val) for k, val in ms.items()}

@@ -77,8 +77,8 @@ for name, net in (('G', G), ('D', D)):
     stat = torch.zeros(8, dtype=torch.float64, device=dev)
     kern[name] = {'parameters': n,
                   'grad_norm_ms': events(lambda: E.grad_norm(g, 1e30, ws, stat)),
-                  'adam_step_ms': events(lambda: E.adam_step(p, g, m, v, 10, 1e-3)),
-                  'adam_clip_step_ms': events(lambda: E.adam_clip_step(p, g, m, v, None, 10, 1e-3, stat))}
+                  'adam_step_ms': events(lambda: E.adam_update(p, g, m, v, step=10, lr=1e-3)),
+                  'adam_clip_step_ms': events(lambda: E.adam_update(p, g, m, v, step=10, lr=1e-3, stat=stat))}
     kern[name]['grad_norm_GBps'] = round(4 * n / kern[name]['grad_norm_ms'] / 1e6, 1)
 print(json.dumps({'metric': 'cfg2 training step with Trainer.clip_grad_norm, ms per step (median of rounds; min..max)',
                   'rounds': ROUNDS, 'steps_per_round': STEPS, 'launch_mode': modes, 'clip_values': [round(c, 5) for c in clip],

@@ -71,9 +71,9 @@ n = legs['default'].generator.flat.numel()
 p, g, m, v = (torch.randn(n, device=dev) * s for s in (0.02, 1e-3, 1e-3, 0.0))
 v = v + 1e-6
 kern = {'parameters': n,
-        'adam_ms': events(lambda: E.adam_step(p, g, m, v, 100, 1e-3)),
-        'adam_again_ms': events(lambda: E.adam_step(p, g, m, v, 100, 1e-3)),
-        'adamw_ms': events(lambda: E.adamw_step(p, g, m, v, 100, 1e-3, 1e-2, beta1=0.5, beta2=0.999))}
+        'adam_ms': events(lambda: E.adam_update(p, g, m, v, step=100, lr=1e-3)),
+        'adam_again_ms': events(lambda: E.adam_update(p, g, m, v, step=100, lr=1e-3)),
+        'adamw_ms': events(lambda: E.adam_update(p, g, m, v, step=100, lr=1e-3, weight_decay=1e-2, beta1=0.5, beta2=0.999))}
 kern['adamw_tb_per_s'] = round(28.0 * n / (kern['adamw_ms'][0] * 1e-3) / 1e12, 3)
 med = {k: statistics.median(val) for k, val in ms.items()}
 print(json.dumps({'metric': 'cfg2 training step, betas + weight_decay set for both networks against the default step, ms per step '
